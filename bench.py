@@ -14,7 +14,11 @@ scaling, no data-path collective (scan-to-map ICPs of one trajectory are
 sequential).  The barrier and the max-over-ranks timing use
 torch.distributed (RCCL).
 
-The JSON line also carries
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: `roofline`
+and `cpu_baseline` are null there, and nothing else is measured.  `--dump-outputs DIR` writes what the last timed step
+returned (dump_outputs).  With `--full` the default workload also measures its companion figures (fixed-30 iterations,
+two contexts, a batch no step repeats, host clouds), the kernels' HIP-event profile, the CPU baseline and the other
+BASELINE configs as `workloads` legs; the `--no-*` options switch single ones of them off again.  The JSON line then carries
   roofline     kNN kernel (dominant): algorithmic bytes per launch
                ((20 N + 12 M) per active problem) / the kernel's
                mean duration measured with HIP events on the context's stream,
@@ -94,6 +98,20 @@ def compact_line(full: dict) -> dict:
 
 
 FULL_RECORD_NAME = "bench_full.json"
+
+
+STATS_FIELDS = ("status", "iterations", "converged", "max_iter_reached", "overlap", "residual", "trim_limit", "n_kept", "n_finite", "cov")
+
+
+def dump_outputs(path, T, st):
+    """--dump-outputs DIR: what the caller of the timed path received from its last step -- every problem's pose (`T`, B x 4 x 4)
+    and its pgicp_stats record, one field per file (`cov` B x 6 x 6) -- as DIR/<name>.npy in float64, in problem order."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"T": np.asarray(T, dtype=np.float64)}
+    for k in STATS_FIELDS:
+        arrays[k] = np.asarray([s[k] for s in st], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def write_full_record(full: dict):
@@ -1321,7 +1339,7 @@ def workload_legs(args, world, rank):
     return (legs if rank == 0 else None), lc_leg
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -1331,8 +1349,14 @@ def main():
     ap.add_argument("--n-scan", type=int, default=100_000)
     ap.add_argument("--n-map", type=int, default=1_000_000)
     ap.add_argument("--fixed-iters", action="store_true", help="disable the Differential checker: exactly 30 iterations")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: after the timed steps also measure the companion figures, the kernels' HIP-event profile "
+                         "(roofline), the CPU baseline and the other BASELINE configs' legs (`workloads`); a plain run measures the "
+                         "headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="default workload: write what the last timed step returned (poses and per-problem stats) as DIR/<name>.npy")
     ap.add_argument("--no-fixed30", action="store_true",
-                    help="skip the companion figure: by default, after the timed run, one step is also timed with the Differential "
+                    help="skip the companion figure: with --full, after the timed run, one step is also timed with the Differential "
                          "checker disabled (exactly 30 iterations per scan, SURVEY.md section 8(d)) and reported as `fixed_30_iterations`; "
                          "pass this for a kernel trace that should hold only the metric's launches")
     ap.add_argument("--with-fixed30", action="store_true", help="(the default now; kept so that older command lines still parse)")
@@ -1348,7 +1372,7 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=64, help="scans of the CPU baseline's batch (at least one per host core)")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-host-input", action="store_true",
-                    help="skip the PCIe-inclusive companion figure: by default the timed steps are repeated with the scans in HOST "
+                    help="skip the PCIe-inclusive companion figure: with --full the timed steps are repeated with the scans in HOST "
                          "memory (pinned, and pageable), uploaded one step ahead on the context's copy stream (pgicp_upload_f32) while "
                          "the current step aligns; reported as `host_input`, never as `value`")
     ap.add_argument("--streams", type=int, default=1,
@@ -1378,14 +1402,27 @@ def main():
     ap.add_argument("--lc-contexts", type=int, default=1, help="loopclosure: sub-batches of a rank's shard aligned concurrently on this many contexts")
     ap.add_argument("--shard-proxy", action="store_true",
                     help="loopclosure at N = 1: also time every rank's LPT shard of a 2-, 4- and 8-rank job alone on this GPU and report "
-                         "the predicted multi-GPU speed-up (`shard_proxy`; always on in the default line's loop_closure leg)")
+                         "the predicted multi-GPU speed-up (`shard_proxy`; always on in the --full line's loop_closure leg)")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="scan2map: skip the `workloads` legs the default line carries next to the headline (stream, loop closure, "
+                    help="scan2map: skip the `workloads` legs the --full line carries next to the headline (stream, loop closure, "
                          "SLAM -- BASELINE.json configs[2..4], each with its own roofline and cpu_baseline, never `value`)")
     ap.add_argument("--prepare-only", action="store_true",
                     help="generate + cache the synthetic workload and exit (run this before a rocprofv3 --pmc pass: the "
                          "generator forks worker processes, which must not happen under the counter profiler)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "scan2map":
+        ap.error("--dump-outputs writes the default workload's outputs")
+    if args.workload == "scan2map" and not args.full:
+        # a plain run measures the headline alone: the companion figures, the profile replay, the CPU baseline and the
+        # other configs' legs are --full's
+        args.no_cpu_baseline = args.no_profile = args.no_fixed30 = args.no_host_input = args.no_workloads = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # `--gpus N` without a launcher: start the N ranks ourselves (torch.distributed.run sets WORLD_SIZE; then we ARE a rank)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.prepare_only:
@@ -1510,6 +1547,8 @@ def main():
 
     # accuracy of what was timed (not part of the metric, guards against a fast wrong answer)
     T, st = last
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, T, st)
     err_t = [float(np.linalg.norm((np.linalg.inv(w.T_truth[b % len(d_scans)]) @ T[b])[:3, 3])) for b in range(B)
              if st[b]["status"] == 0]
 

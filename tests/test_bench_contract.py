@@ -1,9 +1,10 @@
-"""The bench line's contract, checked on the round's recorded run (`python bench.py --steps 20 --warmup 5` on the GPU box):
+"""The bench line's contract, checked on the round's recorded run (`python bench.py --full --steps 20 --warmup 5` on an MI355X):
 profiles/rNN_bench_n1.json is the LINE bench.py printed (round 6 on: the short form of bench.compact_line), and
 profiles/rNN_bench_n1_full.json the full record it wrote to bench_full.json (up to round 5 the line WAS the full record).
 Checked: the fields the driver reads, the roofline and cpu_baseline objects and their arithmetic, and that the printed line is
-short enough for the driver to keep whole (BENCH_r05.json: `parsed: null` -- the line had grown to 22.9 KB)."""
-import glob, json, os, sys
+short enough for the driver to keep whole (BENCH_r05.json: `parsed: null` -- the line had grown to 22.9 KB).
+A plain run (no `--full`) measures the headline alone, and `--dump-outputs` writes what its last timed step returned."""
+import glob, json, os, subprocess, sys
 
 import pytest
 
@@ -115,3 +116,62 @@ def test_recorded_line_keeps_the_contract():
 def test_metric_is_baselines():
     d, base = latest()
     assert base["metric"].split()[0].lower() in d["metric"].lower() or "scans/sec" in d["metric"]
+
+
+def test_plain_run_measures_the_headline_alone():
+    """Without --full the default workload skips every companion figure, the profile replay, the CPU baseline and the legs;
+    --full brings them back, and its --no-* options still switch single ones off."""
+    import bench
+    extras = ("no_cpu_baseline", "no_profile", "no_fixed30", "no_host_input", "no_workloads")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, k) for k in extras)
+    full = bench.parse_args(["--full", "--steps", "7"])
+    assert not any(getattr(full, k) for k in extras)
+    assert bench.parse_args(["--full", "--no-workloads"]).no_workloads and not bench.parse_args(["--full", "--no-workloads"]).no_profile
+    # the named workloads are explicit requests: unchanged
+    assert not bench.parse_args(["--workload", "stream"]).no_profile
+    for bad in (["--steps", "0"], ["--workload", "f64", "--dump-outputs", "x"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_every_returned_array_in_float64(tmp_path):
+    import numpy as np
+    import bench
+    B = 3
+    T = np.stack([np.eye(4) * (b + 1) for b in range(B)])
+    st = [dict(status=0, iterations=5 + b, converged=True, max_iter_reached=False, overlap=0.5, residual=1e-3 * b, trim_limit=0.25,
+               n_kept=100 + b, n_finite=120, cov=np.full((6, 6), float(b))) for b in range(B)]
+    bench.dump_outputs(str(tmp_path / "out"), T, st)
+    names = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert names == sorted(["T.npy"] + [k + ".npy" for k in bench.STATS_FIELDS])
+    got = {n[:-4]: np.load(tmp_path / "out" / n) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["T"], T) and got["cov"].shape == (B, 6, 6) and got["cov"][2, 0, 0] == 2.0
+    assert got["iterations"].tolist() == [5.0, 6.0, 7.0] and got["converged"].tolist() == [1.0, 1.0, 1.0]
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_outputs_repeat(tmp_path):
+    """Two plain runs with the same (small) arguments: the contract's keys, `steps` timed steps, nothing but the headline measured,
+    and the same outputs bit for bit."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--n-scan", "5000", "--n-map", "50000", "--queries", "4", "--batch", "8"]
+    outs = []
+    for k in range(2):
+        d_out = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d_out)], cwd=ROOT,
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = strict_loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "scans/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["scans_total"] == 3 * 8 and d["value"] == pytest.approx(d["scans_converged"] / (3 * d["ms_per_step"] * 1e-3), rel=1e-3)
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["legs"]["f64"] is None
+        outs.append({f.name: np.load(f) for f in sorted(d_out.iterdir())})
+    assert outs[0]["T.npy"].shape == (8, 4, 4) and outs[0]["cov.npy"].shape == (8, 6, 6)
+    assert sorted(outs[0]) == sorted(outs[1])
+    for name, a in outs[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, outs[1][name], equal_nan=True), name

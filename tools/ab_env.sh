@@ -4,7 +4,7 @@ OUT=$1; VAR=$2; VALS=$3; shift 3
 mkdir -p $OUT
 python bench.py --prepare-only
 for v in $VALS; do
-  env $VAR=$v python bench.py --no-cpu-baseline --no-fixed30 --no-host-input "$@" 2>/dev/null | tail -1 > $OUT/bench_${VAR}_$v.json
+  env $VAR=$v python bench.py --full --no-cpu-baseline --no-fixed30 --no-host-input "$@" 2>/dev/null | tail -1 > $OUT/bench_${VAR}_$v.json
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_${VAR}_$v.json"))

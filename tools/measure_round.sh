@@ -11,7 +11,7 @@ python3 bench.py --workload slam --prepare-only > /dev/null 2>&1
 python3 bench.py --workload slam --slam-scans 600 --slam-points 100000 --slam-filters sensor --prepare-only > /dev/null 2>&1
 # run NAME ARGS...: the printed line -> $OUT/NAME.json (what the driver parses), the full record bench.py wrote -> $OUT/NAME_full.json
 run() { n=$1; shift; rm -f bench_full.json; python3 bench.py "$@" 2>/dev/null | tail -1 > $OUT/$n.json; cp bench_full.json $OUT/${n}_full.json 2>/dev/null; }
-run bench_n1 --steps 20 --warmup 5     # (the driver's command line)
+run bench_n1 --full --steps 20 --warmup 5     # (the headline's command line, with every companion figure and leg)
 run bench_loopclosure --workload loopclosure --pairs 512 --steps 2 --warmup 1
 run bench_stream_1 --workload stream --streams 1 --steps 2 --warmup 1
 run bench_stream_4 --workload stream --streams 4 --steps 2 --warmup 1
@@ -26,10 +26,10 @@ python3 tools/bench_normals.py 2>/dev/null | grep -v amdgpu > $OUT/bench_normals
 REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 # kernel trace of the headline command (without the companion figures, so that it holds only the metric's launches)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/trace -o t -- python3 $REPO/bench.py --no-fixed30 --no-cpu-baseline --no-host-input --no-workloads > $REPO/$OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/trace -o t -- python3 $REPO/bench.py --full --no-fixed30 --no-cpu-baseline --no-host-input --no-workloads > $REPO/$OUT/trace.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/trace_lc -o t -- python3 $REPO/bench.py --workload loopclosure --pairs 512 --steps 2 --warmup 1 --no-cpu-baseline --no-profile > $REPO/$OUT/trace_lc.log 2>&1
 # the copy / compute overlap of the host-input pipeline: kernels and memory copies on one time line
-timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $REPO/$OUT/trace_host -o t -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-fixed30 --no-cpu-baseline --no-profile --no-workloads > $REPO/$OUT/trace_host.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $REPO/$OUT/trace_host -o t -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no-fixed30 --no-cpu-baseline --no-profile --no-workloads > $REPO/$OUT/trace_host.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/trace_stream -o t -- python3 $REPO/bench.py --workload stream --steps 1 --warmup 1 --no-cpu-baseline --no-profile --no-host-input > $REPO/$OUT/trace_stream.log 2>&1
 # the facade at sensor size: two passes of the 600-scan drive (the program itself after `--`)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/trace_slam100k -o t -- $REPO/tools/slam_run /tmp/pgslam_amd_seq_600_100000_0.8.bin --filters sensor --passes 2 > $REPO/$OUT/trace_slam100k.log 2>&1

@@ -14,7 +14,7 @@ slam() { echo -n "facade 100k single thread, $1: "; env $1 ./tools/slam_run $SEQ
 import json,sys; d=json.loads(sys.stdin.read()); h=d['localizer_host_s']; print(d['scans_per_s'], d['keyframes'], d['loops_closed'], d['map_rebuilds'], 'icp', h['icp'], 'probe', h['after_icp_parts']['overlap_probe'])"; }
 {
 for rep in 1 2; do for s in X=0 $1; do
-  echo -n "headline, $s: "; rm -f bench_full.json; env $s python3 bench.py --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
+  echo -n "headline, $s: "; rm -f bench_full.json; env $s python3 bench.py --full --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
   echo -n "loop closing, $s: "; rm -f bench_full.json; env $s python3 bench.py --workload loopclosure --pairs 512 --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>/tmp/err.txt; val
   echo -n "stream 1, $s: "; rm -f bench_full.json; env $s python3 bench.py --workload stream --streams 1 --steps 2 --warmup 1 --no-cpu-baseline --no-host-input > /dev/null 2>/tmp/err.txt; val
   echo -n "stream fleet 16, $s: "; rm -f bench_full.json; env $s python3 bench.py --workload stream --streams 16 --fleet --steps 2 --warmup 1 --no-cpu-baseline --no-host-input > /dev/null 2>/tmp/err.txt; val

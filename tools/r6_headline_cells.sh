@@ -8,6 +8,6 @@ print(round(d['value'],1), d['unit'], round(d['ms_per_step'],2), 'ms/step; knn p
 {
 for rep in 1 2; do
 for s in "X=0" "PGICP_CELL_SCALE=0.85" "PGICP_CELL_SCALE=0.7" "PGICP_CELL_SCALE=0.7 PGICP_FAST_RINGS_UNSEEDED=5 PGICP_FAST_RINGS_SEEDED=2" "PGICP_CELL_SCALE=0.7 PGICP_FAST_RINGS_UNSEEDED=4 PGICP_FAST_RINGS_SEEDED=2 PGICP_MED_RINGS=8" "PGICP_CELL_SCALE=0.85 PGICP_FAST_RINGS_UNSEEDED=4 PGICP_FAST_RINGS_SEEDED=2" "PGICP_CELL_SCALE=0.85 PGICP_MED_RINGS=8" "PGICP_MED_RINGS=8" "PGICP_FAST_RINGS_SEEDED=2" "PGICP_CELL_SCALE=0.6 PGICP_FAST_RINGS_UNSEEDED=6 PGICP_FAST_RINGS_SEEDED=2 PGICP_MED_RINGS=8" "PGICP_CELL_SCALE=1.15"; do
-  echo -n "headline, $s: "; rm -f bench_full.json; env $s python3 bench.py --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
+  echo -n "headline, $s: "; rm -f bench_full.json; env $s python3 bench.py --full --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
 done; done
 } 2>&1 | tee $OUT/headline_cells.txt

@@ -14,7 +14,7 @@ import json; d=json.load(open('bench_full.json')); r=d.get('roofline') or {}
 print(round(d['value'],1), d['unit'], round(d['ms_per_step'],2), 'ms/step; knn pass us', r.get('avg_launch_us') and round(r['avg_launch_us'],1), 'unseeded', r.get('avg_unseeded_launch_us') and round(r['avg_unseeded_launch_us'],1), 'seeded', r.get('avg_seeded_launch_us') and round(r['avg_seeded_launch_us'],1), 'frac', r.get('frac') and round(r['frac'],4))"; }
 for t in 0 64,8 8 16 32,4 128,16,4 64,8 0; do
   echo -n "headline, PGICP_SAMPLE_STEPS=$t: "; rm -f bench_full.json
-  PGICP_SAMPLE_STEPS=$t python3 bench.py --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
+  PGICP_SAMPLE_STEPS=$t python3 bench.py --full --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
 done
 for t in 0 64,8 8 0 64,8; do
   echo -n "loop closing, PGICP_SAMPLE_STEPS=$t: "; rm -f bench_full.json

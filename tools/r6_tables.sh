@@ -14,7 +14,7 @@ for t in dense succinct dense succinct; do
 done
 for t in dense succinct; do
   echo -n "headline, PGICP_TABLES=$t: "; rm -f bench_full.json
-  PGICP_TABLES=$t python3 bench.py --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
+  PGICP_TABLES=$t python3 bench.py --full --no-cpu-baseline --no-fixed30 --no-host-input --no-workloads > /dev/null 2>/tmp/err.txt; val
 done
 for t in dense succinct dense succinct; do
   echo -n "stream (one vehicle, 2 M-pt sliding map), PGICP_TABLES=$t: "; rm -f bench_full.json
