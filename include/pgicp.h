@@ -384,6 +384,34 @@ int pgicp_surface_normals_f32(pgicp_ctx *ctx, const float *xyz, int stride, int 
 int pgicp_surface_normals_f64(pgicp_ctx *ctx, const double *xyz, int stride, int n, int mem, int knn, double max_dist,
                               double *out_nrm, int out_stride, double *out_eig, int32_t *out_ids, double *out_d2);
 
+/* (ABI 6, added) pgicp_sampling_surface_normal = [EXT] libpointmatcher SamplingSurfaceNormalDataPointsFilter{ratio, knn,
+ * samplingMethod, maxBoxDim, averageExistingDescriptors, keepNormals = 1} (DataPointsFilters/SamplingSurfaceNormal.cpp), the
+ * reference filter upstream's ICP::setDefault() installs and the one most point-to-plane YAML chains get their normals from:
+ * pgslam applies it in every setMap (Localizer.hpp:148, 168, 254 -> 314-315) and in every loop-closure ICP (LoopCloser.hpp:98).
+ * The statement is the oracle's, bit for bit (oracle/icp_oracle.c, orc_sampling_surface_normal): a range of more than knn points
+ * is cut at the median of the widest side of its carried bounds, a range of at most knn points is a box whose normal is the
+ * smallest eigenvector of its scatter; a box larger than maxBoxDim or of rank < 2 is dropped.  Upstream's: the recursion, the
+ * halves, the box rules.  Restated, with nothing upstream to be bit-exact against (the oracle's comment says why): the order of
+ * equal coordinates (a sort on (coordinate, index) for std::nth_element), the draw of samplingMethod 0 (SplitMix64 of seed and
+ * the ORIGINAL index for rand()), the eigen-solver (cyclic Jacobi in double for Eigen's).
+ *   xyz: n points at `stride`; desc (may be NULL): drows values a point, contiguous.  mem applies to every array: host in ->
+ *   host out, device in -> device out (a filtered map can go to pgicp_map_create with PGICP_DEVICE without crossing PCIe).
+ *   ratio and max_box_dim are rounded to T, as the host filter holds them; knn in [3, 1024].
+ *   Out, for the n_out kept points in ascending input index: out_xyz (the point, or with samplingMethod 1 its box's mean),
+ *   out_nrm (may be NULL) the box's normal, out_desc the descriptors -- with samplingMethod 1 and average_descriptors the box's
+ *   mean of each row (summed in box order in T), else the point's own --, kept_idx (may be NULL) the input index.  The output
+ *   arrays need room for n points.  n_boxes (may be NULL): boxes fused (not dropped).  n_out / n_boxes are host ints.
+ *   A NaN or infinite coordinate returns PGICP_ERR_ARG (no statement to match: the comparison is then no strict weak order,
+ *   a carried side inf - inf); so does an argument out of range -- a caller with a host fallback takes it then. */
+int pgicp_sampling_surface_normal_f32(pgicp_ctx *ctx, const float *xyz, int stride, int n, int mem, int knn, double ratio, int sampling_method,
+                                      double max_box_dim, uint64_t seed, const float *desc, int drows, int average_descriptors,
+                                      float *out_xyz, int out_stride, float *out_nrm, int nrm_stride, float *out_desc, int32_t *kept_idx,
+                                      int *n_out, int *n_boxes);
+int pgicp_sampling_surface_normal_f64(pgicp_ctx *ctx, const double *xyz, int stride, int n, int mem, int knn, double ratio, int sampling_method,
+                                      double max_box_dim, uint64_t seed, const double *desc, int drows, int average_descriptors,
+                                      double *out_xyz, int out_stride, double *out_nrm, int nrm_stride, double *out_desc, int32_t *kept_idx,
+                                      int *n_out, int *n_boxes);
+
 /* pgicp_filter_cloud = the localizer's input stage on the device: input_filters_.apply(cloud) (Localizer.hpp:103) for the
  * filters that only drop points, then rigid_transformation_->compute(cloud, T_robot_sensor) (Localizer.hpp:106), in one pass
  * over the uploaded scan.  `features`: frows x n column-major (a point = frows contiguous values, xyz first); `descriptors`

@@ -14,6 +14,7 @@
 // object without a usable GPU throws.
 #pragma once
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <istream>
 #include <limits>
@@ -143,6 +144,9 @@ template <> struct Abi<float> {
     static int map_create_batch(pgicp_ctx *c, int k, const float *const *x, const int *xs, const float *const *n, const int *ns, const int *m, int center, int *ids) { return pgicp_map_create_batch_f32(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
     static int normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig) { return pgicp_surface_normals_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
     static int normals_ids(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig, int32_t *ids) { return pgicp_surface_normals_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
+    static int sampling_normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const float *d, int dr, int avg,
+                                float *ox, float *on, float *od, int32_t *idx, int *n_out)
+    { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
     static int partial(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
     static int partial_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
     static int partial_seeded_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pgicp_partial_chain_seeded_f32(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
@@ -172,6 +176,9 @@ template <> struct Abi<double> {
     static int map_create_batch(pgicp_ctx *c, int k, const double *const *x, const int *xs, const double *const *n, const int *ns, const int *m, int center, int *ids) { return pgicp_map_create_batch_f64(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
     static int normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig) { return pgicp_surface_normals_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
     static int normals_ids(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig, int32_t *ids) { return pgicp_surface_normals_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
+    static int sampling_normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const double *d, int dr, int avg,
+                                double *ox, double *on, double *od, int32_t *idx, int *n_out)
+    { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
     static int partial(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
     static int partial_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
     static int partial_seeded_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pgicp_partial_chain_seeded_f64(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
@@ -660,16 +667,57 @@ struct PointMatcher {
     //! averaged (samplingMethod 1); boxes larger than maxBoxDim or of rank < 2 are dropped; the kept points stay in cloud order.
     //! The statement is the oracle's (oracle/icp_oracle.c orc_sampling_surface_normal, which says what is upstream's and what
     //! cannot be: nth_element's arrangement -> a sort on (coordinate, index); rand() -> the seeded draw; EigenSolver -> Jacobi).
-    //! Host side: it runs once per keyframe / map, on the reference (Localizer.hpp:314-315).
+    //! It runs once per keyframe / map, on the reference (Localizer.hpp:314-315), and per loop-closure candidate: on the device
+    //! (pgicp_sampling_surface_normal_*, the same bits) when there is one, unless PGSLAM_HOST_SAMPLING_NORMALS=1 or the device
+    //! refuses the cloud (a NaN or infinite coordinate, an out-of-range knn); then the host recursion below.  ranOnDevice():
+    //! which of the two the last inPlaceFilter took.
     struct SamplingSurfaceNormalDataPointsFilter : DataPointsFilter {
         T ratio; int knn, samplingMethod; T maxBoxDim; bool averageExistingDescriptors, keepNormals; unsigned long long seed;
+        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
+        bool onDevice = false;
         SamplingSurfaceNormalDataPointsFilter(T r = T(0.5), int k = 7, int method = 0, T box = std::numeric_limits<T>::infinity(), bool avg = true,
                                               bool kn = true, unsigned long long sd = 1)
             : ratio(r), knn(k), samplingMethod(method), maxBoxDim(box), averageExistingDescriptors(avg), keepNormals(kn), seed(sd) {}
+        SamplingSurfaceNormalDataPointsFilter(const SamplingSurfaceNormalDataPointsFilter &) = delete;
+        SamplingSurfaceNormalDataPointsFilter &operator=(const SamplingSurfaceNormalDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        //! the device form; false (the cloud untouched) when the device refuses the arguments
+        bool deviceFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            Matrix ox(3, n), on(3, n), od(drows > 0 ? drows : 1, n);
+            std::vector<int32_t> idx((size_t)n);
+            int kept = 0;
+            const int st = pgslam_amd::Abi<T>::sampling_normals(ctx, c.features.data(), frows, n, knn, (double)ratio, samplingMethod, (double)maxBoxDim,
+                                                                (uint64_t)seed, drows > 0 ? c.descriptors.data() : nullptr, drows,
+                                                                averageExistingDescriptors ? 1 : 0, ox.data(), on.data(), drows > 0 ? od.data() : nullptr,
+                                                                idx.data(), &kept);
+            if (st == PGICP_ERR_ARG) return false;
+            check(ctx, st);
+            // what the host recursion leaves: the kept columns in input order, rows 0-2 from the device (the box mean with
+            // samplingMethod 1, row 3 then 1), the other feature rows gathered, the descriptors compacted or averaged
+            Matrix f(frows, kept), d(drows, kept), nrm(3, kept);
+            for (int o = 0; o < kept; o++) {
+                const int i = idx[o];
+                for (int r = 0; r < 3; r++) f(r, o) = ox(r, o);
+                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
+                if (samplingMethod != 0 && frows > 3) f(3, o) = T(1);
+                for (int r = 0; r < drows; r++) d(r, o) = od(r, o);
+                for (int r = 0; r < 3; r++) nrm(r, o) = on(r, o);
+            }
+            c.features = f;
+            if (drows > 0) c.descriptors = d;
+            if (keepNormals) c.setDescriptor("normals", nrm);
+            return true;
+        }
         void inPlaceFilter(DataPoints &c) override
         {
+            onDevice = false;
             const int n = (int)c.features.cols();
             if (n == 0) return;
+            const char *knob = std::getenv("PGSLAM_HOST_SAMPLING_NORMALS");
+            static const bool have_device = pgicp_device_count() > 0;
+            if (have_device && !(knob && std::strcmp(knob, "1") == 0) && deviceFilter(c)) { onDevice = true; return; }
             const int drows = (int)c.descriptors.rows();
             std::vector<int> idx(n);
             for (int i = 0; i < n; i++) idx[i] = i;

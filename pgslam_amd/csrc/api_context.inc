@@ -116,6 +116,7 @@ struct pgicp_ctx {
     // reading, for the next three calls: a localizer that pre-processes scan k + 1 while scan k aligns, and now and then a
     // scan that was not pre-processed ahead, has three calls between making a reading and aligning it)
     struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop; } fset[4];
+    DevBuf ssn_work, ssn_io, ssn_cnt;   // pgicp_sampling_surface_normal_*: the build's scratch, host inputs' / outputs' device copies, counters
     DevBuf robust_dev;              // RobustOutlierFilter: the pairs' absolute deviations from the median (the second selection's input)
     int fset_next = 0;
     int up_next = 0;

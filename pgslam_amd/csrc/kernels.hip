@@ -13,6 +13,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <map>
 #include <type_traits>
 #ifndef PGICP_FAST_BLOCK
 #define PGICP_FAST_BLOCK 64
@@ -185,5 +187,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_minimise.inc"
 #include "k_filter.inc"
 #include "k_launch.inc"
+#include "k_ssn.inc"
 
 }  // namespace pgicp

@@ -96,4 +96,22 @@ void launch_unpermute(hipStream_t st, const MapDev<T> *maps, int map, const int 
 
 constexpr int kScanChunkHost = 4096;
 
+// pgicp_sampling_surface_normal_*: the device scratch of one call (sampling_normals_scratch gives the bytes of each array, in
+// this order); counters (4 ints, device): [0] boxes made, [1] boxes fused, [2] a coordinate is not finite, [3] points kept
+constexpr int kSsnArrays = 19;
+constexpr int kSsnMaxKnn = 1024;        // (one thread fuses a box: its loops are sequential, nothing is sized by knn)
+struct SsnScratch {
+    void *keys[2];
+    int *lst[2], *flag[2], *scan, *bsum, *seg_of[2], *side;
+    void *seg[2], *boxes;
+    int *keep, *box_of;
+    void *bnrm, *bmean;
+    int *pos;
+};
+size_t sampling_normals_scratch(int n, int elem, size_t *sizes);
+template <typename T>
+int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
+                            const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
+                            T *out_desc, int *kept_idx, int *counters);
+
 }  // namespace pgicp

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "pgicp_ctx_device", "pgicp_comm_unique_id", "pgicp_comm_create", "pgicp_comm_destroy", "pgicp_comm_info",
     "pgicp_comm_last_error", "pgicp_shard_slots", "pgicp_allgather_edges", "pgicp_comm_create_host", "pgicp_profile_process",
     "pgicp_debug_reading_order", "pgicp_partial_chain_seeded_f32", "pgicp_partial_chain_seeded_f64",
+    "pgicp_sampling_surface_normal_f32", "pgicp_sampling_surface_normal_f64",
 ]
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
 
@@ -688,6 +689,46 @@ class Context:
         if want_ids:
             out += [ids, d2]
         return out[0] if len(out) == 1 else tuple(out)
+
+    def sampling_surface_normal(self, xyz, knn=7, ratio=0.5, sampling_method=0, max_box_dim=float("inf"), seed=1, descriptors=None,
+                                average_descriptors=True, dtype=None):
+        """SamplingSurfaceNormalDataPointsFilter on the device (pgicp_sampling_surface_normal_*).  numpy in -> numpy out, torch
+        CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
+        normals (k,3), kept_idx (k,) int32, descriptors (k,drows) or None, boxes: boxes fused) for the k kept points, in
+        ascending input index."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+        x = _Buf(xyz, dtype)
+        n = x.n
+        d = None
+        drows = 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
+                assert d.ndim == 2 and d.shape[0] == n
+            drows = int(d.shape[1])
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
+            ox, on, oi = mk((max(n, 1), 3), xyz.dtype), mk((max(n, 1), 3), xyz.dtype), mk((max(n, 1),), torch.int32)
+            od = mk((max(n, 1), drows), xyz.dtype) if d is not None else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            ox, on = np.empty((max(n, 1), 3), dtype=x.dtype), np.empty((max(n, 1), 3), dtype=x.dtype)
+            oi = np.empty(max(n, 1), dtype=np.int32)
+            od = np.empty((max(n, 1), drows), dtype=x.dtype) if d is not None else None
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        n_out, boxes = C.c_int(0), C.c_int(0)
+        fn = getattr(self.lib, "pgicp_sampling_surface_normal" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
+                       C.c_int(sampling_method), C.c_double(max_box_dim), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
+                       C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(on), C.c_int(3), ptr(od), ptr(oi),
+                       C.byref(n_out), C.byref(boxes)))
+        k = n_out.value
+        return dict(xyz=ox[:k], normals=on[:k], kept_idx=oi[:k], descriptors=od[:k] if od is not None else None, boxes=boxes.value)
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
