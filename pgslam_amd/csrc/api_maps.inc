@@ -210,8 +210,9 @@ int map_create_batch(pgicp_ctx *c, int n, const MapSrc<T> *src, int mem, int cen
         for (int a = 0; a < 3; a++) {
             // the centroid is an order-independent fixed-point sum (2^-24 units in an int64): sum |v| 2^24 must stay
             // below 2^63 -- e.g. a million points at ECEF / UTM-scale coordinates would wrap silently.  Refused, not wrong.
+            // An uncentred map (mean 0, as pgicp_surface_normals builds its cloud) never reads the sum: no limit there.
             const double vmax = std::max(std::fabs((double)key_to_double(st[3 + a])), std::fabs((double)key_to_double(st[6 + a])));
-            if (vmax * (double)m >= 5.0e11)
+            if (center && vmax * (double)m >= 5.0e11)
                 return fail(c, PGICP_ERR_ARG, "pgicp_map_create: |coordinate| x points = " + std::to_string(vmax * (double)m) +
                                               " overflows the centroid's fixed-point sum (limit 5e11): express the cloud in a local frame first");
             const double mean_d = ((double)(long long)st[a] / 16777216.0) / (double)m;

@@ -391,6 +391,40 @@ def test_knn_k_against_scipy_and_brute(oracle32, oracle64):
             assert np.all(np.isinf(db[(want < 0) & clear[:, None]]))
 
 
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_knn_k_tree_equals_brute_at_every_list_size(oracle32, oracle64, dt):
+    """The GPU tests of the top-K lists (tests/test_gpu_topk.py) trust orc_kdtree_knn_k at k up to 32: the k-d tree against the
+    brute force bit for bit at k = 1, 8, 9, 16, 17, 32 (each list size's full case and the next one's first), on exact ties (a
+    lattice of spacing 1/8, queried at its points and half way between them), d2 == maxDist^2 exactly, and a cluster of 40
+    identical points; the brute force against numpy's lexicographic (d2, index) order on some rows."""
+    o = oracle32 if dt == np.float32 else oracle64
+    rng = np.random.default_rng(21)
+    lat = np.stack(np.meshgrid(np.arange(10), np.arange(10), np.arange(6), indexing="ij"), -1).reshape(-1, 3) / 8.0
+    lat = lat[rng.permutation(len(lat))].astype(dt)
+    clu = (rng.normal(size=(500, 3)) * 0.4).astype(dt)
+    dup = rng.choice(500, 40, replace=False)
+    clu[dup] = clu[dup[0]]
+    dup = np.sort(dup)
+    for m, q, mds in ((lat, np.concatenate([lat, lat[:200] + dt(1 / 16)]), (0.25, np.inf)),
+                      (clu, np.concatenate([clu, rng.normal(size=(100, 3)).astype(dt)]), (0.5, np.inf))):
+        for k in (1, 8, 9, 16, 17, 32):
+            for md in mds:
+                ib, db = o.knn_brute_k(q, m, k, md)
+                ik, dk = o.knn_k(m, q, k, md)
+                assert ib.tobytes() == ik.tobytes() and db.tobytes() == dk.tobytes(), (k, md)
+                md2 = dt(md) * dt(md)
+                for i in range(0, len(q), 41):
+                    d = (q[i] - m).astype(dt)
+                    dd = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+                    order = np.lexsort((np.arange(len(m)), dd))[:k]
+                    np.testing.assert_array_equal(ib[i], np.where(dd[order] <= md2, order, -1))
+                if m is lat and md == 0.25 and k == 32:      # 27 lattice points lie closer: the boundary is reached and kept
+                    assert np.any(db == md2)
+        if m is clu:                                         # the 40 copies: a copy's k neighbours are the k lowest indices
+            ib, db = o.knn_brute_k(clu[dup[:1]], clu, 32, 0.5)
+            assert np.array_equal(ib[0], dup[:32]) and np.all(db == 0)
+
+
 def test_point_to_point_against_numpy_svd(oracle32, oracle64):
     """PointToPointErrorMinimizer: the sums, and the increment against a weighted Kabsch through numpy.linalg.svd; a
     reflection is turned into the second-best rotation; the residual is the sum of the pairs' distances."""
