@@ -297,7 +297,7 @@ int pgicp_icp_pair_f64(pgicp_ctx *ctx, const double *reading, int rd_stride, int
  * maxDist), dist2 are SQUARED distances (+inf when id == -1); both hold knn entries
  * per reading point ([point][neighbour]: a knn x N column-major Matches matrix).
  * pgicp_outlier_weights = outlierFilters.compute (Localizer.hpp:330,
- * LoopCloser.hpp:360) for TrimmedDistOutlierFilter.
+ * LoopCloser.hpp:360) for TrimmedDistOutlierFilter (and VarTrimmedDistOutlierFilter, below).
  * pgicp_error_stats = ErrorElements(...) + weightedPointUsedRatio
  * (Localizer.hpp:332,347) and getResidualError (LoopCloser.hpp:362);
  * `reading` must already be in the map's frame (as pgslam passes it).
@@ -312,6 +312,41 @@ int pgicp_outlier_weights_f32(pgicp_ctx *ctx, const float *dist2, int n, int mem
                               float *limit, int *n_finite);
 int pgicp_outlier_weights_f64(pgicp_ctx *ctx, const double *dist2, int n, int mem, double *weights,
                               double *limit, int *n_finite);
+/* (ABI 6, added) [EXT] VarTrimmedDistOutlierFilter{minRatio, maxRatio, lambda}: a TrimmedDist filter whose ratio is chosen
+ * in every iteration (OutlierFiltersImpl.cpp, VarTrimmedDistOutlierFilter::compute / optimizeInlierRatio, restated from
+ * upstream's published source as recalled; nothing else pins it).  On the matcher's knn x N squared distances d (+inf: no
+ * neighbour within maxDist), of one problem:
+ *   1. P = knn * N, every entry counted (infinite ones and zeros too).
+ *   2. L = the entries with d != +inf and d > 0, sorted ascending; c its length (zeros are left out of L only).  c == 0:
+ *      ConvergenceError "no outlier to filter" -- PGICP_ERR_NO_MATCH for that problem.
+ *   3. minEl = (int)floor(T(minRatio) * P), maxEl = (int)floor(T(maxRatio) * P), both evaluated in T.
+ *   4. for every j in the window W = [minEl, min(maxEl, c)):  S_j = L[0] + ... + L[j], id = j + 1, f = id / P,
+ *      FRMS_j = (1 / f^lambda)^2 * S_j / id.
+ *   5. j* = the position of the smallest FRMS_j, the lowest j on a tie (Eigen's minCoeff(&index)).
+ *   6. tuned = (float)j* / (float)P -- in float for T = double too, as upstream casts it -- converted to T.
+ *   7. limit = getDistsQuantile(tuned) over all finite entries, zeros included (the TrimmedDist selection at `tuned`);
+ *      weight = d <= limit ? 1 : 0.
+ * Deviations from upstream:
+ *   DEVIATION (sums and objective in double): upstream sums S with a sequential std::partial_sum in T and evaluates FRMS in T.
+ *     Here S_j and FRMS_j are doubles, summed in this order: tiles of 1024 sorted values in sequence; inside a tile an
+ *     inclusive shuffle scan per 64-lane wave, plus the totals of the tile's earlier waves, plus the earlier tiles' sum.  So
+ *     j* is a function of the data, except where two FRMS values tie to about 1e-12 relative.
+ *   DEVIATION (window end): upstream maps P entries of a vector it only reserve()d, so positions >= c read uninitialised
+ *     memory.  Here the window ends at c.
+ *   DEVIATION (empty window): if W is empty, tuned = (float)minEl / (float)P (upstream: undefined).
+ * pgicp_set_var_trim(p = {minRatio, maxRatio, lambda}) puts the filter in the chain's quantile slot (NULL: takes it out);
+ * it needs 0 < minRatio < maxRatio <= 1 and a finite lambda >= 0 (else PGICP_ERR_ARG).  While it is on, every call that runs
+ * the chain's outlier filter applies it -- pgicp_align*, the residual pass of pgicp_align_residual_batch_*,
+ * pgicp_partial_chain* (seeded too: exact, the matcher resolves every pair) and pgicp_outlier_weights -- and refuses
+ * (PGICP_ERR_ARG) a chain with robust_fct != PGICP_ROBUST_NONE or quantile_scale != 1.  pgicp_params.trim_ratio is then
+ * ignored (it must still be valid); a MaxDist / SurfaceNormal outlier filter still multiplies its weights in.  The matcher
+ * resolves every query exactly in every iteration (as with the Robust filter), and pgicp_stats.trim_limit is step 7's limit.
+ * pgicp_last_var_trim_ratio: `tuned` of the last iteration of `problem` in the last align / partial-chain / outlier-weights
+ * call (upstream's "Optimized ratio" log line); -1 where the problem had no positive finite distance; PGICP_ERR_ARG when
+ * `problem` is out of that call's range or the call ran no VarTrimmed filter. */
+int pgicp_set_var_trim(pgicp_ctx *ctx, const double *p /* [3] minRatio, maxRatio, lambda; NULL = off */);
+int pgicp_get_var_trim(const pgicp_ctx *ctx, int *on, double *p /* [3] */);
+int pgicp_last_var_trim_ratio(pgicp_ctx *ctx, int problem, double *ratio);
 int pgicp_error_stats_f32(pgicp_ctx *ctx, int map_id, const float *reading, int stride, int n, int mem,
                           const int32_t *ids, const float *weights, double *weighted_point_used_ratio,
                           double *residual, double sys[30]);

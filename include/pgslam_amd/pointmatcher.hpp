@@ -1094,6 +1094,32 @@ struct PointMatcher {
             return w;
         }
     };
+    //! [EXT] VarTrimmedDistOutlierFilter{minRatio, maxRatio, lambda}: a TrimmedDist filter whose ratio is chosen at every call --
+    //! the trim that minimises the fractional RMSD of the sorted residuals over [minRatio, maxRatio] (OutlierFiltersImpl.cpp,
+    //! optimizeInlierRatio; the statement and its marked deviations: include/pgicp.h, pgicp_set_var_trim).  Every parameter must
+    //! be given (upstream's defaults are not pinned here); 0 < minRatio < maxRatio <= 1, lambda finite and >= 0.  It takes the
+    //! quantile slot (no TrimmedDist / MedianDist / Robust filter beside it).  Inside an ICP run the device applies it; this
+    //! stage-level call is pgicp_outlier_weights under the same setting.
+    struct VarTrimmedDistOutlierFilter : OutlierFilter {
+        ICPChainBase *chain; T minRatio, maxRatio, lambda;
+        VarTrimmedDistOutlierFilter(ICPChainBase *c, T mn, T mx, T l) : chain(c), minRatio(mn), maxRatio(mx), lambda(l)
+        {
+            if (!(minRatio > T(0) && minRatio < maxRatio && maxRatio <= T(1)))
+                throw std::runtime_error("VarTrimmedDistOutlierFilter: need 0 < minRatio < maxRatio <= 1");
+            if (!(lambda >= T(0)) || !std::isfinite((double)lambda))
+                throw std::runtime_error("VarTrimmedDistOutlierFilter: lambda must be finite and >= 0");
+        }
+        OutlierWeights compute(const DataPoints &, const DataPoints &, const Matches &input) override
+        {
+            OutlierWeights w(input.dists.rows(), input.dists.cols());
+            chain->pushParams();
+            T lim; int nf;
+            check(chain->ctx, A::weights(chain->ctx, input.dists.data(), (int)input.dists.size(), w.data(), &lim, &nf));
+            return w;
+        }
+        //! the ratio the last call chose (upstream logs it as "Optimized ratio")
+        double lastRatio() const { double r = 0.0; check(chain->ctx, pgicp_last_var_trim_ratio(chain->ctx, 0, &r)); return r; }
+    };
     //! [EXT] MedianDistOutlierFilter{factor}: limit = factor * getDistsQuantile(0.5) on the SQUARED match distances, weight 1
     //! while dist <= limit (OutlierFiltersImpl.cpp as restated in oracle/icp_oracle.c: orc_median_weights).  On the device
     //! it is the trimmed filter's exact order statistic at ratio 0.5, scaled (pgicp_params.quantile_scale).
@@ -1415,11 +1441,21 @@ struct PointMatcher {
                         if (dtype != "point2point") throw std::runtime_error("RobustOutlierFilter: distanceType " + dtype + " is not supported (point2point)");
                         if (nbIter != 0) throw std::runtime_error("RobustOutlierFilter: nbIterationForScale must be 0 (the scale is estimated at every iteration)");
                         outlierFilters.push_back(std::make_shared<RobustOutlierFilter>(this, fct, tun, scale, approx));
+                    } else if (m.name == "VarTrimmedDistOutlierFilter" && n_trim++ == 0) {
+                        // (every parameter explicit: upstream's defaults are not pinned here -- refuse rather than guess)
+                        for (auto &kv : m.params)
+                            if (kv.first != "minRatio" && kv.first != "maxRatio" && kv.first != "lambda")
+                                throw std::runtime_error("VarTrimmedDistOutlierFilter: unknown parameter " + kv.first);
+                        for (const char *k : {"minRatio", "maxRatio", "lambda"})
+                            if (!m.params.count(k)) throw std::runtime_error(std::string("VarTrimmedDistOutlierFilter: parameter ") + k + " must be given");
+                        outlierFilters.push_back(std::make_shared<VarTrimmedDistOutlierFilter>(this, (T)to_double(m.params.at("minRatio"), "minRatio"),
+                                                                                               (T)to_double(m.params.at("maxRatio"), "maxRatio"),
+                                                                                               (T)to_double(m.params.at("lambda"), "lambda")));
                     } else if (m.name == "MaxDistOutlierFilter" && n_max++ == 0)
                         outlierFilters.push_back(std::make_shared<MaxDistOutlierFilter>(m.params.count("maxDist") ? (T)to_double(m.params.at("maxDist"), "maxDist") : T(1)));
                     else
                         throw std::runtime_error("loadFromYaml: unsupported outlier filter chain at " + m.name +
-                                                 " (supported: one of TrimmedDistOutlierFilter, MedianDistOutlierFilter or RobustOutlierFilter, and / or one MaxDistOutlierFilter, "
+                                                 " (supported: one of TrimmedDistOutlierFilter, VarTrimmedDistOutlierFilter, MedianDistOutlierFilter or RobustOutlierFilter, and / or one MaxDistOutlierFilter, "
                                                  "and / or one SurfaceNormalOutlierFilter)");
                 }
             } else outlierFilters.push_back(std::make_shared<TrimmedDistOutlierFilter>(this, T(0.85)));
@@ -1477,7 +1513,9 @@ struct PointMatcher {
             if (matcher) { p.knn = matcher->knn; p.epsilon = (double)matcher->epsilon; p.max_dist = (double)matcher->maxDist; }
             p.trim_ratio = 1.0;                    // no TrimmedDist filter in the chain: every finite pair passes it
             p.outlier_max_dist = 0.0;
+            const VarTrimmedDistOutlierFilter *vt = nullptr;
             for (auto &f : outlierFilters) {
+                if (auto v = std::dynamic_pointer_cast<VarTrimmedDistOutlierFilter>(f)) vt = v.get();
                 if (auto t = std::dynamic_pointer_cast<TrimmedDistOutlierFilter>(f)) { p.trim_ratio = (double)t->ratio; p.quantile_scale = 1.0; }
                 if (auto md = std::dynamic_pointer_cast<MedianDistOutlierFilter>(f)) { p.trim_ratio = 0.5; p.quantile_scale = (double)md->factor; }
                 if (auto m = std::dynamic_pointer_cast<MaxDistOutlierFilter>(f)) p.outlier_max_dist = (double)m->maxDist;
@@ -1508,6 +1546,8 @@ struct PointMatcher {
             if (!hasCounter) p.max_iters = 1 << 20;
             if (!hasDiff) { p.min_diff_rot = 0; p.min_diff_trans = 0; }
             check(ctx, pgicp_set_params(ctx, &p));
+            if (vt) { const double q[3] = {(double)vt->minRatio, (double)vt->maxRatio, (double)vt->lambda}; check(ctx, pgicp_set_var_trim(ctx, q)); }
+            else check(ctx, pgicp_set_var_trim(ctx, nullptr));
         }
         //! LoopCloser.hpp:317
         bool getMaxNumIterationsReached() const { return lastStats.max_iter_reached != 0; }

@@ -118,6 +118,13 @@ struct pgicp_ctx {
     struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop; } fset[4];
     DevBuf ssn_work, ssn_io, ssn_cnt;   // pgicp_sampling_surface_normal_*: the build's scratch, host inputs' / outputs' device copies, counters
     DevBuf robust_dev;              // RobustOutlierFilter: the pairs' absolute deviations from the median (the second selection's input)
+    // (ABI 6, added) VarTrimmedDistOutlierFilter (pgicp_set_var_trim): on, {minRatio, maxRatio, lambda}; the sort's two key
+    // lists (one key per pair each); the tuned ratio of every problem's last iteration in the last align / partial-chain /
+    // outlier-weights call (empty: that call did not run the filter)
+    int vt_on = 0;
+    double vt[3] = {0.0, 0.0, 0.0};
+    DevBuf vt_keys, vt_prob;
+    std::vector<double> vt_last;
     int fset_next = 0;
     int up_next = 0;
     int up_seen = 0;            // upload sets whose device pointers the running call was handed (see UploadUse)
@@ -347,6 +354,7 @@ ChainDev<T> make_chain(const pgicp_params &p)
     ch.use_normals = p.normal_max_angle > 0.0 ? 1 : 0;
     ch.normal_cos = std::cos((T)p.normal_max_angle);          // in T, as the filter evaluates `cos(maxAngle)`
     ch.scan_pos = nullptr;                                     // (set by chain_of: it names a buffer of the context)
+    ch.var_trim = 0; ch.vt_min = ch.vt_max = ch.vt_lambda = 0.0;   // (set by chain_of: a setting of the context)
     return ch;
 }
 
@@ -357,7 +365,21 @@ ChainDev<T> chain_of(pgicp_ctx *c, const pgicp_params &p)
 {
     ChainDev<T> ch = make_chain<T>(p);
     ch.scan_pos = p.sum_order == PGICP_SUM_ORDER_SCAN ? c->scan_pos.as<int>() : nullptr;
+    ch.var_trim = c->vt_on;
+    ch.vt_min = c->vt[0]; ch.vt_max = c->vt[1]; ch.vt_lambda = c->vt[2];
     return ch;
+}
+
+// VarTrimmedDistOutlierFilter takes the chain's quantile slot: no RobustOutlierFilter, no MedianDist factor beside it
+// (checked at every call that runs the chain: the two settings are made separately)
+int var_trim_check(pgicp_ctx *c)
+{
+    if (!c->vt_on) return PGICP_OK;
+    if (c->prm.robust_fct != PGICP_ROBUST_NONE)
+        return fail(c, PGICP_ERR_ARG, "VarTrimmedDistOutlierFilter: no RobustOutlierFilter beside it (one quantile / robust filter per chain)");
+    if (c->prm.quantile_scale != 1.0)
+        return fail(c, PGICP_ERR_ARG, "VarTrimmedDistOutlierFilter: quantile_scale must be 1 (no MedianDistOutlierFilter beside it)");
+    return PGICP_OK;
 }
 
 double key_to_double(unsigned long long k)

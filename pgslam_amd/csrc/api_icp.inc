@@ -38,6 +38,8 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
                 const BorrowSpec *borrow = nullptr)
 {
     if (P > 65535) return fail(c, PGICP_ERR_ARG, "pgicp: at most 65535 problems per batch (the problem index is a launch-grid dimension)");
+    c->vt_last.clear();
+    { const int vst = var_trim_check(c); if (vst) return vst; }
     State<T> &S = state<T>(c);
     L.P = P; L.max_n = 0; L.max_rows = 1; L.total = 0; L.table_kinds = 0;
     c->last_n0 = -1;                            // (this call overwrites the correspondences another context might seed from)
@@ -92,6 +94,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
         // (the sort's words; afterwards the selection's key list: one key per PAIR)
         HIPC(c, c->qtmp.ensure(std::max(sizeof(unsigned long long) * (size_t)L.total, sizeof(T) * (size_t)L.total * L.knn)));
         if (c->prm.robust_fct != PGICP_ROBUST_NONE) HIPC(c, c->robust_dev.ensure(sizeof(T) * (size_t)L.total * L.knn));
+        if (c->vt_on) HIPC(c, c->vt_keys.ensure(2 * sizeof(T) * (size_t)L.total * L.knn));      // (two key lists: the sort's ping-pong)
         HIPC(c, c->order.ensure(sizeof(int) * (size_t)L.total));
         if (c->prm.sum_order == PGICP_SUM_ORDER_SCAN) HIPC(c, c->scan_pos.ensure(sizeof(int) * (size_t)L.total));
         HIPC(c, c->slow_list.ensure(sizeof(int2) * (size_t)L.total));
@@ -218,6 +221,16 @@ static int probe_rings(const BatchLayout &L)
     return v > 0 ? v : L.rings_unseeded;
 }
 
+// VarTrimmedDistOutlierFilter: every active problem's ratio of this iteration into ProblemDev::vt_ratio (k_vartrim.inc)
+template <typename T>
+void var_trim_enqueue(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, int nA)
+{
+    State<T> &S = state<T>(c);
+    char *keys = (char *)c->vt_keys.p;
+    launch_var_trim<T>(c->stream, c->probs.as<ProblemDev>(), S.d2.template as<T>(), c->active.as<int>(), nA, keys,
+                       keys + sizeof(T) * (size_t)L.total * L.knn, ch.vt_min, ch.vt_max, ch.vt_lambda);
+}
+
 // `stage`: 0 the whole iteration; 1 only its matcher pass (fast kernel + queue compaction); 2 everything but that pass -- the
 // driver of a single problem enqueues the NEXT iteration's matcher pass before it knows whether there is a next iteration
 // (align_batch: every kernel leaves at once for a problem that is done), so that the device does not wait for the host's
@@ -242,7 +255,12 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
         }
         {
             ProfScope ps(c, PGICP_PROF_TRIM, act_units, act_probs);
-            launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_pairs(), 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, use_seed);
+            if (ch.var_trim) {
+                var_trim_enqueue<T>(c, L, ch, nA);
+                launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_pairs(), 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
+            } else {
+                launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_pairs(), 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, use_seed);
+            }
         }
         {
             ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);
@@ -271,16 +289,19 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
     if (stage == 1) return;
     {
         ProfScope ps(c, PGICP_PROF_TRIM, act_units, act_probs);
-        // (with the grid matcher this selection also clears the matcher's segmented queue counters for the next iteration)
+        // (with the grid matcher this selection also clears the matcher's segmented queue counters for the next iteration; under
+        //  VarTrimmed that -- and far_mode -- is all it is for: k_robust_open and the second == 2 selection overwrite its threshold.
+        //  A cheaper counter clear would spare one selection an iteration there; the TrimmedDist path is left as it is)
         const bool grid = c->prm.matcher == PGICP_MATCHER_GRID;
         launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 0, active, c->sel_tables.as<int>(), c->qtmp.p,
-                              grid ? (int *)c->queue.p : nullptr, ch.robust.fct != 0 ? 0 : (use_seed == 1 || c->sel_guess_first));      // (every selection but a run's first starts from the last one's result,
+                              grid ? (int *)c->queue.p : nullptr, (ch.robust.fct != 0 || ch.var_trim) ? 0 : (use_seed == 1 || c->sel_guess_first));      // (every selection but a run's first starts from the last one's result,
                                                                                           // ProblemDev::qraw; a run's first from the previous call's, ::qhint, if there is one)
         c->seg_clean = grid ? 1 : 0;
     }
     const bool robust = ch.robust.fct != 0;
-    // RobustOutlierFilter: nothing is trimmed -- the threshold the lazy path resolves queued queries up to is +inf from here on
-    if (robust) launch_robust_open(c->stream, probs, active, nA);
+    // RobustOutlierFilter: nothing is trimmed -- the threshold the lazy path resolves queued queries up to is +inf from here on;
+    // VarTrimmedDistOutlierFilter: its ratio is chosen over every distance -- the same
+    if (robust || ch.var_trim) launch_robust_open(c->stream, probs, active, nA);
     if (c->prm.matcher == PGICP_MATCHER_GRID) {
         // lazy resolution: only queued queries whose lower bound is within the threshold just
         // selected (an upper bound of the final one) are searched exactly; then the threshold
@@ -303,7 +324,13 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
             }
         }
         ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        if (!robust) launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 1, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 1);
+        if (!robust && !ch.var_trim) launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 1, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 1);
+    }
+    if (ch.var_trim) {
+        // every distance is exact now: the ratio of this iteration, then the selection at that ratio
+        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
+        var_trim_enqueue<T>(c, L, ch, nA);
+        launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
     }
     if (robust) {
         // the scale of this iteration from the (now exact) distances: median, absolute deviations, their median
@@ -355,7 +382,8 @@ void one_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, bo
         mix(&ch, sizeof ch);
         const void *bufs[] = {c->probs.p, S.d_maps.p, S.rd_sorted.p, S.slot.p, S.d2.p, S.none_r.p, c->small.p, c->slow_list.p, c->slow_lb.p,
                               c->slow_ring.p, c->slow2.p, c->active.p, c->queue.p, c->sel_tables.p, c->qtmp.p, c->partials.p, c->h_flag, c->stamp_dev,
-                              c->robust_dev.p, L.normals ? S.nrm_sorted.p : nullptr};
+                              c->robust_dev.p, L.normals ? S.nrm_sorted.p : nullptr, c->vt_on ? c->vt_keys.p : nullptr,
+                              (const void *)(size_t)(c->vt_on ? L.total : 0)};     // (VarTrimmed: the second key list starts L.total pairs in)
         mix(bufs, sizeof bufs);
         pgicp_ctx::IterGraph *g = nullptr;
         for (auto &e : c->iter_graphs) if (e.exec && e.key == key) { g = &e; break; }
@@ -407,6 +435,13 @@ static void hints_store(pgicp_ctx *c, int kind, const std::vector<ProblemDev> &h
     std::vector<pgicp_ctx::SelHint> &H = c->sel_hints[kind];
     H.resize(hp.size());
     for (size_t p = 0; p < hp.size(); p++) std::memcpy(H[p].q, hp[p].qrec, sizeof H[p].q);
+}
+
+// pgicp_last_var_trim_ratio: the tuned ratio of every problem's last iteration (the chain has no VarTrimmed filter: none)
+static void var_trim_record(pgicp_ctx *c, const std::vector<ProblemDev> &hp)
+{
+    c->vt_last.clear();
+    if (c->vt_on) for (const ProblemDev &D : hp) c->vt_last.push_back(D.vt_ratio);
 }
 
 // number of finished problems after the iteration just enqueued (its k_compact_active carries c->flag_stamp)
@@ -552,6 +587,7 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
     HIPC(c, hipGetLastError());
     std::memcpy(hp.data(), c->h_down, sizeof(ProblemDev) * (size_t)P);
     hints_store(c, 0, hp);
+    var_trim_record(c, hp);
     for (int p = 0; p < P && !rsys.empty(); p++) {
         const double *rs = rsys.data() + (size_t)p * kSys;
         const bool ok = hp[p].status == PGICP_ST_OK && rs[28] > 0.0;

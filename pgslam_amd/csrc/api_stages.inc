@@ -139,6 +139,7 @@ int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ra
     HIPC(c, hipGetLastError());
     std::memcpy(hp.data(), c->h_down, sizeof(ProblemDev) * (size_t)P);
     hints_store(c, 1, hp);
+    var_trim_record(c, hp);
     int worst = PGICP_OK;
     for (int p = 0; p < P; p++) {
         const double *s = sys.data() + (size_t)p * kSys;
@@ -184,6 +185,8 @@ template <typename T>
 int outlier_weights(pgicp_ctx *c, const T *dist2, int n, int mem, T *weights, T *limit, int *n_finite)
 {
     if (!c || !dist2 || n <= 0) return fail(c, PGICP_ERR_ARG, "pgicp_outlier_weights: bad argument");
+    c->vt_last.clear();
+    { const int vst = var_trim_check(c); if (vst) return vst; }
     HIPC(c, hipSetDevice(c->device));
     const T *d_d2 = dist2;
     T *d_w = weights;
@@ -199,10 +202,46 @@ int outlier_weights(pgicp_ctx *c, const T *dist2, int n, int mem, T *weights, T 
     // by the same block selection); `limit` comes back +inf -- the filter has none
     const bool robust = c->prm.robust_fct != PGICP_ROBUST_NONE;
     if (robust) HIPC(c, c->robust_dev.ensure(sizeof(T) * (size_t)n));
+    // VarTrimmedDistOutlierFilter: the ratio first (k_var_trim over one problem record that spans the array), read back --
+    // then the same selection and weights as TrimmedDist's at that ratio
+    double ratio = c->prm.trim_ratio;
+    if (c->vt_on) {
+        const size_t rec = (sizeof(ProblemDev) + 63) & ~(size_t)63;
+        HIPC(c, c->vt_prob.ensure(rec + 64));
+        HIPC(c, c->vt_keys.ensure(2 * sizeof(T) * (size_t)n));
+        ProblemDev D;
+        std::memset(&D, 0, sizeof D);
+        D.n = n; D.knn = 1; D.off = 0;
+        const int zero = 0;
+        XFER(c, h2d(c, c->vt_prob.p, &D, sizeof D));
+        XFER(c, h2d(c, (char *)c->vt_prob.p + rec, &zero, sizeof zero));
+        {
+            ProfScope ps(c, PGICP_PROF_TRIM, n);
+            launch_var_trim<T>(c->stream, c->vt_prob.as<ProblemDev>(), d_d2, (const int *)((char *)c->vt_prob.p + rec), 1, c->vt_keys.p,
+                               (char *)c->vt_keys.p + sizeof(T) * (size_t)n, c->vt[0], c->vt[1], c->vt[2]);
+        }
+        XFER(c, d2h(c, &D, c->vt_prob.p, sizeof D));
+        HIPC(c, stream_sync(c));
+        HIPC(c, hipGetLastError());
+        c->vt_last.assign(1, D.vt_ratio);
+        if (D.vt_ratio < 0.0) {
+            // (no positive finite distance: upstream's ConvergenceError; the finite count is still reported)
+            if (limit) *limit = std::numeric_limits<T>::infinity();
+            if (n_finite) {
+                T h[2];
+                launch_trim_raw<T>(c->stream, d_d2, n, (T)1, (T)1, c->small.as<T>(), nullptr);
+                XFER(c, d2h(c, h, c->small.p, sizeof h));
+                HIPC(c, stream_sync(c));
+                *n_finite = (int)h[1];
+            }
+            return fail(c, PGICP_ERR_NO_MATCH, "VarTrimmedDistOutlierFilter: no outlier to filter (ConvergenceError)");
+        }
+        ratio = D.vt_ratio;
+    }
     {
         ProfScope ps(c, PGICP_PROF_TRIM, n);
         if (robust) launch_robust_raw<T>(c->stream, d_d2, n, make_chain<T>(c->prm).robust, c->robust_dev.as<T>(), c->small.as<T>(), d_w);
-        else launch_trim_raw<T>(c->stream, d_d2, n, (T)c->prm.trim_ratio, (T)c->prm.quantile_scale, c->small.as<T>(), d_w);
+        else launch_trim_raw<T>(c->stream, d_d2, n, (T)ratio, (T)c->prm.quantile_scale, c->small.as<T>(), d_w);
     }
     T h[2];
     XFER(c, d2h(c, h, c->small.p, sizeof h));

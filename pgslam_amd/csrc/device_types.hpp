@@ -107,6 +107,10 @@ struct ChainDev {
     T normal_cos;        // SurfaceNormalOutlierFilter: cos(maxAngle) evaluated in T on the host
     int use_normals;     // ... and whether it is in the chain
     RobustDev<T> robust; // RobustOutlierFilter (the chain's distance filter then: no quantile filter beside it)
+    // (ABI 6, added) VarTrimmedDistOutlierFilter{minRatio, maxRatio, lambda}: the quantile is chosen per problem and iteration
+    // (k_var_trim -> ProblemDev::vt_ratio); var_trim 0: not in the chain
+    int var_trim;
+    double vt_min, vt_max, vt_lambda;
     // (ABI 6, per call rather than per chain) PGICP_SUM_ORDER_SCAN: sorted position of every reading point of the batch -- the
     // inverse of the reading sort, indexed like the per-point arrays -- so that the reduce kernels can walk the pairs in the
     // caller's order; null: they walk the sorted order
@@ -151,6 +155,9 @@ struct ProblemDev {
     double qhint[2][4];
     double qrec[2][4];
     double robust_s2;        // RobustOutlierFilter: this iteration's squared scale (k_robust_finish)
+    double vt_ratio;         // VarTrimmedDistOutlierFilter: this iteration's tuned ratio (k_var_trim), -1: no positive finite distance
+    int vt_count;            // ... and the number of positive finite distances it was chosen over
+    int vt_pad_;
     double sys[kSys];        // final sums of the last iteration
     Checker chk;
 };

@@ -132,7 +132,15 @@ __device__ __forceinline__ void sel_pick_bin(const int *__restrict__ gh, T ratio
 
 __device__ __forceinline__ bool sel_skip(const ProblemDev &P, int second)
 {
-    return P.done || (second && P.n_refined == 0);      // the re-selection only runs if the lazy path refined something
+    return P.done || (second == 1 && P.n_refined == 0);      // the re-selection only runs if the lazy path refined something
+}
+
+// the quantile a selection takes: the chain's TrimmedDist ratio, or (second == 2: the selection after k_var_trim) the problem's
+// VarTrimmedDist ratio of this iteration -- a float, exact in T
+template <typename T>
+__device__ __forceinline__ T sel_ratio(const ProblemDev &P, const ChainDev<T> &ch, int second)
+{
+    return second == 2 ? (T)P.vt_ratio : ch.trim_ratio;
 }
 
 // what every final stage of a selection leaves in the problem record (thread 0 of the problem's block)
@@ -146,6 +154,12 @@ __device__ __forceinline__ void sel_store(ProblemDev &P, const ChainDev<T> &ch, 
     // the quantile itself (a MedianDist factor below 1 keeps less than the median it is computed from)
     P.limit = (double)fmin(limit * ch.trim_scale, ch.outlier_max_d2);        // (x 1 is exact: TrimmedDist unchanged)
     P.rlimit = fmax((double)limit, P.limit);
+    if (second == 2) {
+        // VarTrimmedDist: no positive finite distance (no outlier to filter) keeps nothing -- the solve reports NO_MATCH; the
+        // next matcher pass must again find every pair exactly (the ratio is chosen over all of them): no search cap
+        if (P.vt_ratio < 0.0) P.limit = -1.0;
+        P.rlimit = __longlong_as_double(0x7FF0000000000000LL);
+    }
     P.qraw = (double)limit;
     if (!second) P.qraw1 = (double)limit;
     if (P.iters < 4) P.qrec[second ? 1 : 0][P.iters] = (double)limit;
@@ -238,7 +252,7 @@ __global__ __launch_bounds__(256) void k_sel_filter(const ProblemDev *__restrict
         keys[u] = i < last ? Bits<T>::key(d2[poff + i]) : ~(U)0;
     }
     int bin, krem, total;
-    sel_pick_bin<T, 256>(gh, ch.trim_ratio, lds_scan, s_pick, bin, krem, total);     // barriers inside
+    sel_pick_bin<T, 256>(gh, sel_ratio<T>(P, ch, second), lds_scan, s_pick, bin, krem, total);     // barriers inside
     if (total == 0) return;
     for (int base = first; base < last; base += kSelTile) {
         if (base != first) {
@@ -285,7 +299,7 @@ __global__ __launch_bounds__(kSelectBlock) void k_sel_final(ProblemDev *__restri
     __shared__ int s_k;
     int *gh = tables + (long long)prob * kSelStride;
     int bin, krem, total;
-    sel_pick_bin<T, kSelectBlock>(gh, ch.trim_ratio, lds_scan, s_pick, bin, krem, total);
+    sel_pick_bin<T, kSelectBlock>(gh, sel_ratio<T>(P, ch, second), lds_scan, s_pick, bin, krem, total);
     const int cnt = gh[kSelBins];
     __syncthreads();
     // leave the table clean for the next selection of this problem
@@ -447,7 +461,7 @@ __global__ __launch_bounds__(kSelectBlock) void k_sel_final2(ProblemDev *__restr
     int n_finite = total;
     bool selected = false;
     if (total > 0) {
-        const long long kk = select_rank<T>(total, ch.trim_ratio);
+        const long long kk = select_rank<T>(total, sel_ratio<T>(P, ch, second));
         if (kk >= below && kk < (long long)below + cnt) {
             // the slice of the band that holds the rank (counted by k_sel_band), its keys into LDS in one pass over the
             // band's list, the select inside LDS over the bits a slice's keys differ in
@@ -556,7 +570,7 @@ __global__ __launch_bounds__(kSelectBlock) void k_sel_final2(ProblemDev *__restr
         } else {
             // the wanted rank lies outside the band: this block selects over all of the problem's distances (three passes)
             if (threadIdx.x == 0) atomicAdd(&g_sel_fallbacks, 1);
-            trim_select_block<T>(d2 + pairs_off(P), pairs_n(P), ch.trim_ratio, limit, n_finite);
+            trim_select_block<T>(d2 + pairs_off(P), pairs_n(P), sel_ratio<T>(P, ch, second), limit, n_finite);
         }
     }
     if (threadIdx.x == 0) sel_store<T>(P, ch, second, limit, n_finite);
@@ -574,7 +588,7 @@ __global__ __launch_bounds__(kSelectBlock) void k_sel_small(ProblemDev *__restri
     if (sel_skip(P, second)) return;
     T limit;
     int nf;
-    trim_select_block<T>(d2 + pairs_off(P), pairs_n(P), ch.trim_ratio, limit, nf);
+    trim_select_block<T>(d2 + pairs_off(P), pairs_n(P), sel_ratio<T>(P, ch, second), limit, nf);
     sel_queue_counters(P, prob, second, seg_count);
     if (threadIdx.x == 0) sel_store<T>(P, ch, second, limit, nf);
 }

@@ -188,5 +188,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_filter.inc"
 #include "k_launch.inc"
 #include "k_ssn.inc"
+#include "k_vartrim.inc"
 
 }  // namespace pgicp

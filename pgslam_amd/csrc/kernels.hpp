@@ -80,6 +80,9 @@ template <typename T>
 void launch_robust_scale(hipStream_t st, ProblemDev *probs, const T *d2, T *dev, const ChainDev<T> &ch, int n_active, int max_pairs,
                          const int *active, int *tables, void *keys);
 template <typename T>
+void launch_var_trim(hipStream_t st, ProblemDev *probs, const T *d2, const int *active, int n_active, void *keys_a, void *keys_b,
+                     double min_ratio, double max_ratio, double lambda);
+template <typename T>
 void launch_trim_raw(hipStream_t st, const T *d2, int n, T ratio, T scale, T *limit_nf, T *w);
 template <typename T>
 void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, const T *desc, int drows, int n, int n_filters,

@@ -417,6 +417,34 @@ int pgicp_outlier_weights_f32(pgicp_ctx *c, const float *d2, int n, int mem, flo
 int pgicp_outlier_weights_f64(pgicp_ctx *c, const double *d2, int n, int mem, double *w, double *limit, int *nf)
 { return outlier_weights<double>(c, d2, n, mem, w, limit, nf); }
 
+int pgicp_set_var_trim(pgicp_ctx *c, const double *p)
+{
+    if (!c) return PGICP_ERR_ARG;
+    if (!p) { c->vt_on = 0; c->vt[0] = c->vt[1] = c->vt[2] = 0.0; return PGICP_OK; }
+    if (!(p[0] > 0.0 && p[0] < p[1] && p[1] <= 1.0))
+        return fail(c, PGICP_ERR_ARG, "VarTrimmedDistOutlierFilter: need 0 < minRatio < maxRatio <= 1");
+    if (!(p[2] >= 0.0) || !std::isfinite(p[2])) return fail(c, PGICP_ERR_ARG, "VarTrimmedDistOutlierFilter: lambda must be finite and >= 0");
+    c->vt_on = 1;
+    for (int k = 0; k < 3; k++) c->vt[k] = p[k];
+    return PGICP_OK;
+}
+int pgicp_get_var_trim(const pgicp_ctx *c, int *on, double *p)
+{
+    if (!c) return PGICP_ERR_ARG;
+    if (on) *on = c->vt_on;
+    if (p) for (int k = 0; k < 3; k++) p[k] = c->vt[k];
+    return PGICP_OK;
+}
+int pgicp_last_var_trim_ratio(pgicp_ctx *c, int problem, double *ratio)
+{
+    if (!c || !ratio) return PGICP_ERR_ARG;
+    if (problem < 0 || problem >= (int)c->vt_last.size())
+        return fail(c, PGICP_ERR_ARG, "pgicp_last_var_trim_ratio: the last align / partial-chain / outlier-weights call ran no VarTrimmedDistOutlierFilter "
+                                      "on problem " + std::to_string(problem) + " (" + std::to_string(c->vt_last.size()) + " problems)");
+    *ratio = c->vt_last[(size_t)problem];
+    return PGICP_OK;
+}
+
 int pgicp_error_stats_f32(pgicp_ctx *c, int map_id, const float *rd, int stride, int n, int mem, const int32_t *ids,
                           const float *w, double *ratio, double *residual, double sys[30])
 { return error_stats<float>(c, map_id, rd, stride, n, mem, ids, w, ratio, residual, sys); }

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "pgicp_comm_last_error", "pgicp_shard_slots", "pgicp_allgather_edges", "pgicp_comm_create_host", "pgicp_profile_process",
     "pgicp_debug_reading_order", "pgicp_partial_chain_seeded_f32", "pgicp_partial_chain_seeded_f64",
     "pgicp_sampling_surface_normal_f32", "pgicp_sampling_surface_normal_f64",
+    "pgicp_set_var_trim", "pgicp_get_var_trim", "pgicp_last_var_trim_ratio",
 ]
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
 
@@ -405,6 +406,29 @@ class Context:
         except PgicpError:
             self.params = before            # a refused setting leaves the context (and this mirror of it) as it was
             raise
+
+    def set_var_trim(self, min_ratio=None, max_ratio=None, lam=None):
+        """[EXT] VarTrimmedDistOutlierFilter{minRatio, maxRatio, lambda} in the chain's quantile slot (pgicp_set_var_trim); called
+        with no arguments it takes the filter out.  align*, partial_chain* and outlier_weights then apply it."""
+        if min_ratio is None and max_ratio is None and lam is None:
+            self._check(self.lib.pgicp_set_var_trim(self.h, None))
+            return
+        p = (C.c_double * 3)(float(min_ratio), float(max_ratio), float(lam))
+        self._check(self.lib.pgicp_set_var_trim(self.h, p))
+
+    def get_var_trim(self):
+        """(minRatio, maxRatio, lambda), or None when the filter is off."""
+        on = C.c_int(0)
+        p = (C.c_double * 3)()
+        self._check(self.lib.pgicp_get_var_trim(self.h, C.byref(on), p))
+        return tuple(p[:]) if on.value else None
+
+    def last_var_trim_ratio(self, problem=0):
+        """The tuned ratio of the last iteration of `problem` in the last align / partial-chain / outlier-weights call
+        (-1: the problem had no positive finite distance)."""
+        r = C.c_double(0)
+        self._check(self.lib.pgicp_last_var_trim_ratio(self.h, C.c_int(problem), C.byref(r)))
+        return r.value
 
     @property
     def stream(self):
