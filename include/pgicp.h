@@ -447,6 +447,41 @@ int pgicp_sampling_surface_normal_f64(pgicp_ctx *ctx, const double *xyz, int str
                                       double *out_xyz, int out_stride, double *out_nrm, int nrm_stride, double *out_desc, int32_t *kept_idx,
                                       int *n_out, int *n_boxes);
 
+/* (ABI 6, added) pgicp_voxel_grid = [EXT] libpointmatcher VoxelGridDataPointsFilter{vSizeX, vSizeY, vSizeZ, useCentroid,
+ * averageExistingDescriptors} (DataPointsFilters/VoxelGrid.cpp; defaults 1, 1, 1, 1, 1), restated from upstream's code as
+ * recalled, 3-D clouds only.  The down-sampler of most YAML chains: per scan (Localizer.hpp:103) and on the concatenated map
+ * in referenceDataPointsFilters (Localizer.hpp:314-315, LoopCloser.hpp:98).  Arithmetic in T (float for _f32, double for
+ * _f64), no contraction, correctly rounded division; v = v_size rounded to T.
+ *   1. lo_a / hi_a = min / max of coordinate a over the cloud; minB_a = lo_a / v_a, maxB_a = hi_a / v_a, NOT floored (the grid
+ *      is anchored at the cloud's minimum).
+ *   2. numDiv_a = (unsigned)((1 + maxB_a) - minB_a).
+ *   3. per point: i_a = (unsigned)floor(x_a / v_a - minB_a); idx = i + j numDivX + k numDivX numDivY.
+ *   4. a voxel's first point is its smallest input index; its count the number of its points.
+ *   5. use_centroid: rows 0-2 of the first point become ((x_first + x_2nd) + x_3rd) + ... in ascending input index, divided by
+ *      T(count); row 3 and any further feature rows stay the first point's.
+ *   6. else: coordinate a is the voxel's centre (minB_a + T(i_a)) v_a + v_a / 2, i_a recovered from idx by / and -.
+ *   7. average_descriptors: every descriptor row summed as in 5 and divided by T(count) (normals not renormalised); else the
+ *      first point's descriptors.
+ *   8. one point per non-empty voxel, in ascending first-point index (upstream's std::sort of pointsToKeep).
+ * Deviations:
+ *   (a) idx is computed in 64 bits and no dense array of numVox voxels exists (upstream: 32-bit idx and numVox, all voxels
+ *       allocated, InvalidParameter on bad_alloc, wrapped indices past 2^32); where numVox < 2^32 the results are the same.
+ *       A grid with a numDiv_a >= 2^31 or numDivX numDivY numDivZ >= 2^62 is refused.
+ *   (b) a NaN or infinite coordinate is refused (upstream's floor to unsigned is undefined for it).
+ *   (c) an empty cloud gives an empty cloud (upstream's minCoeff of nothing is undefined).
+ *   (the sign of a zero bound does not matter: -0.0 and +0.0 give the same i_a, numDiv_a and centre)
+ *   xyz: n points at `stride`; desc (may be NULL): drows values a point, contiguous.  mem applies to every array: host in ->
+ *   host out (through the context's pinned buffers), device in -> device out.  Out, for the n_out voxels in ascending
+ *   first-point index: out_xyz at out_stride, out_desc (drows a voxel), kept_idx (may be NULL) the first point's input index,
+ *   out_count (may be NULL) the voxel's points.  The output arrays need room for n points; n_out is a host int.
+ *   PGICP_ERR_ARG: a size not finite and > 0 in T, a refused grid, a coordinate not finite, an argument out of range. */
+int pgicp_voxel_grid_f32(pgicp_ctx *ctx, const float *xyz, int stride, int n, int mem, const double v_size[3], int use_centroid, const float *desc,
+                         int drows, int average_descriptors, float *out_xyz, int out_stride, float *out_desc, int32_t *kept_idx, int32_t *out_count,
+                         int *n_out);
+int pgicp_voxel_grid_f64(pgicp_ctx *ctx, const double *xyz, int stride, int n, int mem, const double v_size[3], int use_centroid, const double *desc,
+                         int drows, int average_descriptors, double *out_xyz, int out_stride, double *out_desc, int32_t *kept_idx, int32_t *out_count,
+                         int *n_out);
+
 /* pgicp_filter_cloud = the localizer's input stage on the device: input_filters_.apply(cloud) (Localizer.hpp:103) for the
  * filters that only drop points, then rigid_transformation_->compute(cloud, T_robot_sensor) (Localizer.hpp:106), in one pass
  * over the uploaded scan.  `features`: frows x n column-major (a point = frows contiguous values, xyz first); `descriptors`

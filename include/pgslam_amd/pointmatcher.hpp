@@ -13,6 +13,7 @@
 // Header only; link with -lpgicp.  There is no CPU fallback: constructing an ICP
 // object without a usable GPU throws.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -147,6 +148,8 @@ template <> struct Abi<float> {
     static int sampling_normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const float *d, int dr, int avg,
                                 float *ox, float *on, float *od, int32_t *idx, int *n_out)
     { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
+    static int voxel_grid(pgicp_ctx *c, const float *x, int xs, int n, const double *v, int cen, const float *d, int dr, int avg, float *ox, float *od, int32_t *idx, int *n_out)
+    { return pgicp_voxel_grid_f32(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
     static int partial(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
     static int partial_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
     static int partial_seeded_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pgicp_partial_chain_seeded_f32(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
@@ -179,6 +182,8 @@ template <> struct Abi<double> {
     static int sampling_normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const double *d, int dr, int avg,
                                 double *ox, double *on, double *od, int32_t *idx, int *n_out)
     { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
+    static int voxel_grid(pgicp_ctx *c, const double *x, int xs, int n, const double *v, int cen, const double *d, int dr, int avg, double *ox, double *od, int32_t *idx, int *n_out)
+    { return pgicp_voxel_grid_f64(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
     static int partial(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
     static int partial_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
     static int partial_seeded_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pgicp_partial_chain_seeded_f64(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
@@ -796,6 +801,143 @@ struct PointMatcher {
             compactColumns(c, [&](int j) { return keep[j] != 0; });
         }
     };
+    //! [EXT] VoxelGridDataPointsFilter{vSizeX, vSizeY, vSizeZ, useCentroid, averageExistingDescriptors} (DataPointsFilters/
+    //! VoxelGrid.cpp): one point per non-empty voxel of a grid anchored at the cloud's minimum -- the voxel's centroid (summed in
+    //! ascending index) or centre, row 3 and further feature rows the voxel's first point's, the descriptors averaged or the first
+    //! point's -- in ascending first-point index.  The statement, with its marked deviations, is in include/pgicp.h
+    //! (pgicp_voxel_grid_*).  3-D clouds only.  On the device (the same bits) when there is one, unless PGSLAM_HOST_VOXEL_GRID=1
+    //! or the device refuses the cloud; then the host form below, which sorts (key, index) instead of allocating the dense
+    //! grid.  No deviceSpec: a chain that holds it takes the per-filter path (it changes values, pgicp_filter_cloud only drops
+    //! points).  ranOnDevice(): which of the two the last inPlaceFilter took.  From YAML the three sizes come together or not at
+    //! all (upstream fills a missing one with 1 m; here one or two sizes alone are refused).
+    struct VoxelGridDataPointsFilter : DataPointsFilter {
+        T vSizeX, vSizeY, vSizeZ; bool useCentroid, averageExistingDescriptors;
+        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
+        bool onDevice = false;
+        std::vector<T> oxBuf, odBuf;                 // the device form's outputs, kept from call to call (a 1 M-point map: no fresh pages)
+        std::vector<int32_t> idxBuf;
+        VoxelGridDataPointsFilter(T vx = T(1), T vy = T(1), T vz = T(1), bool cen = true, bool avg = true)
+            : vSizeX(vx), vSizeY(vy), vSizeZ(vz), useCentroid(cen), averageExistingDescriptors(avg)
+        {
+            for (T v : {vx, vy, vz})
+                if (!(v > T(0)) || !std::isfinite(v)) throw std::runtime_error("VoxelGridDataPointsFilter: vSizeX, vSizeY and vSizeZ must be finite and > 0");
+        }
+        VoxelGridDataPointsFilter(const VoxelGridDataPointsFilter &) = delete;
+        VoxelGridDataPointsFilter &operator=(const VoxelGridDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        //! rows 0-2 from `ox` (3 a point), rows 3.. of the first point, descriptors from `od` (drows a point)
+        static void assemble(DataPoints &c, const T *ox, const T *od, const int32_t *idx, int kept)
+        {
+            const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            Matrix f(frows, kept), d(drows, kept);
+            for (int o = 0; o < kept; o++) {
+                const int i = idx[o];
+                for (int r = 0; r < 3; r++) f(r, o) = ox[3 * (size_t)o + r];
+                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
+                for (int r = 0; r < drows; r++) d(r, o) = od[(size_t)drows * o + r];
+            }
+            c.features = f;
+            if (drows > 0) c.descriptors = d;
+        }
+        //! the device form; false (the cloud untouched) when the device refuses the arguments
+        bool deviceFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            if (oxBuf.size() < 3 * (size_t)n) oxBuf.resize(3 * (size_t)n);
+            if (odBuf.size() < (size_t)drows * n) odBuf.resize((size_t)drows * n);
+            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            const double v[3] = {(double)vSizeX, (double)vSizeY, (double)vSizeZ};
+            int kept = 0;
+            const int st = pgslam_amd::Abi<T>::voxel_grid(ctx, c.features.data(), frows, n, v, useCentroid ? 1 : 0, drows > 0 ? c.descriptors.data() : nullptr,
+                                                          drows, averageExistingDescriptors ? 1 : 0, oxBuf.data(), drows > 0 ? odBuf.data() : nullptr,
+                                                          idxBuf.data(), &kept);
+            if (st == PGICP_ERR_ARG) return false;
+            check(ctx, st);
+            assemble(c, oxBuf.data(), odBuf.data(), idxBuf.data(), kept);
+            return true;
+        }
+        //! the host form: the same statement, with a sort of (key, index) for the dense voxel array
+        void hostFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), drows = (int)c.descriptors.rows();
+            const T v[3] = {vSizeX, vSizeY, vSizeZ};
+            T lo[3], hi[3], minB[3];
+            unsigned long long nd[3];
+            for (int a = 0; a < 3; a++) { lo[a] = c.features(a, 0); hi[a] = lo[a]; }
+            for (int i = 0; i < n; i++)
+                for (int a = 0; a < 3; a++) {
+                    const T x = c.features(a, i);
+                    if (!std::isfinite(x))
+                        throw std::runtime_error("VoxelGridDataPointsFilter: a coordinate is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
+                    if (x < lo[a]) lo[a] = x;
+                    if (x > hi[a]) hi[a] = x;
+                }
+            for (int a = 0; a < 3; a++) {
+                minB[a] = lo[a] / v[a];
+                const T maxB = hi[a] / v[a];
+                const T d = (T(1) + maxB) - minB[a];
+                if (!(d < T(2147483648.0)))
+                    throw std::runtime_error("VoxelGridDataPointsFilter: the grid is too fine (a numDiv >= 2^31; a RemoveNaNDataPointsFilter or a bounding box ahead of it may help)");
+                nd[a] = (unsigned long long)(unsigned)d;
+            }
+            if ((unsigned __int128)(nd[0] * nd[1]) * nd[2] >= ((unsigned __int128)1 << 62))
+                throw std::runtime_error("VoxelGridDataPointsFilter: the grid is too fine (numDivX numDivY numDivZ >= 2^62; a RemoveNaNDataPointsFilter or a bounding box ahead of it may help)");
+            std::vector<std::pair<unsigned long long, int>> kv((size_t)n);
+            for (int i = 0; i < n; i++) {
+                unsigned long long ia[3];
+                for (int a = 0; a < 3; a++) ia[a] = (unsigned long long)(unsigned)std::floor(c.features(a, i) / v[a] - minB[a]);
+                kv[i] = {ia[0] + ia[1] * nd[0] + ia[2] * (nd[0] * nd[1]), i};
+            }
+            std::sort(kv.begin(), kv.end());
+            struct Vox { int first, start, count; };
+            std::vector<Vox> vox;
+            for (int s = 0; s < n; s++) {
+                if (s == 0 || kv[s].first != kv[s - 1].first) vox.push_back({kv[s].second, s, 0});
+                vox.back().count++;
+            }
+            std::sort(vox.begin(), vox.end(), [](const Vox &a, const Vox &b) { return a.first < b.first; });
+            const int kept = (int)vox.size();
+            Matrix ox(3, kept), od(drows > 0 ? drows : 1, kept);
+            std::vector<int32_t> idx((size_t)kept);
+            for (int o = 0; o < kept; o++) {
+                const Vox &V = vox[o];
+                const int i = V.first;
+                idx[o] = i;
+                const T cnt = (T)V.count;
+                if (useCentroid) {
+                    for (int a = 0; a < 3; a++) {
+                        T sum = c.features(a, i);
+                        for (int k = 1; k < V.count; k++) sum += c.features(a, kv[V.start + k].second);
+                        ox(a, o) = V.count == 1 ? sum : sum / cnt;
+                    }
+                } else {
+                    const unsigned long long key = kv[V.start].first, pl = nd[0] * nd[1];
+                    const unsigned long long k = key / pl, j = (key - k * pl) / nd[0], ii = key - k * pl - j * nd[0];
+                    const unsigned long long ia[3] = {ii, j, k};
+                    for (int a = 0; a < 3; a++) { const T b = minB[a] + (T)ia[a], m = b * v[a]; ox(a, o) = m + v[a] / T(2); }
+                }
+                for (int r = 0; r < drows; r++) {
+                    T sum = c.descriptors(r, i);
+                    if (averageExistingDescriptors) {
+                        for (int k = 1; k < V.count; k++) sum += c.descriptors(r, kv[V.start + k].second);
+                        if (V.count > 1) sum = sum / cnt;
+                    }
+                    od(r, o) = sum;
+                }
+            }
+            assemble(c, ox.data(), od.data(), idx.data(), kept);
+        }
+        void inPlaceFilter(DataPoints &c) override
+        {
+            onDevice = false;
+            if (c.features.rows() != 4) throw std::runtime_error("VoxelGridDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            if (c.features.cols() == 0) return;
+            const char *knob = std::getenv("PGSLAM_HOST_VOXEL_GRID");
+            static const bool have_device = pgicp_device_count() > 0;
+            if (have_device && !(knob && std::strcmp(knob, "1") == 0) && deviceFilter(c)) { onDevice = true; return; }
+            hostFilter(c);
+        }
+    };
     //! [EXT] MaxDensityDataPointsFilter{maxDensity} (DataPointsFilters/MaxDensity.cpp): needs the `densities` descriptor
     //! (SurfaceNormalDataPointsFilter{keepDensities: 1}); keeps a point at or below maxDensity, a denser one with probability
     //! maxDensity / density -- times (1 - nbSaturatedPts / nbPointsIn) in INTEGER arithmetic for points at the cloud's largest
@@ -892,6 +1034,22 @@ struct PointMatcher {
                     this->push_back(std::make_shared<SamplingSurfaceNormalDataPointsFilter>((T)ratio, knn, method, (T)to_double(get("maxBoxDim", "inf"), m.name),
                                                                                              to_double(get("averageExistingDescriptors", "1"), m.name) != 0.0,
                                                                                              to_double(get("keepNormals", "1"), m.name) != 0.0, (unsigned long long)seed));
+                } else if (m.name == "VoxelGridDataPointsFilter") {
+                    auto get = [&](const char *k) { return to_double(m.params.count(k) ? m.params.at(k) : std::string("1"), m.name); };
+                    for (auto &kv : m.params)
+                        if (kv.first != "vSizeX" && kv.first != "vSizeY" && kv.first != "vSizeZ" && kv.first != "useCentroid" && kv.first != "averageExistingDescriptors")
+                            throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    // the three sizes are given together or not at all (1 m each, upstream's defaults): one or two sizes alone would
+                    // leave the others at 1 m -- a grid of 0.1 x 1 x 1 m from `vSizeX: 0.1`, which is a typo far more often than a
+                    // choice -- so, as VarTrimmedDistOutlierFilter asks for every parameter, that is refused rather than guessed
+                    const int given = (int)m.params.count("vSizeX") + (int)m.params.count("vSizeY") + (int)m.params.count("vSizeZ");
+                    if (given != 0 && given != 3)
+                        throw std::runtime_error(m.name + ": give vSizeX, vSizeY and vSizeZ together (or none of them: 1 m each)");
+                    const double vx = get("vSizeX"), vy = get("vSizeY"), vz = get("vSizeZ");
+                    for (double vs : {vx, vy, vz})
+                        if (!(vs > 0.0) || !std::isfinite(vs) || !((T)vs > T(0)) || !std::isfinite((T)vs))
+                            throw std::runtime_error(m.name + ": vSizeX, vSizeY and vSizeZ must be finite and > 0");
+                    this->push_back(std::make_shared<VoxelGridDataPointsFilter>((T)vx, (T)vy, (T)vz, get("useCentroid") != 0.0, get("averageExistingDescriptors") != 0.0));
                 } else if (m.name == "MaxDensityDataPointsFilter") {
                     auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double md = get("maxDensity", "10"), seed = get("seed", "1");
@@ -937,7 +1095,7 @@ struct PointMatcher {
                 } else
                     throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name +
                                              "' (supported: Identity, MinDist, MaxDist, BoundingBox, RemoveNaN, SurfaceNormal, "
-                                             "SamplingSurfaceNormal, MaxDensity, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
+                                             "SamplingSurfaceNormal, VoxelGrid, MaxDensity, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
                                              "(seeded samplers, not rand()-parity))");
             }
         }

@@ -117,6 +117,7 @@ struct pgicp_ctx {
     // scan that was not pre-processed ahead, has three calls between making a reading and aligning it)
     struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop; } fset[4];
     DevBuf ssn_work, ssn_io, ssn_cnt;   // pgicp_sampling_surface_normal_*: the build's scratch, host inputs' / outputs' device copies, counters
+    DevBuf vox_work, vox_io, vox_stat;  // pgicp_voxel_grid_*: the sort's scratch, host inputs' / outputs' device copies, bounds and counters
     DevBuf robust_dev;              // RobustOutlierFilter: the pairs' absolute deviations from the median (the second selection's input)
     // (ABI 6, added) VarTrimmedDistOutlierFilter (pgicp_set_var_trim): on, {minRatio, maxRatio, lambda}; the sort's two key
     // lists (one key per pair each); the tuned ratio of every problem's last iteration in the last align / partial-chain /

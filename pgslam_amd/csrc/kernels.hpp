@@ -117,4 +117,28 @@ int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, 
                             const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
                             T *out_desc, int *kept_idx, int *counters);
 
+// pgicp_voxel_grid_*: the bounds and counters of a call (device), the grid the host derives from the bounds, and the scratch
+// (voxel_grid_scratch gives the bytes of each array, in this order)
+struct VoxStat {
+    unsigned long long lo[3], hi[3];    // order-preserving keys of each axis's min / max (-0.0 as +0.0)
+    int bad, kept, nheavy, pad;         // a coordinate is not finite; voxels (points out); voxels summed by k_vox_heavy
+};
+template <typename T>
+struct VoxGrid {
+    T v[3], minB[3];
+    unsigned long long nd[3];           // numDiv of each axis (< 2^31)
+};
+constexpr int kVoxArrays = 14;
+struct VoxScratch {
+    unsigned long long *key[2];
+    int *idx[2], *hist, *hoff, *bsum, *head, *hs, *start, *first, *vox_of, *pos;
+    int2 *heavy;
+};
+size_t voxel_grid_scratch(int n, size_t *sizes);
+template <typename T>
+void launch_voxel_bounds(hipStream_t st, const T *X, int xs, int n, VoxStat *stat);
+template <typename T>
+void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<T> &g, int bits, int centroid, const T *desc, int drows, int average,
+                       const VoxScratch &w, T *out_xyz, int os, T *out_desc, int *kept_idx, int *out_count, VoxStat *stat);
+
 }  // namespace pgicp

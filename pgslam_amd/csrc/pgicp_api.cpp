@@ -33,6 +33,7 @@ using namespace pgicp;
 #include "api_stages.inc"             // match, partial chain, outlier weights, error statistics, transform, local maps, normals
 #include "api_filters_uploads.inc"    // pgicp_filter_cloud*, batched map ABI, last-call diagnostics, map transfer, pgicp_upload_*
 #include "api_sampling.inc"           // pgicp_sampling_surface_normal_* (SamplingSurfaceNormalDataPointsFilter)
+#include "api_voxel.inc"              // pgicp_voxel_grid_* (VoxelGridDataPointsFilter)
 
 extern "C" {
 
@@ -156,6 +157,7 @@ void pgicp_ctx_destroy(pgicp_ctx *c)
         if (c->up[s].consumed) (void)hipEventDestroy(c->up[s].consumed);
     }
     c->ssn_work.release(); c->ssn_io.release(); c->ssn_cnt.release();
+    c->vox_work.release(); c->vox_io.release(); c->vox_stat.release();
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto &m : c->f32.maps) free_map<float>(nullptr, m);
     for (auto &m : c->f64.maps) free_map<double>(nullptr, m);
@@ -486,6 +488,16 @@ int pgicp_sampling_surface_normal_f64(pgicp_ctx *c, const double *xyz, int strid
                                       int out_stride, double *out_nrm, int nrm_stride, double *out_desc, int32_t *kept_idx, int *n_out, int *n_boxes)
 { return sampling_surface_normal<double>(c, xyz, stride, n, mem, knn, ratio, sampling_method, max_box_dim, seed, desc, drows, average_descriptors, out_xyz,
                                          out_stride, out_nrm, nrm_stride, out_desc, kept_idx, n_out, n_boxes); }
+int pgicp_voxel_grid_f32(pgicp_ctx *c, const float *xyz, int stride, int n, int mem, const double v_size[3], int use_centroid, const float *desc,
+                         int drows, int average_descriptors, float *out_xyz, int out_stride, float *out_desc, int32_t *kept_idx, int32_t *out_count,
+                         int *n_out)
+{ return voxel_grid<float>(c, xyz, stride, n, mem, v_size, use_centroid, desc, drows, average_descriptors, out_xyz, out_stride, out_desc, kept_idx,
+                           out_count, n_out); }
+int pgicp_voxel_grid_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int mem, const double v_size[3], int use_centroid, const double *desc,
+                         int drows, int average_descriptors, double *out_xyz, int out_stride, double *out_desc, int32_t *kept_idx, int32_t *out_count,
+                         int *n_out)
+{ return voxel_grid<double>(c, xyz, stride, n, mem, v_size, use_centroid, desc, drows, average_descriptors, out_xyz, out_stride, out_desc, kept_idx,
+                            out_count, n_out); }
 
 int pgicp_transform_f32(pgicp_ctx *c, const double T[16], const float *in, int is, float *out, int os, int n, int ro, int mem)
 { return transform<float>(c, T, in, is, out, os, n, ro, mem); }

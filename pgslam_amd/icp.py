@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "pgicp_debug_reading_order", "pgicp_partial_chain_seeded_f32", "pgicp_partial_chain_seeded_f64",
     "pgicp_sampling_surface_normal_f32", "pgicp_sampling_surface_normal_f64",
     "pgicp_set_var_trim", "pgicp_get_var_trim", "pgicp_last_var_trim_ratio",
+    "pgicp_voxel_grid_f32", "pgicp_voxel_grid_f64",
 ]
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
 
@@ -753,6 +754,44 @@ class Context:
                        C.byref(n_out), C.byref(boxes)))
         k = n_out.value
         return dict(xyz=ox[:k], normals=on[:k], kept_idx=oi[:k], descriptors=od[:k] if od is not None else None, boxes=boxes.value)
+
+    def voxel_grid(self, xyz, v_size=(1.0, 1.0, 1.0), use_centroid=True, descriptors=None, average_descriptors=True, dtype=None):
+        """VoxelGridDataPointsFilter on the device (pgicp_voxel_grid_*, statement in include/pgicp.h).  numpy in -> numpy out, torch
+        CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
+        descriptors (k,drows) or None, kept_idx (k,) int32: each voxel's first point, count (k,) int32: its points) for the k
+        non-empty voxels, in ascending first-point index."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+        x = _Buf(xyz, dtype)
+        n = x.n
+        d = None
+        drows = 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
+                assert d.ndim == 2 and d.shape[0] == n
+            drows = int(d.shape[1])
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
+            ox, oi, oc = mk((max(n, 1), 3), xyz.dtype), mk((max(n, 1),), torch.int32), mk((max(n, 1),), torch.int32)
+            od = mk((max(n, 1), drows), xyz.dtype) if d is not None else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            ox = np.empty((max(n, 1), 3), dtype=x.dtype)
+            oi, oc = np.empty(max(n, 1), dtype=np.int32), np.empty(max(n, 1), dtype=np.int32)
+            od = np.empty((max(n, 1), drows), dtype=x.dtype) if d is not None else None
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        v = (C.c_double * 3)(*[float(s) for s in v_size])
+        n_out = C.c_int(0)
+        fn = getattr(self.lib, "pgicp_voxel_grid" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), v, C.c_int(int(bool(use_centroid))), ptr(d),
+                       C.c_int(drows), C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(od), ptr(oi), ptr(oc), C.byref(n_out)))
+        k = n_out.value
+        return dict(xyz=ox[:k], descriptors=od[:k] if od is not None else None, kept_idx=oi[:k], count=oc[:k])
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
