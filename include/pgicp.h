@@ -347,6 +347,48 @@ int pgicp_outlier_weights_f64(pgicp_ctx *ctx, const double *dist2, int n, int me
 int pgicp_set_var_trim(pgicp_ctx *ctx, const double *p /* [3] minRatio, maxRatio, lambda; NULL = off */);
 int pgicp_get_var_trim(const pgicp_ctx *ctx, int *on, double *p /* [3] */);
 int pgicp_last_var_trim_ratio(pgicp_ctx *ctx, int problem, double *ratio);
+/* (ABI 6, added) [EXT] GenericDescriptorOutlierFilter{source, descName, useSoftThreshold, useLargerThan, threshold}: a weight
+ * per pair from a one-row descriptor of the reference (OutlierFiltersImpl.cpp, GenericDescriptorOutlierFilter::compute,
+ * restated from upstream's published source as recalled; nothing else pins it).  desc = the map's values
+ * (pgicp_map_set_values), id = the pair's neighbour (an index into the cloud given to pgicp_map_create), all in T:
+ *   hard, useLargerThan 1 (PGICP_DESC_FILTER_LARGER):  w = desc(id) > threshold ? 1 : 0      (strict)
+ *   hard, useLargerThan 0 (PGICP_DESC_FILTER_SMALLER): w = desc(id) < threshold ? 1 : 0      (strict)
+ *   soft (PGICP_DESC_FILTER_SOFT):                     w = desc(id) / max over the knn x N pairs of desc(id)
+ * The chain multiplies every filter's weights element by element in T; each filter is computed on its own (the TrimmedDist
+ * quantile still runs over all distances).  The only other real-valued factor is the Robust weight, and the product of two
+ * IEEE values does not depend on their order, so neither does the result.
+ * Deviations from upstream:
+ *   DEVIATION (a) (no neighbour): a pair with id == -1 weighs 0 and does not enter the soft maximum (upstream indexes the
+ *     descriptor with the invalid id).
+ *   DEVIATION (b) (values): values must be finite (refused by pgicp_map_set_values otherwise); soft mode needs values >= 0
+ *     (a call that meets a negative one is refused, PGICP_ERR_ARG).  A soft maximum of 0 gives every pair weight 0 and the
+ *     problem ends PGICP_ERR_NO_MATCH (upstream divides by zero).
+ *   DEVIATION (c) (source): only source = reference.  As recalled, upstream reads desc(0, input.ids(k, i)) for both sources,
+ *     which for a reading is the reading's descriptor at the REFERENCE's index -- nothing sensible to be faithful to; the C++
+ *     drop-in refuses `source: reading` at load time.  This rests on memory of upstream, not on its text.
+ *   DEVIATION (d) (parameters): descName must be given, and so must threshold in hard mode (no default is guessed); at most
+ *     one GenericDescriptor filter per chain.
+ * pgicp_set_descriptor_filter(mode, threshold) puts the filter in the chain (PGICP_DESC_FILTER_OFF takes it out; a hard mode
+ * needs a finite threshold, soft ignores it).  While it is on, pgicp_align*, its batches, the residual pass of
+ * pgicp_align_residual_batch_* and pgicp_partial_chain* multiply it in; pgicp_partial_chain_seeded* then searches unseeded
+ * (as it does for knn > 1).  Such a call is refused (PGICP_ERR_ARG, the context stays usable) when one of its maps has no
+ * values, or in soft mode when a map holds a negative value.  Soft mode makes the matcher resolve every query exactly in every
+ * iteration (the maximum covers pairs the distance filters drop).  pgicp_outlier_weights stays a function of the distances
+ * alone: it has no ids, so it leaves this factor out -- the caller multiplies it in.  pgicp_error_stats takes the caller's
+ * weights as they are.  pgicp_stats.n_kept and .overlap follow from the combined weight.
+ * pgicp_map_set_values_*: one value per map point in the caller's point order, values[i * stride] (stride >= 1, so one row
+ * of a column-major descriptor matrix is passed without a copy), host or device memory.  Any map id (pgicp_map_create*,
+ * pgicp_map_create_batch_*, a map indexed over a pgicp_build_local_map_* output, one handed over by pgicp_map_transfer); the
+ * values belong to the map: pgicp_map_destroy drops them, and a map later made under the same id has none.  values == NULL
+ * drops them.  (pgicp_icp_pair_* indexes a map of its own, which has none: it is refused while the filter is on.) */
+#define PGICP_DESC_FILTER_OFF 0
+#define PGICP_DESC_FILTER_LARGER 1      /* hard, useLargerThan 1 */
+#define PGICP_DESC_FILTER_SMALLER 2     /* hard, useLargerThan 0 */
+#define PGICP_DESC_FILTER_SOFT 3        /* useSoftThreshold 1 */
+int pgicp_set_descriptor_filter(pgicp_ctx *ctx, int mode, double threshold);
+int pgicp_get_descriptor_filter(const pgicp_ctx *ctx, int *mode, double *threshold);
+int pgicp_map_set_values_f32(pgicp_ctx *ctx, int map_id, const float *values, int stride, int mem);
+int pgicp_map_set_values_f64(pgicp_ctx *ctx, int map_id, const double *values, int stride, int mem);
 int pgicp_error_stats_f32(pgicp_ctx *ctx, int map_id, const float *reading, int stride, int n, int mem,
                           const int32_t *ids, const float *weights, double *weighted_point_used_ratio,
                           double *residual, double sys[30]);

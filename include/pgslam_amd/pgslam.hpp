@@ -81,8 +81,11 @@ struct Types {
 //! LocalMap<T>::BuildCloudFromData: keyframes[0] is the reference keyframe (copied as is), every
 //! other keyframe cloud is moved by T_refkf_world * optimized_T_world_kf and appended, in the given order
 //! (the reference walks its buffer newest -> oldest, LocalMap.hpp:213-223).  One device pass.
+//! `descName` (optional): a one-row descriptor to carry as an extra row after the normals, in the same point order, when every
+//! keyframe has it -- as upstream's concatenate keeps the descriptors all clouds share (a GenericDescriptorOutlierFilter's row).
+//! Left empty, or missing from a keyframe, the output is what it is without it.
 template <typename T>
-typename Types<T>::DP BuildLocalMapCloud(const std::vector<typename Types<T>::Keyframe> &keyframes)
+typename Types<T>::DP BuildLocalMapCloud(const std::vector<typename Types<T>::Keyframe> &keyframes, const std::string &descName = std::string())
 {
     using PMT = PointMatcher<T>;
     using DP = typename Types<T>::DP;
@@ -91,12 +94,29 @@ typename Types<T>::DP BuildLocalMapCloud(const std::vector<typename Types<T>::Ke
     const int k = (int)keyframes.size();
     bool all_normals = true;
     long long total = 0;
-    for (auto &kf : keyframes) { all_normals = all_normals && kf.cloud_ptr->descriptorExists("normals"); total += kf.cloud_ptr->getNbPoints(); }
+    bool all_desc = !descName.empty();
+    for (auto &kf : keyframes) {
+        all_normals = all_normals && kf.cloud_ptr->descriptorExists("normals"); total += kf.cloud_ptr->getNbPoints();
+        all_desc = all_desc && kf.cloud_ptr->descriptorExists(descName) && kf.cloud_ptr->getDescriptorDimension(descName) == 1;
+    }
+    const int drows = (all_normals ? 3 : 0) + (all_desc ? 1 : 0);
     DP out;
     out.features = typename PMT::Matrix(4, (int)total);
     out.featureLabels = keyframes[0].cloud_ptr->featureLabels;
     for (long long j = 0; j < total; j++) out.features(3, (int)j) = T(1);
-    if (all_normals) { out.descriptors = typename PMT::Matrix(3, (int)total); out.descriptorLabels.push_back(typename DP::Label("normals", 3)); }
+    if (drows) out.descriptors = typename PMT::Matrix(drows, (int)total);
+    if (all_normals) out.descriptorLabels.push_back(typename DP::Label("normals", 3));
+    if (all_desc) {
+        // (the extra row: copied as it is, keyframe after keyframe in the given order -- the points' order)
+        out.descriptorLabels.push_back(typename DP::Label(descName, 1));
+        const int r = all_normals ? 3 : 0;
+        long long j = 0;
+        for (auto &kf : keyframes) {
+            const DP &c = *kf.cloud_ptr;
+            const int cr = c.getDescriptorStartingRow(descName);
+            for (int i = 0; i < (int)c.getNbPoints(); i++) out.descriptors(r, (int)j++) = c.descriptors(cr, i);
+        }
+    }
     std::vector<const T *> xs(k), ns(k);
     std::vector<int> sx(k), sn(k), cnt(k);
     std::vector<double> Ts((size_t)16 * k, 0.0);
@@ -109,7 +129,7 @@ typename Types<T>::DP BuildLocalMapCloud(const std::vector<typename Types<T>::Ke
     }
     pgicp_ctx *ctx = pgslam_amd::default_context();
     PMT::check(ctx, pgslam_amd::Abi<T>::local_map(ctx, k, xs.data(), all_normals ? ns.data() : nullptr, sx.data(), sn.data(), cnt.data(), Ts.data(),
-                                                   out.features.data(), 4, all_normals ? out.descriptors.data() : nullptr, 3));
+                                                   out.features.data(), 4, all_normals ? out.descriptors.data() : nullptr, all_normals ? drows : 3));
     return out;
 }
 
@@ -247,7 +267,8 @@ public:
         temp_icp.referenceDataPointsFilters.apply(reference);
         temp_icp.matcher->init(reference);
         // a SurfaceNormalOutlierFilter compares descriptors of both clouds: the stage-by-stage chain below needs the reference
-        if (temp_icp.hasNormalFilter()) prepared_reference_ = std::move(reference); else prepared_reference_ = DP();
+        // (so does a GenericDescriptorOutlierFilter: its host form reads the reference's descriptor)
+        if (temp_icp.hasNormalFilter() || temp_icp.descriptorFilter()) prepared_reference_ = std::move(reference); else prepared_reference_ = DP();
     }
     //! the same for a candidate map that is in device memory already (assembled there from resident keyframe clouds): no
     //! upload; only when the chain's reference filters change nothing (false: the caller takes the host flow)
@@ -258,7 +279,8 @@ public:
             std::istringstream iss(icp_config_buffer_);
             temp_icp_->loadFromYaml(iss);
         }
-        if (!temp_icp_->referenceDataPointsFilters.allIdentity() || temp_icp_->hasNormalFilter()) return false;
+        // (a GenericDescriptorOutlierFilter needs the map's descriptor row: device clouds carry xyz and normals only)
+        if (!temp_icp_->referenceDataPointsFilters.allIdentity() || temp_icp_->hasNormalFilter() || temp_icp_->descriptorFilter()) return false;
         temp_icp_->matcher->initDevice(candidate_map_in_world_frame, 0);
         return true;
     }
@@ -373,12 +395,13 @@ public:
     }
     void MakeReference(size_t i) { std::swap(data_[i], data_.back()); }      // std::iter_swap, Localizer.hpp:220
     //! reference keyframe first, then newest -> oldest (LocalMap.hpp:213-223), one device pass
-    void BuildCloudFromData()
+    //! (`descName`: an extra descriptor row to carry, BuildLocalMapCloud)
+    void BuildCloudFromData(const std::string &descName = std::string())
     {
         std::vector<Keyframe> order;
         order.push_back(data_.back());
         for (size_t i = data_.size() - 1; i-- > 0;) order.push_back(data_[i]);
-        cloud_ = BuildLocalMapCloud<T>(order);
+        cloud_ = BuildLocalMapCloud<T>(order, descName);
     }
     //! the same order, for the device-side assembly (BuildLocalMapOnDevice)
     std::vector<Keyframe> AssemblyOrder() const
@@ -464,7 +487,7 @@ private:
         kf.id = next_id_++; kf.cloud_ptr = cloud; kf.T_world_kf = T_world_kf; kf.optimized_T_world_kf = T_world_kf;
         local_map_.PushKeyframe(kf);
     }
-    void Rebuild() { local_map_.BuildCloudFromData(); icp_sequence_.setMap(local_map_.Cloud()); rebuilds_++; }
+    void Rebuild() { local_map_.BuildCloudFromData(icp_sequence_.descriptorName()); icp_sequence_.setMap(local_map_.Cloud()); rebuilds_++; }
     LocalMap<T> local_map_;
     TransformationPtr rigid_transformation_;
     DataPointsFilters input_filters_;
@@ -515,7 +538,8 @@ public:
     //! of the candidate map if an observer (onAlign) asks for it.
     bool DeviceCandidateEquivalent() const
     {
-        return icp_.referenceDataPointsFilters.allIdentity() && icp_.deviceReadingEquivalent();
+        // (a GenericDescriptorOutlierFilter reads the candidate map's descriptor row: device clouds carry xyz and normals only)
+        return icp_.referenceDataPointsFilters.allIdentity() && icp_.deviceReadingEquivalent() && !icp_.descriptorFilter();
     }
     Result ProcessCandidateOnDevice(const DPPtr &input_cloud, const pgslam_amd::DeviceCloud<T> &input_dev, const pgslam_amd::DeviceCloud<T> &candidate_dev,
                                     const Matrix &input_T_refkf_kf, std::function<DP()> host_reference)
@@ -600,7 +624,12 @@ public:
         std::shared_ptr<pgslam_amd::DeviceCloud<T>> reading_dev, reference_dev;
     };
     pgicp_ctx *Context() { return chain_.ctx; }
-    bool DeviceCandidateEquivalent() const { return chain_.referenceDataPointsFilters.allIdentity() && chain_.deviceReadingEquivalent(); }
+    bool DeviceCandidateEquivalent() const
+    {
+        return chain_.referenceDataPointsFilters.allIdentity() && chain_.deviceReadingEquivalent() && !chain_.descriptorFilter();
+    }
+    //! the descriptor row the candidates' maps must carry ("" when the chain has no GenericDescriptorOutlierFilter)
+    std::string DescriptorName() const { return chain_.descriptorName(); }
     size_t device_batches() const { return device_batches_; }
     void SetIcpConfigFromString(const std::string &yaml) { std::istringstream iss(yaml); chain_.loadFromYaml(iss); yaml_ = yaml; }
     void Add(const Candidate &c) { queue_.push_back(c); }
@@ -655,6 +684,13 @@ public:
         }
         // every candidate's reference is indexed in one call (ICP::operator() builds it inside, LoopCloser.hpp:98)
         PM::check(ctx, pgslam_amd::Abi<T>::map_create_batch(ctx, P, xyz.data(), xs.data(), nrm.data(), ns.data(), ms.data(), 1, maps.data()));
+        // a GenericDescriptorOutlierFilter's row of every reference goes with its map (throws when one lacks it: the maps go back)
+        try {
+            for (int k = 0; k < P; k++) chain_.setMapValues(reference_of(k), maps[k]);
+        } catch (...) {
+            for (int k = 0; k < P; k++) pgicp_map_destroy(ctx, maps[k]);
+            throw;
+        }
         // a SurfaceNormalOutlierFilter acts when the readings carry normals (without them its weights are ones):
         // all of the batch's readings or none -- one device chain per call
         int with_nrm = 0;

@@ -159,6 +159,7 @@ template <> struct Abi<float> {
     static int map_create_dev(pgicp_ctx *c, const float *x, int xs, const float *n, int ns, int m, int center, int *id) { return pgicp_map_create_f32(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
     static int transform_dev(pgicp_ctx *c, const double *T16, const float *in, int is, float *out, int os, int n, int rotate_only) { return pgicp_transform_f32(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
     static int last_matches(pgicp_ctx *c, int problem, int32_t *ids, float *d2) { return pgicp_debug_last_matches_f32(c, problem, ids, d2); }
+    static int set_values(pgicp_ctx *c, int id, const float *v, int stride) { return pgicp_map_set_values_f32(c, id, v, stride, PGICP_HOST); }
 };
 template <> struct Abi<double> {
     static int map_create(pgicp_ctx *c, const double *x, int xs, const double *n, int ns, int m, int center, int *id) { return pgicp_map_create_f64(c, x, xs, n, ns, m, PGICP_HOST, center, id); }
@@ -193,6 +194,7 @@ template <> struct Abi<double> {
     static int map_create_dev(pgicp_ctx *c, const double *x, int xs, const double *n, int ns, int m, int center, int *id) { return pgicp_map_create_f64(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
     static int transform_dev(pgicp_ctx *c, const double *T16, const double *in, int is, double *out, int os, int n, int rotate_only) { return pgicp_transform_f64(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
     static int last_matches(pgicp_ctx *c, int problem, int32_t *ids, double *d2) { return pgicp_debug_last_matches_f64(c, problem, ids, d2); }
+    static int set_values(pgicp_ctx *c, int id, const double *v, int stride) { return pgicp_map_set_values_f64(c, id, v, stride, PGICP_HOST); }
 };
 
 }  // namespace pgslam_amd
@@ -1214,12 +1216,15 @@ struct PointMatcher {
             chain->pushParams();
             check(chain->ctx, A::map_create(chain->ctx, ref.xyzPtr(), ref.xyzStride(), ref.normalsPtr(), ref.normalsStride(), (int)ref.getNbPoints(), center, &mapId));
             mapSize = (int)ref.getNbPoints();
+            chain->setMapValues(ref, mapId);          // (a GenericDescriptorOutlierFilter's row of the reference; nothing without one)
         }
         //! the same over a cloud that is in device memory already (DeviceCloud): no upload
         void initDevice(const pgslam_amd::DeviceCloud<T> &ref, int center)
         {
             release();
             chain->pushParams();
+            if (chain->descriptorFilter())
+                throw std::logic_error("Matcher: a GenericDescriptorOutlierFilter needs the reference's descriptors; a device cloud carries xyz and normals only");
             check(chain->ctx, A::map_create_dev(chain->ctx, ref.xyz, ref.xs, ref.hasNormals() ? ref.nrm : nullptr, ref.ns, ref.n, center, &mapId));
             mapSize = ref.n;
         }
@@ -1365,6 +1370,53 @@ struct PointMatcher {
                     normalized(bx, by, bz);
                     if (((ax * bx + ay * by) + az * bz) < eps) w(i, j) = T(0);
                 }
+            }
+            return w;
+        }
+    };
+    //! [EXT] GenericDescriptorOutlierFilter{source, descName, useSoftThreshold, useLargerThan, threshold}: a weight per pair from the
+    //! one-row descriptor `descName` of the reference at the pair's neighbour (OutlierFiltersImpl.cpp; the statement and its marked
+    //! deviations: include/pgicp.h, pgicp_set_descriptor_filter).  Hard: desc > threshold (useLargerThan 1) or desc < threshold,
+    //! strict, 1 / 0; soft: desc / its maximum over the pairs.  Only `source: reference`; descName, and threshold in hard mode,
+    //! must be given.  Inside an ICP run the device applies it (the matcher's map carries the row: pgicp_map_set_values); this
+    //! host version serves the stage-level call of the partial chains, from Matches.ids and the reference's descriptor.
+    struct GenericDescriptorOutlierFilter : OutlierFilter {
+        std::string descName; bool soft; bool largerThan; T threshold;
+        GenericDescriptorOutlierFilter(const std::string &name, bool s, bool larger, T thr) : descName(name), soft(s), largerThan(larger), threshold(thr)
+        {
+            if (descName.empty()) throw std::runtime_error("GenericDescriptorOutlierFilter: descName must be given");
+            if (!soft && !std::isfinite((double)threshold)) throw std::runtime_error("GenericDescriptorOutlierFilter: threshold must be finite");
+        }
+        int mode() const { return soft ? PGICP_DESC_FILTER_SOFT : largerThan ? PGICP_DESC_FILTER_LARGER : PGICP_DESC_FILTER_SMALLER; }
+        //! the reference's row `descName` (throws when it is missing or is not one row)
+        int row(const DataPoints &reference) const
+        {
+            if (!reference.descriptorExists(descName))
+                throw std::runtime_error("GenericDescriptorOutlierFilter: the reference has no descriptor '" + descName + "'");
+            if (reference.getDescriptorDimension(descName) != 1)
+                throw std::runtime_error("GenericDescriptorOutlierFilter: the descriptor '" + descName + "' has more than one row");
+            return reference.getDescriptorStartingRow(descName);
+        }
+        OutlierWeights compute(const DataPoints &, const DataPoints &reference, const Matches &input) override
+        {
+            const int r = row(reference);
+            OutlierWeights w = OutlierWeights::Constant(input.ids.rows(), input.ids.cols(), T(0));
+            T mx = T(0);
+            for (int j = 0; j < w.cols(); j++)
+                for (int i = 0; i < w.rows(); i++) {
+                    const int id = input.ids(i, j);
+                    if (id < 0) continue;                         // (deviation a: no neighbour weighs 0, outside the maximum)
+                    const T v = reference.descriptors(r, id);
+                    if (!std::isfinite((double)v)) throw std::runtime_error("GenericDescriptorOutlierFilter: a value is not finite");
+                    if (soft) {
+                        if (v < T(0)) throw std::runtime_error("GenericDescriptorOutlierFilter: soft mode needs values >= 0");
+                        w(i, j) = v;
+                        if (v > mx) mx = v;
+                    } else w(i, j) = (largerThan ? v > threshold : v < threshold) ? T(1) : T(0);
+                }
+            if (soft) {
+                if (!(mx > T(0))) return OutlierWeights::Constant(w.rows(), w.cols(), T(0));       // (deviation b)
+                for (int j = 0; j < w.cols(); j++) for (int i = 0; i < w.rows(); i++) w(i, j) = w(i, j) / mx;
             }
             return w;
         }
@@ -1571,8 +1623,28 @@ struct PointMatcher {
             // the chain multiplies its filters' weights (A.4): one QUANTILE filter (TrimmedDist or MedianDist) and / or one
             // MaxDist filter, in any order
             if (y.has("outlierFilters")) {
-                int n_trim = 0, n_max = 0, n_nrm = 0;
+                int n_trim = 0, n_max = 0, n_nrm = 0, n_gd = 0;
                 for (auto &m : y.sections.at("outlierFilters")) {
+                    if (m.name == "GenericDescriptorOutlierFilter") {
+                        if (n_gd++) throw std::runtime_error("GenericDescriptorOutlierFilter: at most one per chain");
+                        std::string source = "reference", name;
+                        bool soft = false, larger = true, hasThr = false;
+                        T thr = T(0);
+                        for (auto &kv : m.params) {
+                            if (kv.first == "source") source = kv.second;
+                            else if (kv.first == "descName") name = kv.second;
+                            else if (kv.first == "useSoftThreshold") soft = to_double(kv.second, "useSoftThreshold") != 0.0;
+                            else if (kv.first == "useLargerThan") larger = to_double(kv.second, "useLargerThan") != 0.0;
+                            else if (kv.first == "threshold") { thr = (T)to_double(kv.second, "threshold"); hasThr = true; }
+                            else throw std::runtime_error("GenericDescriptorOutlierFilter: unknown parameter " + kv.first);
+                        }
+                        // (deviation c: upstream's reading source reads the reading's descriptor at the reference's index)
+                        if (source != "reference") throw std::runtime_error("GenericDescriptorOutlierFilter: source " + source + " is not supported (reference)");
+                        if (name.empty()) throw std::runtime_error("GenericDescriptorOutlierFilter: parameter descName must be given");
+                        if (!soft && !hasThr) throw std::runtime_error("GenericDescriptorOutlierFilter: parameter threshold must be given (hard mode)");
+                        outlierFilters.push_back(std::make_shared<GenericDescriptorOutlierFilter>(name, soft, larger, thr));
+                        continue;
+                    }
                     if (m.name == "SurfaceNormalOutlierFilter" && n_nrm++ == 0) {
                         outlierFilters.push_back(std::make_shared<SurfaceNormalOutlierFilter>(m.params.count("maxAngle") ? (T)to_double(m.params.at("maxAngle"), "maxAngle") : T(1.57)));
                         continue;
@@ -1614,7 +1686,7 @@ struct PointMatcher {
                     else
                         throw std::runtime_error("loadFromYaml: unsupported outlier filter chain at " + m.name +
                                                  " (supported: one of TrimmedDistOutlierFilter, VarTrimmedDistOutlierFilter, MedianDistOutlierFilter or RobustOutlierFilter, and / or one MaxDistOutlierFilter, "
-                                                 "and / or one SurfaceNormalOutlierFilter)");
+                                                 "and / or one SurfaceNormalOutlierFilter, and / or one GenericDescriptorOutlierFilter)");
                 }
             } else outlierFilters.push_back(std::make_shared<TrimmedDistOutlierFilter>(this, T(0.85)));
             errorMinimizer = std::make_shared<ErrorMinimizer>(this);
@@ -1706,6 +1778,8 @@ struct PointMatcher {
             check(ctx, pgicp_set_params(ctx, &p));
             if (vt) { const double q[3] = {(double)vt->minRatio, (double)vt->maxRatio, (double)vt->lambda}; check(ctx, pgicp_set_var_trim(ctx, q)); }
             else check(ctx, pgicp_set_var_trim(ctx, nullptr));
+            if (const GenericDescriptorOutlierFilter *gd = descriptorFilter()) check(ctx, pgicp_set_descriptor_filter(ctx, gd->mode(), (double)gd->threshold));
+            else check(ctx, pgicp_set_descriptor_filter(ctx, PGICP_DESC_FILTER_OFF, 0.0));
         }
         //! LoopCloser.hpp:317
         bool getMaxNumIterationsReached() const { return lastStats.max_iter_reached != 0; }
@@ -1740,8 +1814,9 @@ struct PointMatcher {
         T sensorNoiseOverlap(const DataPoints &reading, int problem, const pgicp_stats &st) const
         {
             for (auto &f : outlierFilters)
-                if (std::dynamic_pointer_cast<RobustOutlierFilter>(f) || std::dynamic_pointer_cast<SurfaceNormalOutlierFilter>(f))
-                    throw std::runtime_error("getOverlap: the sensor-noise overlap (a reading with simpleSensorNoise) is not supported with a Robust / SurfaceNormal outlier filter");
+                if (std::dynamic_pointer_cast<RobustOutlierFilter>(f) || std::dynamic_pointer_cast<SurfaceNormalOutlierFilter>(f) ||
+                    std::dynamic_pointer_cast<GenericDescriptorOutlierFilter>(f))
+                    throw std::runtime_error("getOverlap: the sensor-noise overlap (a reading with simpleSensorNoise) is not supported with a Robust / SurfaceNormal / GenericDescriptor outlier filter");
             const int n = (int)reading.getNbPoints(), knn = std::max(1, matcher ? matcher->knn : 1);
             std::vector<int32_t> ids((size_t)n * knn);
             std::vector<T> d2((size_t)n * knn);
@@ -1782,6 +1857,23 @@ struct PointMatcher {
         };
         //! a device copy of a cloud may stand for the cloud itself in operator(): the chain's reading filters change nothing
         //! and no outlier filter looks at the reading's descriptors
+        //! the chain's GenericDescriptorOutlierFilter, or null
+        const GenericDescriptorOutlierFilter *descriptorFilter() const
+        {
+            for (auto &f : outlierFilters) if (auto g = std::dynamic_pointer_cast<GenericDescriptorOutlierFilter>(f)) return g.get();
+            return nullptr;
+        }
+        //! its descName ("" without the filter): the row a local map built for this chain must carry (BuildLocalMapCloud)
+        std::string descriptorName() const { const GenericDescriptorOutlierFilter *g = descriptorFilter(); return g ? g->descName : std::string(); }
+        //! the map `mapId` made from `ref` gets the filter's row of it (pgicp_map_set_values, a view of the column-major matrix:
+        //! stride = rows); throws when the row is missing or is not one row.  Nothing without the filter.
+        void setMapValues(const DataPoints &ref, int mapId)
+        {
+            const GenericDescriptorOutlierFilter *gd = descriptorFilter();
+            if (!gd || ref.getNbPoints() == 0) return;
+            const int r = gd->row(ref);
+            check(ctx, A::set_values(ctx, mapId, ref.descriptors.data() + r, (int)ref.descriptors.rows()));
+        }
         bool hasNormalFilter() const
         {
             for (auto &f : outlierFilters) if (std::dynamic_pointer_cast<SurfaceNormalOutlierFilter>(f)) return true;
@@ -1903,7 +1995,7 @@ struct PointMatcher {
         bool hasMap() const { return mapPointCloud.getNbPoints() != 0 || mapOnDevice; }
         //! a map that is in device memory already (the localizer assembles it there from resident keyframe clouds) may stand
         //! for setMap(cloud): the chain's reference filters change nothing
-        bool deviceMapEquivalent() const { return this->referenceDataPointsFilters.allIdentity(); }
+        bool deviceMapEquivalent() const { return this->referenceDataPointsFilters.allIdentity() && !this->descriptorFilter(); }
         //! setMap for such a map: mean-centre + index build, no cloud crosses PCIe.  `hostCopy` makes the host cloud if an
         //! observer (onAlign) or getPrefilteredMap() asks for it.
         bool setMap(const pgslam_amd::DeviceCloud<T> &deviceCloud, std::function<DataPoints()> hostCopy)

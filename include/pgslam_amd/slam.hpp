@@ -699,7 +699,8 @@ public:
     };
     void SetDeviceCandidates(bool on) { device_candidates_ = on; }
     size_t device_candidates() const { return device_candidates_made_; }
-    bool PrepareCandidate(size_t input_v, PreparedCandidate &out, pgicp_ctx *device_ctx = nullptr)
+    //! (`descName`: the chain's GenericDescriptorOutlierFilter row, carried by the host-built candidate map)
+    bool PrepareCandidate(size_t input_v, PreparedCandidate &out, pgicp_ctx *device_ctx = nullptr, const std::string &descName = std::string())
     {
         auto lock = map_manager_->GetGraphLock();
         auto &g = map_manager_->GetGraph();
@@ -725,7 +726,7 @@ public:
             return true;
         }
         for (size_t v : comp) lm.PushKeyframe(g[v]);
-        lm.BuildCloudFromData();
+        lm.BuildCloudFromData(descName);
         out.reference = std::make_shared<DP>(lm.Cloud());
         return true;
     }
@@ -733,7 +734,7 @@ public:
     {
         PreparedCandidate c;
         PairLoopCloser<T> &lc = closer();
-        if (!PrepareCandidate(input_v, c, lc.DeviceCandidateEquivalent() ? (pgicp_ctx *)lc.icp().ctx : nullptr)) return;
+        if (!PrepareCandidate(input_v, c, lc.DeviceCandidateEquivalent() ? (pgicp_ctx *)lc.icp().ctx : nullptr, lc.icp().descriptorName())) return;
         auto r = c.reference_dev ? lc.ProcessCandidateOnDevice(c.reading, *c.reading_dev, *c.reference_dev, c.guess, c.host_reference)
                                  : lc.ProcessCandidate(*c.reading, *c.reference, c.guess);                     // :98 + CheckIcpResult
         if (r.accepted) {
@@ -1046,7 +1047,7 @@ protected:
         } else {
             map_segs_.clear();
             for (size_t v : comp_) lm.PushKeyframe(g[v]);
-            lm.BuildCloudFromData();
+            lm.BuildCloudFromData(icp_sequence_.descriptorName());
             icp_sequence_.setMap(lm.Cloud());
         }
         rebuilds_++;
@@ -1079,7 +1080,7 @@ protected:
             }
             if (!prepared) {
                 probe_segs_.clear();
-                lm.BuildCloudFromData();
+                lm.BuildCloudFromData(icp_sequence_.descriptorName());
                 const DP world_map = rigid_->compute(lm.Cloud(), g[comp.back()].optimized_T_world_kf);
                 probe_->PrepareOverlapReference(world_map);
             }
@@ -1402,7 +1403,7 @@ private:
             pgicp_ctx *dev_ctx = batch.DeviceCandidateEquivalent() ? batch.Context() : nullptr;
             for (size_t v : vs) {
                 typename Base::PreparedCandidate c;
-                if (this->PrepareCandidate(v, c, dev_ctx)) cands.push_back(c);
+                if (this->PrepareCandidate(v, c, dev_ctx, batch.DescriptorName())) cands.push_back(c);
             }
             // a reading with `simpleSensorNoise` takes getOverlap()'s sensor-noise branch, which reads the ICP's LAST error elements:
             // the batch's fused residual pass replaces them, so such candidates go one at a time (the base class's ProcessCandidate)

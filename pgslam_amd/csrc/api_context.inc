@@ -61,6 +61,11 @@ struct MapHost {
     float *sc_ext = nullptr;
     unsigned *occ = nullptr;
     float *ptsf = nullptr;          // MapDev::ptsf (double maps)
+    // (ABI 6, added) GenericDescriptorOutlierFilter: the map's values in slot order (pgicp_map_set_values; MapDev::val), their own
+    // allocation -- dropped with the record -- and whether one of them is negative (soft mode refuses the map then)
+    std::shared_ptr<SharedBlock> vblock;
+    T *val = nullptr;
+    bool val_neg = false;
     int first = 0;                  // MapDev::first
     // the one device allocation holding all of the above -- shared by the maps of one batched build and
     // returned to the pool (or freed) by whoever drops the last reference
@@ -119,6 +124,7 @@ struct pgicp_ctx {
     DevBuf ssn_work, ssn_io, ssn_cnt;   // pgicp_sampling_surface_normal_*: the build's scratch, host inputs' / outputs' device copies, counters
     DevBuf vox_work, vox_io, vox_stat;  // pgicp_voxel_grid_*: the sort's scratch, host inputs' / outputs' device copies, bounds and counters
     DevBuf robust_dev;              // RobustOutlierFilter: the pairs' absolute deviations from the median (the second selection's input)
+    DevBuf gd_stage;                // pgicp_map_set_values: host values packed for the copy, and the kernel's two flags
     // (ABI 6, added) VarTrimmedDistOutlierFilter (pgicp_set_var_trim): on, {minRatio, maxRatio, lambda}; the sort's two key
     // lists (one key per pair each); the tuned ratio of every problem's last iteration in the last align / partial-chain /
     // outlier-weights call (empty: that call did not run the filter)
@@ -126,6 +132,9 @@ struct pgicp_ctx {
     double vt[3] = {0.0, 0.0, 0.0};
     DevBuf vt_keys, vt_prob;
     std::vector<double> vt_last;
+    // (ABI 6, added) GenericDescriptorOutlierFilter (pgicp_set_descriptor_filter): PGICP_DESC_FILTER_*, the hard modes' threshold
+    int gd_mode = 0;
+    double gd_thr = 0.0;
     int fset_next = 0;
     int up_next = 0;
     int up_seen = 0;            // upload sets whose device pointers the running call was handed (see UploadUse)
@@ -356,6 +365,7 @@ ChainDev<T> make_chain(const pgicp_params &p)
     ch.normal_cos = std::cos((T)p.normal_max_angle);          // in T, as the filter evaluates `cos(maxAngle)`
     ch.scan_pos = nullptr;                                     // (set by chain_of: it names a buffer of the context)
     ch.var_trim = 0; ch.vt_min = ch.vt_max = ch.vt_lambda = 0.0;   // (set by chain_of: a setting of the context)
+    ch.gd_mode = PGICP_DESC_FILTER_OFF; ch.gd_thr = (T)0;            // (the same)
     return ch;
 }
 
@@ -368,6 +378,7 @@ ChainDev<T> chain_of(pgicp_ctx *c, const pgicp_params &p)
     ch.scan_pos = p.sum_order == PGICP_SUM_ORDER_SCAN ? c->scan_pos.as<int>() : nullptr;
     ch.var_trim = c->vt_on;
     ch.vt_min = c->vt[0]; ch.vt_max = c->vt[1]; ch.vt_lambda = c->vt[2];
+    ch.gd_mode = c->gd_mode; ch.gd_thr = (T)c->gd_thr;              // (the threshold in T, as the comparison is)
     return ch;
 }
 

@@ -56,6 +56,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
             return fail(c, PGICP_ERR_ARG, "pgicp: bad reading in problem " + std::to_string(p));
         MapHost<T> *M = get_map<T>(c, pr[p].map_id);
         if (!M) return fail(c, PGICP_ERR_ARG, "pgicp: unknown map id " + std::to_string(pr[p].map_id));
+        { const int gst = descriptor_filter_check<T>(c, M, pr[p].map_id); if (gst) return gst; }
         L.max_n = std::max(L.max_n, pr[p].n);
         L.table_kinds |= M->sw ? 2 : 1;
         L.max_h = std::max(L.max_h, (double)M->g.h);
@@ -261,6 +262,7 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
             } else {
                 launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_pairs(), 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, use_seed);
             }
+            if (ch.gd_mode == PGICP_DESC_FILTER_SOFT) launch_gd_max<T>(c->stream, probs, maps, S.slot.template as<int>(), nA, L.max_pairs(), active);
         }
         {
             ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);
@@ -302,6 +304,10 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
     // RobustOutlierFilter: nothing is trimmed -- the threshold the lazy path resolves queued queries up to is +inf from here on;
     // VarTrimmedDistOutlierFilter: its ratio is chosen over every distance -- the same
     if (robust || ch.var_trim) launch_robust_open(c->stream, probs, active, nA);
+    // GenericDescriptorOutlierFilter, soft mode: its maximum covers every pair with a neighbour -- the same, and (no Robust /
+    // VarTrimmed filter to set it) the second selection below must then restore the iteration's threshold
+    const bool gd_soft = ch.gd_mode == PGICP_DESC_FILTER_SOFT;
+    if (gd_soft && !robust && !ch.var_trim && c->prm.matcher == PGICP_MATCHER_GRID) launch_gd_open(c->stream, probs, active, nA);
     if (c->prm.matcher == PGICP_MATCHER_GRID) {
         // lazy resolution: only queued queries whose lower bound is within the threshold just
         // selected (an upper bound of the final one) are searched exactly; then the threshold
@@ -336,6 +342,11 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
         // the scale of this iteration from the (now exact) distances: median, absolute deviations, their median
         ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
         launch_robust_scale<T>(c->stream, probs, S.d2.template as<T>(), c->robust_dev.as<T>(), ch, nA, L.max_n, active, c->sel_tables.as<int>(), c->qtmp.p);
+    }
+    if (gd_soft) {
+        // every pair is exact now: the soft maximum of this iteration
+        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
+        launch_gd_max<T>(c->stream, probs, maps, S.slot.template as<int>(), nA, L.max_n, active);
     }
     {
         ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);

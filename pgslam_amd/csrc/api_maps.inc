@@ -17,6 +17,7 @@ int sync_maps_table(pgicp_ctx *c)
         h[i].cell_start_f = m.cell_start_f; h[i].kx = m.kx; h[i].sw = m.sw; h[i].ostart = m.ostart;
         h[i].sc_count = m.sc_count;
         h[i].slot_of = m.slot_of;
+        h[i].val = m.val;
         h[i].near = m.near;
         h[i].sc_dist = m.sc_dist;
         h[i].sc_wit = m.sc_wit;
@@ -357,3 +358,59 @@ int map_create(pgicp_ctx *c, const T *xyz, int xyz_stride, const T *nrm, int nrm
     return map_create_batch<T>(c, 1, &s, mem, center, map_id);
 }
 
+
+// pgicp_map_set_values: values[i * stride] of every map point i, into the map's slot order (its own allocation)
+template <typename T>
+int map_set_values(pgicp_ctx *c, int map_id, const T *values, int stride, int mem)
+{
+    if (!c) return PGICP_ERR_ARG;
+    MapHost<T> *M = get_map<T>(c, map_id);
+    if (!M) return fail(c, PGICP_ERR_ARG, "pgicp_map_set_values: unknown map id");
+    HIPC(c, hipSetDevice(c->device));
+    if (!values) {
+        HIPC(c, stream_sync(c));                  // (work queued on the stream may still read the old values)
+        M->vblock.reset(); M->val = nullptr; M->val_neg = false;
+        return sync_maps_table<T>(c);
+    }
+    if (stride < 1 || (mem != PGICP_HOST && mem != PGICP_DEVICE)) return fail(c, PGICP_ERR_ARG, "pgicp_map_set_values: bad argument");
+    const int m = M->m;
+    const size_t vbytes = sizeof(T) * (size_t)m;
+    const T *d_src = values;
+    int d_stride = stride;
+    std::vector<T> packed;
+    HIPC(c, c->gd_stage.ensure(64 + (mem == PGICP_HOST ? vbytes : 0)));
+    if (mem == PGICP_HOST) {
+        packed.resize((size_t)m);
+        for (int i = 0; i < m; i++) packed[(size_t)i] = values[(size_t)i * stride];
+        XFER(c, h2d(c, (char *)c->gd_stage.p + 64, packed.data(), vbytes));
+        d_src = (const T *)((char *)c->gd_stage.p + 64);
+        d_stride = 1;
+    }
+    auto blk = std::make_shared<SharedBlock>();
+    HIPC(c, t_malloc((void **)&blk->p, vbytes));
+    blk->bytes = vbytes;
+    HIPC(c, hipMemsetAsync(c->gd_stage.p, 0, 2 * sizeof(int), c->stream));
+    launch_map_values<T>(c->stream, M->pts, M->first, m, d_src, d_stride, (T *)blk->p, c->gd_stage.as<int>());
+    int flags[2] = {0, 0};
+    XFER(c, d2h(c, flags, c->gd_stage.p, sizeof flags));
+    HIPC(c, stream_sync(c));
+    HIPC(c, hipGetLastError());
+    if (flags[0]) return fail(c, PGICP_ERR_ARG, "pgicp_map_set_values: a value is not finite (GenericDescriptorOutlierFilter)");
+    // (the old values, if any, go now: nothing queued reads them any more -- the stream has run dry)
+    M->vblock = blk;
+    M->val = (T *)blk->p;
+    M->val_neg = flags[1] != 0;
+    return sync_maps_table<T>(c);
+}
+
+// every map of a call that runs the GenericDescriptor filter must carry values (non-negative ones in soft mode)
+template <typename T>
+int descriptor_filter_check(pgicp_ctx *c, const MapHost<T> *M, int map_id)
+{
+    if (c->gd_mode == PGICP_DESC_FILTER_OFF) return PGICP_OK;
+    if (!M->val)
+        return fail(c, PGICP_ERR_ARG, "GenericDescriptorOutlierFilter: map " + std::to_string(map_id) + " has no values (pgicp_map_set_values)");
+    if (c->gd_mode == PGICP_DESC_FILTER_SOFT && M->val_neg)
+        return fail(c, PGICP_ERR_ARG, "GenericDescriptorOutlierFilter: soft mode needs values >= 0 (map " + std::to_string(map_id) + " holds a negative one)");
+    return PGICP_OK;
+}

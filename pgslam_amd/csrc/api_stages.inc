@@ -14,6 +14,9 @@ int run_partial(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, i
     // (the matcher alone: no outlier filter runs here, so a SurfaceNormalOutlierFilter's normals are not asked for)
     struct NoNormals { pgicp_ctx *c; double a; ~NoNormals() { c->prm.normal_max_angle = a; } } restore{c, c->prm.normal_max_angle};
     c->prm.normal_max_angle = 0.0;
+    // (matching alone: the GenericDescriptor filter weighs pairs, it does not need the map's values here)
+    struct NoDesc { pgicp_ctx *c; int m; ~NoDesc() { c->gd_mode = m; } } restore_gd{c, c->gd_mode};
+    c->gd_mode = PGICP_DESC_FILTER_OFF;
     int st = batch_begin<T>(c, 1, &pr, [&](int, double *Tpre) {
         double mean[3] = {(double)M->mean[0], (double)M->mean[1], (double)M->mean[2]};
         double Tm_inv[16];
@@ -89,6 +92,7 @@ int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ra
     for (int p = 0; p < P; p++) {
         MapHost<T> *M = get_map<T>(c, pr[p].map_id);
         if (!M) return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain: unknown map id");
+        { const int gst = descriptor_filter_check<T>(c, M, pr[p].map_id); if (gst) return gst; }
         if (!M->has_nrm && needs_ref_normals(c->prm))
             return fail(c, PGICP_ERR_ARG, "pgicp: reference has no normals descriptor");
     }
@@ -100,7 +104,8 @@ int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ra
     // all of it is one kernel instead of the reading sort.  Mode 2 of the matcher: seeds are read, the pass has no history.
     BorrowSpec bs;
     bool borrow = false;
-    if (seed && P == 1 && std::max(1, c->prm.knn) == 1 && c->prm.matcher == PGICP_MATCHER_GRID && !(c->prm.normal_max_angle > 0.0) && seed->src && seed->src != c &&
+    if (seed && P == 1 && std::max(1, c->prm.knn) == 1 && c->prm.matcher == PGICP_MATCHER_GRID && !(c->prm.normal_max_angle > 0.0) &&
+        c->gd_mode == PGICP_DESC_FILTER_OFF && seed->src && seed->src != c &&
         seed->src->device == c->device && seed->n_seg > 0 && seed->n_seg <= 16 && seed->src->last_n0 == pr[0].n && seed->src->template last_is<T>()) {
         pgicp_ctx *a = seed->src;
         State<T> &SA = state<T>(a);

@@ -51,6 +51,8 @@ struct MapDev {
     const float *ptsf;                   // double maps only (else null): the points again as (float x, y, z, index bits) records of 16 bytes, same
                                          // order -- the fast matcher's prefilter reads these and the double record only of a candidate that may win
     const int *slot_of;                  // original index -> position in pts / nrm
+    const T *val;                        // (ABI 6, added) GenericDescriptorOutlierFilter: the map's values (pgicp_map_set_values) in slot
+                                         // order, val[s - first] for slot s; null: the map has none
     const int *near;                     // per 2x2x2 block of cells: a nearby occupied cell, -1 if none within kNearReach
     const unsigned *occ;                 // one bit per cell (cell id = bit index): occupied.  64x smaller than the tables, so it
                                          // stays in L2 where they do not: the searches that walk mostly EMPTY rows test it first
@@ -111,6 +113,10 @@ struct ChainDev {
     // (k_var_trim -> ProblemDev::vt_ratio); var_trim 0: not in the chain
     int var_trim;
     double vt_min, vt_max, vt_lambda;
+    // (ABI 6, added) GenericDescriptorOutlierFilter: PGICP_DESC_FILTER_OFF (0, not in the chain) / _LARGER / _SMALLER / _SOFT, and
+    // the hard modes' threshold in T; the values are the map's (MapDev::val)
+    int gd_mode;
+    T gd_thr;
     // (ABI 6, per call rather than per chain) PGICP_SUM_ORDER_SCAN: sorted position of every reading point of the batch -- the
     // inverse of the reading sort, indexed like the per-point arrays -- so that the reduce kernels can walk the pairs in the
     // caller's order; null: they walk the sorted order
@@ -158,6 +164,9 @@ struct ProblemDev {
     double vt_ratio;         // VarTrimmedDistOutlierFilter: this iteration's tuned ratio (k_var_trim), -1: no positive finite distance
     int vt_count;            // ... and the number of positive finite distances it was chosen over
     int vt_pad_;
+    // GenericDescriptorOutlierFilter, soft mode: the largest value over this iteration's pairs with a neighbour, as the bits of a
+    // T >= 0 (k_gd_max: an integer atomicMax, exact); k_solve_update moves it to gd_last and clears it for the next iteration
+    unsigned long long gd_key, gd_last;
     double sys[kSys];        // final sums of the last iteration
     Checker chk;
 };
@@ -167,6 +176,11 @@ struct ProblemDev {
 #define PGICP_ST_NO_MATCH 1
 #define PGICP_ST_NAN 2
 #define PGICP_ST_BOUND 3     // BoundTransformationChecker's limit exceeded (PGICP_ERR_BOUND at the ABI)
+// GenericDescriptorOutlierFilter modes (mirror pgicp.h's PGICP_DESC_FILTER_*: the same tokens, so both may be included)
+#define PGICP_DESC_FILTER_OFF 0
+#define PGICP_DESC_FILTER_LARGER 1
+#define PGICP_DESC_FILTER_SMALLER 2
+#define PGICP_DESC_FILTER_SOFT 3
 
 struct Mat34 { double v[12]; };                    // row-major 3x4, kernel argument
 // where a problem's reading lives (device); nptr: its `normals` descriptor, or null

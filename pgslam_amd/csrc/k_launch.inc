@@ -310,9 +310,10 @@ void launch_reduce(hipStream_t st, const ProblemDev *probs, const MapDev<T> *map
 {
     const int nb = reduce_blocks(max_n);
     const dim3 grid(nb, P), block(kReduceBlock);
-    const bool gen = ch.knn > 1 || rd_nrm != nullptr || ch.robust.fct != 0;
+    const bool gen = ch.knn > 1 || rd_nrm != nullptr || ch.robust.fct != 0 || ch.gd_mode != PGICP_DESC_FILTER_OFF;
 #define PGICP_REDUCE_LAUNCH(MIN, GEN) \
-    hipLaunchKernelGGL((k_p2plane_reduce<T, MIN, GEN>), grid, block, 0, st, probs, maps, rd_pre, rd_nrm, slot, d2, partials, nb, active, ch.normal_cos, ch.robust, ch.scan_pos)
+    hipLaunchKernelGGL((k_p2plane_reduce<T, MIN, GEN>), grid, block, 0, st, probs, maps, rd_pre, rd_nrm, slot, d2, partials, nb, active, ch.normal_cos, ch.robust, ch.scan_pos, \
+                       ch.gd_mode, ch.gd_thr)
     if (ch.minimizer == 1) { if (gen) PGICP_REDUCE_LAUNCH(1, true); else PGICP_REDUCE_LAUNCH(1, false); }
     else { if (gen) PGICP_REDUCE_LAUNCH(0, true); else PGICP_REDUCE_LAUNCH(0, false); }
 #undef PGICP_REDUCE_LAUNCH
@@ -332,7 +333,12 @@ void launch_cov(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, 
                 const T *d2, double *partials, double *out, int P, int max_n, const ChainDev<T> &ch)
 {
     const int nb = reduce_blocks(max_n);
-    hipLaunchKernelGGL(k_cov_reduce<T>, dim3(nb, P), dim3(kReduceBlock), 0, st, probs, maps, rd_pre, rd_nrm, slot, d2, partials, nb, ch.normal_cos, ch.robust, ch.scan_pos);
+    if (ch.gd_mode != PGICP_DESC_FILTER_OFF)
+        hipLaunchKernelGGL((k_cov_reduce<T, true>), dim3(nb, P), dim3(kReduceBlock), 0, st, probs, maps, rd_pre, rd_nrm, slot, d2, partials, nb, ch.normal_cos,
+                           ch.robust, ch.scan_pos, ch.gd_mode, ch.gd_thr);
+    else
+        hipLaunchKernelGGL((k_cov_reduce<T, false>), dim3(nb, P), dim3(kReduceBlock), 0, st, probs, maps, rd_pre, rd_nrm, slot, d2, partials, nb, ch.normal_cos,
+                           ch.robust, ch.scan_pos, ch.gd_mode, ch.gd_thr);
     hipLaunchKernelGGL(k_sum_partials, dim3(P), dim3(256), 0, st, (const double *)partials, nb, kCovTerms, probs, 0, out);
 }
 
@@ -341,6 +347,22 @@ void launch_robust_open(hipStream_t st, ProblemDev *probs, const int *active, in
 {
     hipLaunchKernelGGL(k_robust_open, dim3(cdiv(n_active, 64)), dim3(64), 0, st, probs, active, n_active);
 }
+// GenericDescriptorOutlierFilter (k_minimise.inc): soft mode's uncapped matcher; the soft maximum of this iteration; the values
+void launch_gd_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active)
+{
+    hipLaunchKernelGGL(k_gd_open, dim3(cdiv(n_active, 64)), dim3(64), 0, st, probs, active, n_active);
+}
+template <typename T>
+void launch_gd_max(hipStream_t st, ProblemDev *probs, const MapDev<T> *maps, const int *slot, int n_active, int max_pairs, const int *active)
+{
+    hipLaunchKernelGGL(k_gd_max<T>, dim3(cdiv(max_pairs, 256 * kGdMaxItems), n_active), dim3(256), 0, st, probs, maps, slot, active);
+}
+template <typename T>
+void launch_map_values(hipStream_t st, const typename Vec4<T>::type *pts, int first, int m, const T *values, int stride, T *out, int *flags)
+{
+    hipLaunchKernelGGL(k_map_values<T>, dim3(cdiv(m, 256)), dim3(256), 0, st, pts, first, m, values, stride, out, flags);
+}
+
 template <typename T>
 void launch_robust_scale(hipStream_t st, ProblemDev *probs, const T *d2, T *dev, const ChainDev<T> &ch, int n_active, int max_pairs,
                          const int *active, int *tables, void *keys)
@@ -482,6 +504,8 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     template void launch_filter_cloud<T>(hipStream_t, const T *, int, int, const T *, int, int, int, const int *, const double *,   \
                                          const double *, int, int, int *, int *, int *, T *, T *, int *, int *, int);       \
     template void launch_slot_of<T>(hipStream_t, const typename Vec4<T>::type *, int, int, int *);                       \
+    template void launch_gd_max<T>(hipStream_t, ProblemDev *, const MapDev<T> *, const int *, int, int, const int *);     \
+    template void launch_map_values<T>(hipStream_t, const typename Vec4<T>::type *, int, int, const T *, int, T *, int *); \
     template void launch_borrow_order<T>(hipStream_t, const ProblemDev *, const SrcDesc *, const int *, const int *, const typename Vec4<T>::type *, int, const SeedSegs &, \
                                          const int *, int, T *, int *, int *);                                            \
     template int launch_surface_normals<T>(hipStream_t, const MapDev<T> *, int, int, int, T, T, T *, int, T *, int *, T *); \

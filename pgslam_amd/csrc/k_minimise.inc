@@ -96,6 +96,16 @@ __device__ __forceinline__ T robust_weight(const RobustDev<T> &rb, T dd, T s2)
     return w;
 }
 
+// [EXT] GenericDescriptorOutlierFilter's weight of a pair whose neighbour's value is v (pgicp.h, pgicp_set_descriptor_filter; in
+// T): hard modes 1 / 0 by the strict comparison, soft v / gmax -- and 0 when the soft maximum is 0 (deviation b)
+template <typename T>
+__device__ __forceinline__ T gd_weight(int mode, T thr, T v, T gmax)
+{
+    if (mode == PGICP_DESC_FILTER_LARGER) return v > thr ? (T)1 : (T)0;
+    if (mode == PGICP_DESC_FILTER_SMALLER) return v < thr ? (T)1 : (T)0;
+    return gmax > (T)0 ? v / gmax : (T)0;
+}
+
 template <typename T, int MIN, bool GEN>
 __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDev *__restrict__ probs,
                                                                   const MapDev<T> *__restrict__ maps,
@@ -103,7 +113,7 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
                                                                   const int *__restrict__ slot,
                                                                   const T *__restrict__ d2, double *__restrict__ partials,
                                                                   int max_blocks, const int *__restrict__ active, T normal_cos, RobustDev<T> rb,
-                                                                  const int *__restrict__ scan_pos)
+                                                                  const int *__restrict__ scan_pos, int gd_mode, T gd_thr)
 {
     // The reduction tree RT-1 (oracle/icp_oracle.c, DESIGN.md section 2): this block is tree block `tile`, thread t adds the pairs
     // at tree positions tile * kReduceSpan + u * 256 + t, u = 0 .. 7, in that order (T2); block_reduce_store is T3 + T4, the solve
@@ -123,6 +133,8 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
     const T limit = (T)P.limit;
     const bool use_nrm = GEN && rd_nrm != nullptr;
     const bool need_nrm = MIN == 0 || use_nrm;
+    const bool gd = GEN && gd_mode != PGICP_DESC_FILTER_OFF;
+    const T gmax = GEN ? Bits<T>::val((typename Bits<T>::U)P.gd_key) : (T)0;
     double acc[kSys];
 #pragma unroll
     for (int k = 0; k < kSys; k++) acc[k] = 0.0;
@@ -150,6 +162,7 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
     }
     V4 mp[kReduceItems], mn[kReduceItems];
     T qv[kReduceItems][3], qn[kReduceItems][3];
+    T gv[GEN ? kReduceItems : 1];
 #pragma unroll
     for (int it = 0; it < kReduceItems; it++) {
         const int e = es[it];
@@ -159,8 +172,10 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
         else mp[it] = M.pts[s];
         const T *q = rd_pre + 3 * (P.off + i);
         qv[it][0] = q[0]; qv[it][1] = q[1]; qv[it][2] = q[2];
-        if constexpr (GEN)
+        if constexpr (GEN) {
             if (use_nrm) { const T *n = rd_nrm + 3 * (P.off + i); qn[it][0] = n[0]; qn[it][1] = n[1]; qn[it][2] = n[2]; }
+            if (gd) gv[it] = M.val[s - (keep[it] ? M.first : 0)];       // (s = 0 for a pair not kept: a valid index, unused)
+        }
     }
 #pragma unroll
     for (int it = 0; it < kReduceItems; it++) {
@@ -177,8 +192,14 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
                 if (((ax * bx + ay * by) + az * bz) < normal_cos) continue;
             }
             double wgt = 1.0;
-            if constexpr (GEN)
-                if (robust) { const T wr = robust_weight<T>(rb, dds[it], rs2); if (wr == (T)0) continue; wgt = (double)wr; }
+            if constexpr (GEN) {
+                // the Robust and the GenericDescriptor weight multiply in T (the other filters' weights are 0 / 1)
+                T w = (T)1;
+                if (robust) w = robust_weight<T>(rb, dds[it], rs2);
+                if (gd) w = w * gd_weight<T>(gd_mode, gd_thr, gv[it], gmax);
+                if (w == (T)0) continue;
+                wgt = (double)w;
+            }
             T px, py, pz;
             apply_T<T>(tcur_of<T>(P), qv[it][0], qv[it][1], qv[it][2], px, py, pz);
             if (MIN == 0)
@@ -325,6 +346,8 @@ __global__ __launch_bounds__(256) void k_solve_update(ProblemDev *__restrict__ p
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
+    P.gd_last = P.gd_key;            // (GenericDescriptor soft maximum: this iteration's, kept for the covariance; the next starts from 0)
+    P.gd_key = 0;
     int status = PGICP_ST_OK;
     if (P.n_finite == 0 || !(sys[28] > 0.0)) status = PGICP_ST_NO_MATCH;
     if (status == PGICP_ST_OK) {
@@ -518,13 +541,15 @@ void launch_compact_active(hipStream_t st, const ProblemDev *probs, int P, int *
 // Censi covariance sums (SURVEY.md A.8) over the last iteration's kept pairs:
 // 21 terms of H (upper) + 21 terms of G (upper); the host inverts H.
 // ---------------------------------------------------------------------------
-template <typename T>
+// GD: a GenericDescriptorOutlierFilter is in the chain (false: the chain's kernel as it was without it)
+template <typename T, bool GD>
 __global__ __launch_bounds__(kReduceBlock) void k_cov_reduce(const ProblemDev *__restrict__ probs,
                                                               const MapDev<T> *__restrict__ maps,
                                                               const T *__restrict__ rd_pre, const T *__restrict__ rd_nrm,
                                                               const int *__restrict__ slot,
                                                               const T *__restrict__ d2, double *__restrict__ partials,
-                                                              int max_blocks, T normal_cos, RobustDev<T> rb, const int *__restrict__ scan_pos)
+                                                              int max_blocks, T normal_cos, RobustDev<T> rb, const int *__restrict__ scan_pos,
+                                                              int gd_mode, T gd_thr)
 {
     // (tree positions -> pairs as in k_p2plane_reduce)
     const ProblemDev &P = probs[blockIdx.y];
@@ -552,7 +577,15 @@ __global__ __launch_bounds__(kReduceBlock) void k_cov_reduce(const ProblemDev *_
         const T dd = d2[poff + e];
         const int s = slot[poff + e];
         if (s < 0 || !(dd <= limit)) continue;
-        if (rb.fct != 0 && robust_weight<T>(rb, dd, (T)P.robust_s2) == (T)0) continue;      // (not an error element)
+        if constexpr (GD) {
+            // the pair's Robust x GenericDescriptor weight in T, as k_p2plane_reduce forms it (the GenericDescriptor soft maximum:
+            // the last iteration's); a pair of weight 0 is not an error element
+            T w = rb.fct != 0 ? robust_weight<T>(rb, dd, (T)P.robust_s2) : (T)1;
+            w = w * gd_weight<T>(gd_mode, gd_thr, M.val[s - M.first], Bits<T>::val((typename Bits<T>::U)P.gd_last));
+            if (w == (T)0) continue;
+        } else {
+            if (rb.fct != 0 && robust_weight<T>(rb, dd, (T)P.robust_s2) == (T)0) continue;      // (not an error element)
+        }
         const int i = knn == 1 ? e : e / knn;
         const T *q = rd_pre + 3 * (P.off + i);
         T pxt, pyt, pzt;
@@ -618,6 +651,53 @@ __global__ __launch_bounds__(64) void k_robust_open(ProblemDev *__restrict__ pro
     P.limit = __longlong_as_double(0x7FF0000000000000LL);
     P.rlimit = P.limit;
 }
+// [EXT] GenericDescriptorOutlierFilter, soft mode.  k_gd_open: as k_robust_open (the maximum covers every pair with a neighbour:
+// the lazy path must resolve every queued query) and the second selection must run whatever the lazy path refined -- it restores
+// the iteration's threshold.  k_gd_max: the maximum value over the pairs with a neighbour -> ProblemDev::gd_key (values >= 0:
+// their bits order as the values do; -0 counts as 0).
+__global__ __launch_bounds__(64) void k_gd_open(ProblemDev *__restrict__ probs, const int *__restrict__ active, int n_active)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_active) return;
+    ProblemDev &P = probs[active[a]];
+    if (P.done) return;
+    P.limit = __longlong_as_double(0x7FF0000000000000LL);
+    P.rlimit = P.limit;
+    P.n_refined = 1;
+}
+constexpr int kGdMaxItems = 16;       // pairs per thread of k_gd_max
+template <typename T>
+__global__ __launch_bounds__(256) void k_gd_max(ProblemDev *__restrict__ probs, const MapDev<T> *__restrict__ maps,
+                                                const int *__restrict__ slot, const int *__restrict__ active)
+{
+    using U = typename Bits<T>::U;
+    ProblemDev &P = probs[active[blockIdx.y]];
+    if (P.done) return;
+    const int np = pairs_n(P);
+    const int base = blockIdx.x * (256 * kGdMaxItems);
+    if (base >= np) return;
+    const MapDev<T> M = maps[P.map];
+    const long long poff = pairs_off(P);
+    int ss[kGdMaxItems];
+#pragma unroll
+    for (int it = 0; it < kGdMaxItems; it++) {
+        const int e = base + it * 256 + threadIdx.x;
+        ss[it] = e < np ? slot[poff + e] : -1;
+    }
+    U k = 0;
+#pragma unroll
+    for (int it = 0; it < kGdMaxItems; it++)
+        if (ss[it] >= 0) { const T v = M.val[ss[it] - M.first]; if (v > (T)0) k = max(k, Bits<T>::key(v)); }
+    __shared__ U red[4];
+    for (int o = 32; o > 0; o >>= 1) { const U t = __shfl_xor(k, o); k = t > k ? t : k; }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) k = red[w] > k ? red[w] : k;
+        if (k) atomicMax(&P.gd_key, (unsigned long long)k);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_robust_absdev(const ProblemDev *__restrict__ probs, const T *__restrict__ d2, T *__restrict__ dev,
                                                        const int *__restrict__ active)
@@ -668,3 +748,17 @@ __global__ __launch_bounds__(256) void k_robust_weights_raw(const T *__restrict_
     w[i] = v == __builtin_huge_val() ? (T)0 : robust_weight<T>(rb, v, s2);      // (no neighbour: never an error element)
 }
 
+
+// pgicp_map_set_values: the caller's values (original point order, values[i * stride]) into the map's slot order; flags[0]: a
+// non-finite value was met, flags[1]: a negative one
+template <typename T>
+__global__ __launch_bounds__(256) void k_map_values(const typename Vec4<T>::type *__restrict__ pts, int first, int m,
+                                                    const T *__restrict__ values, int stride, T *__restrict__ out, int *__restrict__ flags)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= m) return;
+    const T v = values[(long long)Bits<T>::unpack_idx(pts[first + s].w) * stride];
+    out[s] = v;
+    if (!isfinite(v)) atomicOr(flags, 1);
+    else if (v < (T)0) atomicOr(flags + 1, 1);
+}

@@ -160,6 +160,8 @@ __device__ __forceinline__ void sel_store(ProblemDev &P, const ChainDev<T> &ch, 
         if (P.vt_ratio < 0.0) P.limit = -1.0;
         P.rlimit = __longlong_as_double(0x7FF0000000000000LL);
     }
+    // GenericDescriptor soft mode: its maximum is over every pair -- the next matcher pass must again find every pair exactly
+    if (ch.gd_mode == PGICP_DESC_FILTER_SOFT) P.rlimit = __longlong_as_double(0x7FF0000000000000LL);
     P.qraw = (double)limit;
     if (!second) P.qraw1 = (double)limit;
     if (P.iters < 4) P.qrec[second ? 1 : 0][P.iters] = (double)limit;

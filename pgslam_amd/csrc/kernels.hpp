@@ -74,6 +74,11 @@ void launch_cov(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, 
 void launch_sum_partials(hipStream_t st, const double *partials, int max_blocks, int nt, const ProblemDev *probs,
                          int nb_uniform, double *out, int P);
 void launch_robust_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
+void launch_gd_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
+template <typename T>
+void launch_gd_max(hipStream_t st, ProblemDev *probs, const MapDev<T> *maps, const int *slot, int n_active, int max_pairs, const int *active);
+template <typename T>
+void launch_map_values(hipStream_t st, const typename Vec4<T>::type *pts, int first, int m, const T *values, int stride, T *out, int *flags);
 template <typename T>
 void launch_robust_raw(hipStream_t st, const T *d2, int n, const RobustDev<T> &rb, T *dev, T *stat, T *w);
 template <typename T>

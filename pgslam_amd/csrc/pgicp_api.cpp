@@ -447,6 +447,29 @@ int pgicp_last_var_trim_ratio(pgicp_ctx *c, int problem, double *ratio)
     return PGICP_OK;
 }
 
+int pgicp_set_descriptor_filter(pgicp_ctx *c, int mode, double threshold)
+{
+    if (!c) return PGICP_ERR_ARG;
+    if (mode < PGICP_DESC_FILTER_OFF || mode > PGICP_DESC_FILTER_SOFT)
+        return fail(c, PGICP_ERR_ARG, "GenericDescriptorOutlierFilter: unknown mode " + std::to_string(mode));
+    if ((mode == PGICP_DESC_FILTER_LARGER || mode == PGICP_DESC_FILTER_SMALLER) && !std::isfinite(threshold))
+        return fail(c, PGICP_ERR_ARG, "GenericDescriptorOutlierFilter: the threshold must be finite");
+    c->gd_mode = mode;
+    c->gd_thr = mode == PGICP_DESC_FILTER_LARGER || mode == PGICP_DESC_FILTER_SMALLER ? threshold : 0.0;
+    return PGICP_OK;
+}
+int pgicp_get_descriptor_filter(const pgicp_ctx *c, int *mode, double *threshold)
+{
+    if (!c) return PGICP_ERR_ARG;
+    if (mode) *mode = c->gd_mode;
+    if (threshold) *threshold = c->gd_thr;
+    return PGICP_OK;
+}
+int pgicp_map_set_values_f32(pgicp_ctx *c, int map_id, const float *v, int stride, int mem)
+{ return map_set_values<float>(c, map_id, v, stride, mem); }
+int pgicp_map_set_values_f64(pgicp_ctx *c, int map_id, const double *v, int stride, int mem)
+{ return map_set_values<double>(c, map_id, v, stride, mem); }
+
 int pgicp_error_stats_f32(pgicp_ctx *c, int map_id, const float *rd, int stride, int n, int mem, const int32_t *ids,
                           const float *w, double *ratio, double *residual, double sys[30])
 { return error_stats<float>(c, map_id, rd, stride, n, mem, ids, w, ratio, residual, sys); }

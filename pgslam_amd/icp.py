@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "pgicp_debug_reading_order", "pgicp_partial_chain_seeded_f32", "pgicp_partial_chain_seeded_f64",
     "pgicp_sampling_surface_normal_f32", "pgicp_sampling_surface_normal_f64",
     "pgicp_set_var_trim", "pgicp_get_var_trim", "pgicp_last_var_trim_ratio",
+    "pgicp_set_descriptor_filter", "pgicp_get_descriptor_filter", "pgicp_map_set_values_f32", "pgicp_map_set_values_f64",
     "pgicp_voxel_grid_f32", "pgicp_voxel_grid_f64",
 ]
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
@@ -430,6 +431,56 @@ class Context:
         r = C.c_double(0)
         self._check(self.lib.pgicp_last_var_trim_ratio(self.h, C.c_int(problem), C.byref(r)))
         return r.value
+
+    _DESC_MODES = {None: 0, "larger": 1, "smaller": 2, "soft": 3}
+
+    def set_descriptor_filter(self, mode=None, threshold=None):
+        """[EXT] GenericDescriptorOutlierFilter (pgicp_set_descriptor_filter): mode None (off), "larger" / "smaller" (hard,
+        useLargerThan 1 / 0: weight 1 where the map point's value is strictly above / below `threshold`) or "soft" (weight =
+        value / the largest value over the pairs).  The values are the map's (set_map_values)."""
+        if mode not in self._DESC_MODES:
+            raise ValueError(f"set_descriptor_filter: unknown mode {mode!r}")
+        if mode in ("larger", "smaller") and threshold is None:
+            raise ValueError("set_descriptor_filter: a hard mode needs a threshold")
+        self._check(self.lib.pgicp_set_descriptor_filter(self.h, C.c_int(self._DESC_MODES[mode]),
+                                                          C.c_double(0.0 if threshold is None else float(threshold))))
+
+    def get_descriptor_filter(self):
+        """(mode, threshold) as set_descriptor_filter takes them; (None, 0.0) when the filter is off."""
+        m, t = C.c_int(0), C.c_double(0)
+        self._check(self.lib.pgicp_get_descriptor_filter(self.h, C.byref(m), C.byref(t)))
+        return {v: k for k, v in self._DESC_MODES.items()}[m.value], t.value
+
+    def set_map_values(self, map_id, values, dtype=None):
+        """One value per point of map `map_id`, in the order its cloud was given (pgicp_map_set_values); None drops them.
+        values: a 1-D numpy array (any stride -- a row of a descriptor matrix) or a 1-D torch CUDA tensor.  dtype: the map's
+        precision (default: the values' own float32 / float64)."""
+        if values is None:
+            fn = self.lib.pgicp_map_set_values_f64 if map_id & 0x40000000 else self.lib.pgicp_map_set_values_f32
+            self._check(fn(self.h, C.c_int(map_id), None, C.c_int(1), C.c_int(HOST)))
+            return
+        if _is_torch(values) and values.is_cuda:
+            if values.dim() != 1 or values.stride(0) < 1:
+                raise ValueError("set_map_values: values must be a 1-D tensor with a positive stride")
+            dt = np.dtype(str(values.dtype).replace("torch.", ""))
+            if dt not in (np.float32, np.float64):
+                raise TypeError("set_map_values: a float32 or float64 tensor is needed")
+            if dtype is not None and dt != np.dtype(dtype):
+                raise TypeError("set_map_values: the tensor's dtype must be the map's")
+            keep, ptr, stride, mem = values, values.data_ptr(), values.stride(0), DEVICE
+        else:
+            v = np.asarray(values.cpu() if _is_torch(values) else values)
+            if dtype is not None:
+                v = v.astype(dtype, copy=False)
+            if v.dtype not in (np.float32, np.float64):
+                v = v.astype(np.float32)
+            if v.ndim != 1 or v.strides[0] <= 0 or v.strides[0] % v.itemsize != 0:
+                raise ValueError("set_map_values: values must be 1-D with a positive stride of whole elements")
+            dt = v.dtype
+            keep, ptr, stride, mem = v, v.ctypes.data, v.strides[0] // v.itemsize, HOST
+        fn = getattr(self.lib, "pgicp_map_set_values" + self._sfx(dt))
+        self._check(fn(self.h, C.c_int(map_id), C.c_void_p(ptr), C.c_int(stride), C.c_int(mem)))
+        del keep
 
     @property
     def stream(self):
