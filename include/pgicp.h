@@ -21,6 +21,12 @@
  *     converts from the column-major PM::Matrix.)
  *   - A context is thread-compatible (one thread at a time); different contexts
  *     are fully concurrent, each owns its HIP stream (SURVEY.md §8(b) threading).
+ *   - A call's outputs are a function of its arguments, the context's parameters
+ *     and the maps it names; with PGICP_SUM_ORDER_SORTED also of those maps'
+ *     grids; never of earlier calls on the context or of other contexts.  What a
+ *     context carries from call to call (selection hints, search caps, pooled
+ *     blocks, reused buffers, captured graphs) changes how a call runs, not what
+ *     it returns (tests/test_gpu_history.py).
  *   - There is NO CPU fallback: without a usable gfx950 device
  *     pgicp_ctx_create() fails with PGICP_ERR_NO_DEVICE.
  */

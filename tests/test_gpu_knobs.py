@@ -30,6 +30,8 @@ SETTINGS = [
     {"PGICP_SEL_BAND": "1", "PGICP_SEL_SMALL_N": "0"},
     # ... without the next iteration's matcher pass enqueued ahead of the convergence flag, small results copied directly
     {"PGICP_SPECULATE": "0", "PGICP_D2H_DIRECT": "1", "PGICP_PROBE_CAP_SCALE": "0.5"},
+    # without the selection hints a call inherits from the call before it (every first selection unhinted)
+    {"PGICP_SEL_HINTS": "0"},
 ]
 
 
