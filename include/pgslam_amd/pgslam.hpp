@@ -631,6 +631,11 @@ public:
     //! the descriptor row the candidates' maps must carry ("" when the chain has no GenericDescriptorOutlierFilter)
     std::string DescriptorName() const { return chain_.descriptorName(); }
     size_t device_batches() const { return device_batches_; }
+    //! Opt-in (default off: Run refuses a reading that carries `simpleSensorNoise`): Run / RunOnDevice arm the batch with every
+    //! such reading's row (pgicp_arm_reading_noise), and the edge's `overlap` -- what CheckIcpResult compares -- is getOverlap()'s
+    //! sensor-noise branch for those pairs (pgicp_last_noise_overlap), as PairLoopCloser::ProcessCandidate gives it
+    void SetSensorNoiseOnDevice(bool on) { noise_on_device_ = on; }
+    bool SensorNoiseOnDevice() const { return noise_on_device_; }
     void SetIcpConfigFromString(const std::string &yaml) { std::istringstream iss(yaml); chain_.loadFromYaml(iss); yaml_ = yaml; }
     void Add(const Candidate &c) { queue_.push_back(c); }
     void Clear() { queue_.clear(); }
@@ -659,7 +664,7 @@ public:
         std::vector<int> maps(P, -1), xs(P), ns(P), ms(P);
         std::vector<const T *> xyz(P), nrm(P);
         for (int k = 0; k < P; k++)
-            if (queue_[mine[k]].reading && chain_.sensorNoiseApplies(*queue_[mine[k]].reading))
+            if (!noise_on_device_ && queue_[mine[k]].reading && chain_.sensorNoiseApplies(*queue_[mine[k]].reading))
                 throw std::runtime_error("LoopClosureBatch: a reading carries simpleSensorNoise (getOverlap's sensor-noise branch): process the pair with PairLoopCloser");
         bool on_device = DeviceCandidateEquivalent();
         for (int k = 0; k < P && on_device; k++) on_device = queue_[mine[k]].reading_dev && queue_[mine[k]].reference_dev && queue_[mine[k]].reference_dev->hasNormals();
@@ -682,15 +687,12 @@ public:
             nrm[k] = ref.normalsPtr(); ns[k] = ref.normalsStride();
             ms[k] = (int)ref.getNbPoints();
         }
-        // every candidate's reference is indexed in one call (ICP::operator() builds it inside, LoopCloser.hpp:98)
+        // every candidate's reference is indexed in one call (ICP::operator() builds it inside, LoopCloser.hpp:98); whatever
+        // throws below, the maps made so far go back to the pool
+        MapGuard guard{ctx, maps};
         PM::check(ctx, pgslam_amd::Abi<T>::map_create_batch(ctx, P, xyz.data(), xs.data(), nrm.data(), ns.data(), ms.data(), 1, maps.data()));
-        // a GenericDescriptorOutlierFilter's row of every reference goes with its map (throws when one lacks it: the maps go back)
-        try {
-            for (int k = 0; k < P; k++) chain_.setMapValues(reference_of(k), maps[k]);
-        } catch (...) {
-            for (int k = 0; k < P; k++) pgicp_map_destroy(ctx, maps[k]);
-            throw;
-        }
+        // a GenericDescriptorOutlierFilter's row of every reference goes with its map (throws when one lacks it)
+        for (int k = 0; k < P; k++) chain_.setMapValues(reference_of(k), maps[k]);
         // a SurfaceNormalOutlierFilter acts when the readings carry normals (without them its weights are ones):
         // all of the batch's readings or none -- one device chain per call
         int with_nrm = 0;
@@ -698,11 +700,22 @@ public:
         if (with_nrm != 0 && with_nrm != P)
             throw std::runtime_error("LoopClosureBatch: a SurfaceNormalOutlierFilter is configured and only some readings carry normals");
         // getOverlap() of a reading that carries `simpleSensorNoise` is computed from the ICP's LAST error elements; this call's
-        // fused residual pass replaces them: such a candidate goes through PairLoopCloser::ProcessCandidate (the caller's choice --
-        // LoopCloserMT does) instead of getting another overlap silently
+        // fused residual pass replaces them.  By default such a candidate is refused -- it goes through
+        // PairLoopCloser::ProcessCandidate (the caller's choice; LoopCloserMT does) instead of getting another overlap silently;
+        // with SetSensorNoiseOnDevice(true) the call is armed with the readings' rows and the device forms the overlap between
+        // the last iteration and the residual pass (pgicp_noise.h)
+        std::vector<const T *> noise_rows(P, nullptr);
+        std::vector<int> noise_strides(P, 1), noise_n(P, 0);
+        bool noisy = false;
         for (int k = 0; k < P; k++)
-            if (chain_.sensorNoiseApplies(reading_of(k)))
-                throw std::runtime_error("LoopClosureBatch: a reading carries simpleSensorNoise (getOverlap's sensor-noise branch): process the pair with PairLoopCloser");
+            if (chain_.sensorNoiseApplies(reading_of(k))) {
+                if (!noise_on_device_)
+                    throw std::runtime_error("LoopClosureBatch: a reading carries simpleSensorNoise (getOverlap's sensor-noise branch): process the pair with PairLoopCloser");
+                const DP &rd = reading_of(k);
+                noise_rows[k] = rd.descriptors.data() + rd.getDescriptorStartingRow("simpleSensorNoise");
+                noise_strides[k] = (int)rd.descriptors.rows(); noise_n[k] = (int)rd.getNbPoints();
+                noisy = true;
+            }
         chain_.pushParams(with_nrm == P && P > 0 && chain_.hasNormalFilter());
         for (int k = 0; k < P; k++) {
             const Candidate &c = queue_[mine[k]];
@@ -718,9 +731,11 @@ public:
         // ICP::operator() of every pair (LoopCloser.hpp:98) and ComputeResidualError (LoopCloser.hpp:343-365) of every result
         // in one device call: the residual pass starts from the last iteration's correspondences
         std::vector<double> residual(P, 1.0 / 0.0);
+        if (noisy) PM::check(ctx, pgslam_amd::Abi<T>::arm_noise(ctx, P, noise_rows.data(), noise_strides.data(), noise_n.data()));
         const int rc = sizeof(T) == 4 ? pgicp_align_residual_batch_f32(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr)
                                       : pgicp_align_residual_batch_f64(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr);
         if (rc != PGICP_OK && rc != PGICP_ERR_NO_MATCH && rc != PGICP_ERR_NAN && rc != PGICP_ERR_BOUND) PM::check(ctx, rc);
+        TakeNoiseOverlap(ctx, noise_rows, st);
         for (int k = 0; k < P; k++) {
             const Candidate &c = queue_[mine[k]];
             pgicp_edge &e = edges[k];
@@ -731,7 +746,6 @@ public:
             std::memcpy(e.cov, st[k].cov, sizeof e.cov);
             e.residual = residual[k];
             e.accepted = pgicp_check_icp_result(&st[k], residual[k], (double)overlap_threshold, (double)residual_threshold);
-            pgicp_map_destroy(ctx, maps[k]);
         }
         return edges;
     }
@@ -752,6 +766,11 @@ public:
     }
 
 private:
+    //! the maps of one Run go back to the pool when it leaves, by return or by exception
+    struct MapGuard {
+        pgicp_ctx *ctx; std::vector<int> &ids;
+        ~MapGuard() { for (int &m : ids) if (m >= 0) { pgicp_map_destroy(ctx, m); m = -1; } }
+    };
     static int64_t CostOf(const Candidate &c)
     {
         return (int64_t)(c.reading ? c.reading->getNbPoints() : c.reading_dev ? (size_t)c.reading_dev->n : 0) +
@@ -772,10 +791,7 @@ private:
             xyz[k] = ref.xyz; xs[k] = ref.xs; nrm[k] = ref.nrm; ns[k] = ref.ns; ms[k] = ref.n;
         }
         // whatever throws below (a partially failed map_create_batch, pushParams, PM::check): the maps made so far go back to the pool
-        struct MapGuard {
-            pgicp_ctx *ctx; std::vector<int> &ids;
-            ~MapGuard() { for (int &m : ids) if (m >= 0) { pgicp_map_destroy(ctx, m); m = -1; } }
-        } guard{ctx, maps};
+        MapGuard guard{ctx, maps};
         PM::check(ctx, sizeof(T) == 4 ? pgicp_map_create_batch_f32(ctx, P, (const float *const *)xyz.data(), xs.data(), (const float *const *)nrm.data(), ns.data(), ms.data(), PGICP_DEVICE, 1, maps.data())
                                       : pgicp_map_create_batch_f64(ctx, P, (const double *const *)xyz.data(), xs.data(), (const double *const *)nrm.data(), ns.data(), ms.data(), PGICP_DEVICE, 1, maps.data()));
         chain_.pushParams();
@@ -787,9 +803,25 @@ private:
         }
         std::vector<double> Tout((size_t)16 * P), residual(P, 1.0 / 0.0);
         std::vector<pgicp_stats> st(P);
+        // (SetSensorNoiseOnDevice: the rows are the host clouds' -- a keyframe's cloud is not touched once it is queued.  A
+        // candidate without a host cloud has no descriptors at all, so no sensor-noise branch: its overlap is the ratio.)
+        std::vector<const T *> noise_rows(P, nullptr);
+        std::vector<int> noise_strides(P, 1), noise_n(P, 0);
+        bool noisy = false;
+        for (int k = 0; k < P && noise_on_device_; k++) {
+            const Candidate &c = queue_[mine[k]];
+            if (!c.reading || !chain_.sensorNoiseApplies(*c.reading)) continue;
+            if ((int)c.reading->getNbPoints() != c.reading_dev->n)
+                throw std::runtime_error("LoopClosureBatch: a reading's simpleSensorNoise row and its device copy differ in size");
+            noise_rows[k] = c.reading->descriptors.data() + c.reading->getDescriptorStartingRow("simpleSensorNoise");
+            noise_strides[k] = (int)c.reading->descriptors.rows(); noise_n[k] = c.reading_dev->n;
+            noisy = true;
+        }
+        if (noisy) PM::check(ctx, pgslam_amd::Abi<T>::arm_noise(ctx, P, noise_rows.data(), noise_strides.data(), noise_n.data()));
         const int rc = sizeof(T) == 4 ? pgicp_align_residual_batch_f32(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr)
                                       : pgicp_align_residual_batch_f64(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr);
         if (rc != PGICP_OK && rc != PGICP_ERR_NO_MATCH && rc != PGICP_ERR_NAN && rc != PGICP_ERR_BOUND) PM::check(ctx, rc);
+        TakeNoiseOverlap(ctx, noise_rows, st);
         for (int k = 0; k < P; k++) {
             const Candidate &c = queue_[mine[k]];
             pgicp_edge &e = edges[k];
@@ -804,10 +836,22 @@ private:
         device_batches_++;
         return edges;
     }
+    //! after an armed batch: the sensor-noise overlap replaces weightedPointUsedRatio in the stats of every pair that has one
+    //! (rounded to T, as getOverlap() returns it)
+    static void TakeNoiseOverlap(pgicp_ctx *ctx, const std::vector<const T *> &rows, std::vector<pgicp_stats> &st)
+    {
+        for (size_t k = 0; k < rows.size(); k++) {
+            if (!rows[k] || st[k].status != PGICP_OK) continue;
+            double ov = 0.0;
+            PM::check(ctx, pgicp_last_noise_overlap(ctx, (int)k, &ov, nullptr));
+            st[k].overlap = (double)(T)ov;
+        }
+    }
     typename PM::ICP chain_;
     std::string yaml_;
     std::vector<Candidate> queue_;
     size_t device_batches_ = 0;
+    bool noise_on_device_ = false;
 };
 
 }  // namespace pgslam

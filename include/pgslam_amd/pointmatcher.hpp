@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../pgicp.h"
+#include "../pgicp_noise.h"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -158,7 +159,7 @@ template <> struct Abi<float> {
     static int local_map_dev(pgicp_ctx *c, int k, const float *const *x, const float *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, float *ox, int os, float *on, int ons) { return pgicp_build_local_map_f32(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_DEVICE); }
     static int map_create_dev(pgicp_ctx *c, const float *x, int xs, const float *n, int ns, int m, int center, int *id) { return pgicp_map_create_f32(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
     static int transform_dev(pgicp_ctx *c, const double *T16, const float *in, int is, float *out, int os, int n, int rotate_only) { return pgicp_transform_f32(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
-    static int last_matches(pgicp_ctx *c, int problem, int32_t *ids, float *d2) { return pgicp_debug_last_matches_f32(c, problem, ids, d2); }
+    static int arm_noise(pgicp_ctx *c, int k, const float *const *rows, const int *strides, const int *n) { return pgicp_arm_reading_noise_f32(c, k, rows, strides, n, PGICP_HOST); }
     static int set_values(pgicp_ctx *c, int id, const float *v, int stride) { return pgicp_map_set_values_f32(c, id, v, stride, PGICP_HOST); }
 };
 template <> struct Abi<double> {
@@ -193,7 +194,7 @@ template <> struct Abi<double> {
     static int local_map_dev(pgicp_ctx *c, int k, const double *const *x, const double *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, double *ox, int os, double *on, int ons) { return pgicp_build_local_map_f64(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_DEVICE); }
     static int map_create_dev(pgicp_ctx *c, const double *x, int xs, const double *n, int ns, int m, int center, int *id) { return pgicp_map_create_f64(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
     static int transform_dev(pgicp_ctx *c, const double *T16, const double *in, int is, double *out, int os, int n, int rotate_only) { return pgicp_transform_f64(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
-    static int last_matches(pgicp_ctx *c, int problem, int32_t *ids, double *d2) { return pgicp_debug_last_matches_f64(c, problem, ids, d2); }
+    static int arm_noise(pgicp_ctx *c, int k, const double *const *rows, const int *strides, const int *n) { return pgicp_arm_reading_noise_f64(c, k, rows, strides, n, PGICP_HOST); }
     static int set_values(pgicp_ctx *c, int id, const double *v, int stride) { return pgicp_map_set_values_f64(c, id, v, stride, PGICP_HOST); }
 };
 
@@ -1806,39 +1807,27 @@ struct PointMatcher {
             return errorMinimizer && reading.descriptorExists("simpleSensorNoise") && (errorMinimizer->pointToPoint || reading.descriptorExists("normals"));
         }
     protected:
-        //! getOverlap()'s sensor-noise branch over the last error elements of problem `problem` of the align call that has just
-        //! returned: the pairs the outlier filters kept in its last iteration (exact ids and distances: pgicp_debug_last_matches),
-        //! dists = |reading - reference| in T, mean over the kept pairs, the share below mean + noise(point).  Kept = a neighbour and
-        //! a squared distance within the last threshold (Trimmed / Median / MaxDist filters: what pgicp_stats.trim_limit is);
-        //! a chain whose weights are not that (Robust, SurfaceNormal outlier filters) is refused, not approximated.
-        T sensorNoiseOverlap(const DataPoints &reading, int problem, const pgicp_stats &st) const
+        //! getOverlap()'s sensor-noise branch (pgicp_noise.h): the reading's `simpleSensorNoise` row is handed to the NEXT align call
+        //! of the context (pgicp_arm_reading_noise: copied inside the call, so the host cloud is read here, BEFORE the align is
+        //! started, and never while it runs); the device then forms the share of the last error elements below mean + noise(point)
+        //! with the chain's own combined weights -- Robust, SurfaceNormal and GenericDescriptor filters included.  Returns whether
+        //! the branch applies (and the call is armed).
+        bool armSensorNoise(const DataPoints &reading) const
         {
-            for (auto &f : outlierFilters)
-                if (std::dynamic_pointer_cast<RobustOutlierFilter>(f) || std::dynamic_pointer_cast<SurfaceNormalOutlierFilter>(f) ||
-                    std::dynamic_pointer_cast<GenericDescriptorOutlierFilter>(f))
-                    throw std::runtime_error("getOverlap: the sensor-noise overlap (a reading with simpleSensorNoise) is not supported with a Robust / SurfaceNormal / GenericDescriptor outlier filter");
-            const int n = (int)reading.getNbPoints(), knn = std::max(1, matcher ? matcher->knn : 1);
-            std::vector<int32_t> ids((size_t)n * knn);
-            std::vector<T> d2((size_t)n * knn);
-            check(ctx, A::last_matches(ctx, problem, ids.data(), d2.data()));
-            const int rn = reading.getDescriptorStartingRow("simpleSensorNoise");
-            const T limit = (T)st.trim_limit;
+            if (!sensorNoiseApplies(reading)) return false;
+            const T *row = reading.descriptors.data() + reading.getDescriptorStartingRow("simpleSensorNoise");
+            const int stride = (int)reading.descriptors.rows(), n = (int)reading.getNbPoints();
+            check(ctx, A::arm_noise(ctx, 1, &row, &stride, &n));
+            return true;
+        }
+        //! ... and the result for problem `problem` of the armed align call that has just returned
+        T sensorNoiseOverlap(int problem) const
+        {
+            double overlap = 0.0;
             int nb = 0;
-            T sum = 0;
-            for (int k = 0; k < knn; k++)
-                for (int i = 0; i < n; i++) {
-                    const size_t e = (size_t)i * knn + k;
-                    if (ids[e] >= 0 && d2[e] <= limit) { sum += std::sqrt(d2[e]); nb++; }
-                }
+            check(ctx, pgicp_last_noise_overlap(ctx, problem, &overlap, &nb));
             if (nb == 0) throw ConvergenceError("PointToPlaneErrorMinimizer: no element to minimize");
-            const T mean = sum / (T)nb;
-            int count = 0;
-            for (int k = 0; k < knn; k++)
-                for (int i = 0; i < n; i++) {
-                    const size_t e = (size_t)i * knn + k;
-                    if (ids[e] >= 0 && d2[e] <= limit && std::sqrt(d2[e]) < mean + reading.descriptors(rn, i)) count++;
-                }
-            return (T)count / (T)nb;
+            return (T)overlap;
         }
     public:
         //! A reading whose filtered copy is on its way to (or already in) device memory: pgicp_upload_* started the
@@ -1906,11 +1895,17 @@ struct PointMatcher {
             pgslam_amd::to_row_major16(T_init, Ti);
             pgicp_stats st;
             pushParams();
+            // a host copy whose gaps may still be closing (r.n >= 0) has no row that may be read: such a reading cannot take the
+            // sensor-noise branch and is refused (only the labels are looked at, which the compaction leaves alone); the facade
+            // does not defer the compaction of a cloud that carries `simpleSensorNoise`, GraphLocalizer::PreProcessOn
+            if (r.n >= 0 && r.filtered && sensorNoiseApplies(*r.filtered))
+                throw std::logic_error("ICP: a deferred device reading carries simpleSensorNoise; finish its host compaction and pass it with n = -1");
+            const bool noisy = r.n < 0 && r.filtered && armSensorNoise(*r.filtered);
             // (the call makes its stream wait, on the device, for the upload; the host does not)
             const int rc = A::align_dev(ctx, matcher->mapId, r.dev, r.xyzStride(), r.points(), Ti, To, &st);
             storeStats(st);
             check(ctx, rc);
-            if (r.filtered && sensorNoiseApplies(*r.filtered)) errorMinimizer->lastOverlap = sensorNoiseOverlap(*r.filtered, 0, st);
+            if (noisy) errorMinimizer->lastOverlap = sensorNoiseOverlap(0);
             const TransformationParameters T_out = pgslam_amd::from_row_major16<T>(To);
             if (onAlign && (currentReference || lazyReference) && (!onAlignWanted || onAlignWanted()))
                 if (const DataPoints *ref = observedReference()) onAlign(*r.filtered, *ref, T_init, T_out, st);
@@ -1936,12 +1931,13 @@ struct PointMatcher {
             for (auto &f : outlierFilters) normalFilter = normalFilter || std::dynamic_pointer_cast<SurfaceNormalOutlierFilter>(f) != nullptr;
             const bool withNormals = normalFilter && reading.normalsPtr() != nullptr;
             pushParams(withNormals);
+            const bool noisy = armSensorNoise(reading);
             const int rc = withNormals ? A::align_nrm(ctx, matcher->mapId, reading.xyzPtr(), reading.xyzStride(), (int)reading.getNbPoints(),
                                                       reading.normalsPtr(), reading.normalsStride(), Ti, To, &st)
                                        : A::align(ctx, matcher->mapId, reading.xyzPtr(), reading.xyzStride(), (int)reading.getNbPoints(), Ti, To, &st);
             storeStats(st);
             check(ctx, rc);
-            if (sensorNoiseApplies(reading)) errorMinimizer->lastOverlap = sensorNoiseOverlap(reading, 0, st);
+            if (noisy) errorMinimizer->lastOverlap = sensorNoiseOverlap(0);
             const TransformationParameters T_out = pgslam_amd::from_row_major16<T>(To);
             if (onAlign && (currentReference || lazyReference) && (!onAlignWanted || onAlignWanted()))
                 if (const DataPoints *ref = observedReference()) onAlign(reading, *ref, T_init, T_out, st);

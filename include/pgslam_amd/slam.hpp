@@ -14,6 +14,7 @@
 // Optimizer::PmCovToGtsamCov prepares it); the prior of sigma 1e-6 on the fixed vertex is imposed as a hard
 // constraint.  The optimum is the same to solver tolerance; the iteration path is not GTSAM's.
 #pragma once
+#include <atomic>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -931,7 +932,9 @@ public:
         typename PM::ICPChainBase::DeviceReading direct;
         const T *dev = nullptr;
         // deferred form: only when the ICP will run on the device copy and nobody observes the host cloud during it
-        if (defer && device_input_stage_ && deferred_host_compaction_ && icp_sequence_.deviceReadingEquivalent() && !icp_sequence_.onAlign) {
+        // (nor for a cloud that carries `simpleSensorNoise`: getOverlap()'s sensor-noise branch hands the ICP the host cloud's row)
+        if (defer && device_input_stage_ && deferred_host_compaction_ && icp_sequence_.deviceReadingEquivalent() && !icp_sequence_.onAlign &&
+            !cloud->descriptorExists("simpleSensorNoise")) {
             int kept = 0;
             if (PM::filterOnDeviceDeferred(ctx, input_filters_, *cloud, input_T_robot_sensor, &dev, &kept, defer->dropped)) {
                 device_input_stages_++;
@@ -1379,6 +1382,9 @@ public:
     //! every edge the dispatcher has produced so far, accepted or not, in the order it was produced
     std::vector<pgicp_edge> edges() { std::lock_guard<std::mutex> l(m_); return edges_; }
     size_t device_batches() const { return device_batches_; }
+    //! forwards to LoopClosureBatch::SetSensorNoiseOnDevice: candidates whose reading carries `simpleSensorNoise` then stay in the
+    //! device batch (default off: they go one pair at a time).  Set it before vertices are queued.
+    void SetSensorNoiseOnDevice(bool on) { sensor_noise_on_device_ = on; }
 
 private:
     void Main()
@@ -1408,7 +1414,10 @@ private:
             // a reading with `simpleSensorNoise` takes getOverlap()'s sensor-noise branch, which reads the ICP's LAST error elements:
             // the batch's fused residual pass replaces them, so such candidates go one at a time (the base class's ProcessCandidate)
             bool pairwise = false;
-            for (auto &c : cands) pairwise = pairwise || (c.reading && c.reading->descriptorExists("simpleSensorNoise"));
+            // (SetSensorNoiseOnDevice: the batch arms its call with the rows instead, LoopClosureBatch::SetSensorNoiseOnDevice)
+            const bool noise_on_device = sensor_noise_on_device_;
+            batch.SetSensorNoiseOnDevice(noise_on_device);
+            for (auto &c : cands) pairwise = pairwise || (!noise_on_device && c.reading && c.reading->descriptorExists("simpleSensorNoise"));
             if (pairwise) {
                 if (!pairwise_configured_) { this->closer().SetIcpConfigFromString(yaml_); pairwise_configured_ = true; }
                 PairLoopCloser<T> &lc = this->closer();
@@ -1461,6 +1470,7 @@ private:
     std::deque<size_t> queue_;
     std::thread thread_;
     bool stop_ = false, busy_ = false, paused_ = false, pairwise_configured_ = false;
+    std::atomic<bool> sensor_noise_on_device_{false};
     size_t max_batch_ = (size_t)1 << 30;
     int batches_ = 0, largest_batch_ = 0;
     size_t device_batches_ = 0;

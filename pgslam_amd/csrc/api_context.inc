@@ -135,6 +135,23 @@ struct pgicp_ctx {
     // (ABI 6, added) GenericDescriptorOutlierFilter (pgicp_set_descriptor_filter): PGICP_DESC_FILTER_*, the hard modes' threshold
     int gd_mode = 0;
     double gd_thr = 0.0;
+    // Sensor-noise getOverlap() (include/pgicp_noise.h).  pgicp_arm_reading_noise copies the readings' noise rows into `vals`
+    // (packed, one problem after the other; off[p]: where problem p's start, -1: it has none) and the next ICP call consumes
+    // them (api_noise.inc); every buffer here is allocated by an arm call or an armed ICP call only.  last_*: what
+    // pgicp_last_noise_overlap answers with -- last_P < 0: the last ICP call was not armed.
+    struct Noise {
+        bool armed = false, bad = false;    // bad: a value was negative or not finite
+        int elem = 0;                       // sizeof(T) of the armed values
+        std::vector<long long> off;
+        std::vector<int> n;
+        DevBuf vals, off_dev, dist, out;    // off_dev: `off` on the device, then the staging kernel's flag; dist: sqrt(d2) per pair
+                                            // (-1: not kept); out: {S, nb} per problem, then the counts
+        int last_P = -1;
+        std::vector<double> last_overlap;
+        std::vector<int> last_nb;
+        std::vector<char> last_ok;
+    } noise;
+    int last_icp_P = 0;             // problems of the last ICP call: the last-call diagnostics check their `problem` against it
     int fset_next = 0;
     int up_next = 0;
     int up_seen = 0;            // upload sets whose device pointers the running call was handed (see UploadUse)

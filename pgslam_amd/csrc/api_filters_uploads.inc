@@ -178,6 +178,8 @@ template <typename T>
 int debug_last_matches(pgicp_ctx *c, int problem, int32_t *ids, T *dist2)
 {
     if (!c || problem < 0 || !ids || !dist2) return PGICP_ERR_ARG;
+    // (the record of `problem` sizes the copies below: an index past the last call's own problems would read a stale one)
+    if (problem >= c->last_icp_P) return fail(c, PGICP_ERR_ARG, "pgicp_debug_last_matches: problem " + std::to_string(problem) + " is outside the last call's " + std::to_string(c->last_icp_P));
     HIPC(c, hipSetDevice(c->device));
     State<T> &S = state<T>(c);
     ProblemDev D;

@@ -42,6 +42,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
     { const int vst = var_trim_check(c); if (vst) return vst; }
     State<T> &S = state<T>(c);
     L.P = P; L.max_n = 0; L.max_rows = 1; L.total = 0; L.table_kinds = 0;
+    c->last_icp_P = P;                          // (pgicp_debug_last_matches / _reading_order: the range of their `problem`)
     c->last_n0 = -1;                            // (this call overwrites the correspondences another context might seed from)
     L.knn = std::max(1, c->prm.knn);
     L.normals = c->prm.normal_max_angle > 0.0;
@@ -489,7 +490,9 @@ template <typename T>
 int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgicp_stats *stats, double *residual = nullptr,
                 double *res_ratio = nullptr, int *res_status = nullptr)
 {
+    const bool noisy = noise_take(c);            // (pgicp_arm_reading_noise: one-shot, consumed here whatever follows)
     if (!c || P <= 0 || !pr || !T_out) return fail(c, PGICP_ERR_ARG, "pgicp_align_batch: bad argument");
+    if (noisy) { const int nst = noise_check<T>(c, P, pr); if (nst) return nst; }
     HIPC(c, hipSetDevice(c->device));
     State<T> &S = state<T>(c);
     const pgicp_params &prm = c->prm;
@@ -567,6 +570,22 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         }
     }
     const auto ht2 = std::chrono::steady_clock::now();
+    std::vector<char> nres;                   // {S, nb} of every problem (2 P doubles), then the P counts: one copy
+    if (noisy) {
+        // getOverlap()'s sensor-noise branch over the last error elements (pgicp_noise.h): here, between the last iteration and
+        // the residual pass, which overwrites the correspondences and the threshold.  {S, nb} per problem, then the counts.
+        pgicp_ctx::Noise &N = c->noise;
+        const size_t cnt_off = sizeof(double) * 2 * (size_t)P;
+        HIPC(c, N.out.ensure(cnt_off + sizeof(int) * (size_t)P));
+        HIPC(c, N.dist.ensure(sizeof(T) * (size_t)L.total * L.knn));
+        HIPC(c, hipMemsetAsync((char *)N.out.p + cnt_off, 0, sizeof(int) * (size_t)P, c->stream));
+        launch_noise_overlap<T>(c->stream, c->probs.as<ProblemDev>(), S.d_maps.template as<MapDev<T>>(), L.normals ? S.nrm_sorted.template as<T>() : nullptr,
+                                S.slot.template as<int>(), S.d2.template as<T>(), c->order.as<int>(), N.vals.template as<T>(),
+                                N.off_dev.as<long long>(), N.dist.template as<T>(), c->partials.as<double>(), N.out.as<double>(),
+                                (int *)((char *)N.out.p + cnt_off), P, L.max_pairs(), ch);
+        nres.resize(cnt_off + sizeof(int) * (size_t)P);
+        XFER(c, d2h(c, nres.data(), N.out.p, nres.size()));
+    }
     const bool with_cov = prm.error_minimizer != PGICP_MINIMIZER_POINT_TO_POINT;      // (PointToPoint: the base class's zeros; its WithCov form: the same Censi estimate)
     if (with_cov) {
         ProfScope ps(c, PGICP_PROF_COV, L.total, P);
@@ -599,6 +618,24 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
     std::memcpy(hp.data(), c->h_down, sizeof(ProblemDev) * (size_t)P);
     hints_store(c, 0, hp);
     var_trim_record(c, hp);
+    if (noisy) {
+        pgicp_ctx::Noise &N = c->noise;
+        N.last_P = P;
+        N.last_overlap.assign(P, 0.0); N.last_nb.assign(P, 0); N.last_ok.assign(P, 0);
+        for (int p = 0; p < P; p++) {
+            // (a problem without noise, or one that failed, wrote no partials: its sums are not looked at)
+            if (N.off[p] < 0 || hp[p].status != PGICP_ST_OK) continue;
+            double kept;
+            int cnt;
+            std::memcpy(&kept, nres.data() + sizeof(double) * (2 * (size_t)p + 1), sizeof kept);
+            std::memcpy(&cnt, nres.data() + sizeof(double) * 2 * (size_t)P + sizeof(int) * (size_t)p, sizeof cnt);
+            const int nb = (int)kept;                     // (a count of pairs, exact in a double)
+            if (nb <= 0) continue;
+            N.last_ok[p] = 1;
+            N.last_nb[p] = nb;
+            N.last_overlap[p] = (double)((T)cnt / (T)nb);
+        }
+    }
     for (int p = 0; p < P && !rsys.empty(); p++) {
         const double *rs = rsys.data() + (size_t)p * kSys;
         const bool ok = hp[p].status == PGICP_ST_OK && rs[28] > 0.0;
@@ -666,7 +703,7 @@ int icp_pair(pgicp_ctx *c, const T *reading, int rd_stride, int n, const T *ref_
 {
     int id = -1;
     int st = map_create<T>(c, ref_xyz, ref_stride, ref_nrm, nrm_stride, m, mem, 1, &id);
-    if (st) return st;
+    if (st) { (void)noise_take(c); return st; }
     pgicp_problem pr;
     std::memset(&pr, 0, sizeof pr);
     pr.map_id = id; pr.reading = reading; pr.stride = rd_stride; pr.n = n; pr.mem = mem;

@@ -106,6 +106,29 @@ __device__ __forceinline__ T gd_weight(int mode, T thr, T v, T gmax)
     return gmax > (T)0 ? v / gmax : (T)0;
 }
 
+// The combined outlier weight of a pair that has a neighbour within the quantile / MaxDist limit (`keep` in k_p2plane_reduce):
+// the SurfaceNormalOutlierFilter's 0 / 1 (the step reading's normal is R (R_pre n) with R the rotation of Tc, in T like the
+// points), times the Robust weight, times the GenericDescriptor weight -- the real-valued factors multiply in T.  0: the pair is
+// no error element.  One statement for every kernel that must agree on the last error elements: k_p2plane_reduce (Tc the
+// iteration's transform) and k_noise_sum (k_noise.inc; Tc = T_prev, gmax = gd_last: what the last iteration ran with).
+template <typename T, typename S>
+__device__ __forceinline__ T pair_filter_weight(const S *Tc, bool use_nrm, const T *qn, T bx, T by, T bz, T normal_cos, bool robust,
+                                                const RobustDev<T> &rb, T dd, T rs2, bool gd, int gd_mode, T gd_thr, T gv, T gmax)
+{
+    if (use_nrm) {
+        T ax = ((T)Tc[0] * qn[0] + (T)Tc[1] * qn[1]) + (T)Tc[2] * qn[2];
+        T ay = ((T)Tc[4] * qn[0] + (T)Tc[5] * qn[1]) + (T)Tc[6] * qn[2];
+        T az = ((T)Tc[8] * qn[0] + (T)Tc[9] * qn[1]) + (T)Tc[10] * qn[2];
+        normalized3<T>(ax, ay, az);
+        normalized3<T>(bx, by, bz);
+        if (((ax * bx + ay * by) + az * bz) < normal_cos) return (T)0;
+    }
+    T w = (T)1;
+    if (robust) w = robust_weight<T>(rb, dd, rs2);
+    if (gd) w = w * gd_weight<T>(gd_mode, gd_thr, gv, gmax);
+    return w;
+}
+
 template <typename T, int MIN, bool GEN>
 __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDev *__restrict__ probs,
                                                                   const MapDev<T> *__restrict__ maps,
@@ -180,23 +203,12 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
 #pragma unroll
     for (int it = 0; it < kReduceItems; it++) {
         if (keep[it]) {
-            if (GEN && use_nrm) {
-                // SurfaceNormalOutlierFilter: the step reading's normal is R_iter (R_pre n), in T like the points
-                const auto Tc = tcur_of<T>(P);
-                T ax = ((T)Tc[0] * qn[it][0] + (T)Tc[1] * qn[it][1]) + (T)Tc[2] * qn[it][2];
-                T ay = ((T)Tc[4] * qn[it][0] + (T)Tc[5] * qn[it][1]) + (T)Tc[6] * qn[it][2];
-                T az = ((T)Tc[8] * qn[it][0] + (T)Tc[9] * qn[it][1]) + (T)Tc[10] * qn[it][2];
-                T bx = mn[it].x, by = mn[it].y, bz = mn[it].z;
-                normalized3<T>(ax, ay, az);
-                normalized3<T>(bx, by, bz);
-                if (((ax * bx + ay * by) + az * bz) < normal_cos) continue;
-            }
             double wgt = 1.0;
             if constexpr (GEN) {
-                // the Robust and the GenericDescriptor weight multiply in T (the other filters' weights are 0 / 1)
-                T w = (T)1;
-                if (robust) w = robust_weight<T>(rb, dds[it], rs2);
-                if (gd) w = w * gd_weight<T>(gd_mode, gd_thr, gv[it], gmax);
+                // SurfaceNormal x Robust x GenericDescriptor (pair_filter_weight; the quantile / MaxDist filters are `keep`)
+                const T w = pair_filter_weight<T>(tcur_of<T>(P), use_nrm, qn[it], use_nrm ? mn[it].x : (T)0, use_nrm ? mn[it].y : (T)0,
+                                                  use_nrm ? mn[it].z : (T)0, normal_cos, robust, rb, dds[it], rs2, gd, gd_mode, gd_thr,
+                                                  gd ? gv[it] : (T)0, gmax);
                 if (w == (T)0) continue;
                 wgt = (double)w;
             }

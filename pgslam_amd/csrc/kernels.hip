@@ -190,5 +190,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_ssn.inc"
 #include "k_vartrim.inc"
 #include "k_voxel.inc"
+#include "k_noise.inc"
 
 }  // namespace pgicp

@@ -73,6 +73,15 @@ void launch_cov(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, 
                 const T *d2, double *partials, double *out, int P, int max_n, const ChainDev<T> &ch);
 void launch_sum_partials(hipStream_t st, const double *partials, int max_blocks, int nt, const ProblemDev *probs,
                          int nb_uniform, double *out, int P);
+// SimpleSensorNoise descriptor and the sensor-noise getOverlap() over the last error elements (k_noise.inc, include/pgicp_noise.h)
+template <typename T>
+void launch_simple_sensor_noise(hipStream_t st, const T *xyz, int stride, int n, int sensor_type, T min_r, T angle, T cst, T gain, T *out);
+template <typename T>
+void launch_noise_stage(hipStream_t st, const T *src, int stride, int n, T *dst, int *flag);
+template <typename T>
+void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, const T *rd_nrm, const int *slot, const T *d2,
+                          const int *order, const T *noise, const long long *noise_off, T *dist, double *partials, double *out, int *count,
+                          int P, int max_pairs, const ChainDev<T> &ch);
 void launch_robust_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
 void launch_gd_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
 template <typename T>

@@ -5,6 +5,7 @@
 // steps (un-centring the result, inverting the 6x6 covariance Hessian).
 // There is no CPU compute path here: every stage runs on the GPU.
 #include "pgicp.h"
+#include "pgicp_noise.h"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -29,6 +30,7 @@ using namespace pgicp;
 // sections -- it had grown to 2 700 lines):
 #include "api_context.inc"            // context, allocation accounting, fail() / HIPC / XFER, the pinned bounce buffer, the profile
 #include "api_maps.inc"               // the device table of maps, the block pool, map_create_batch (the index build)
+#include "api_noise.inc"              // pgicp_simple_sensor_noise_*, pgicp_arm_reading_noise_*, the armed ICP call's reduction (pgicp_noise.h)
 #include "api_icp.inc"                // BatchLayout, batch_begin, one iteration, align_batch, icp_pair
 #include "api_stages.inc"             // match, partial chain, outlier weights, error statistics, transform, local maps, normals
 #include "api_filters_uploads.inc"    // pgicp_filter_cloud*, batched map ABI, last-call diagnostics, map transfer, pgicp_upload_*
@@ -158,6 +160,7 @@ void pgicp_ctx_destroy(pgicp_ctx *c)
     }
     c->ssn_work.release(); c->ssn_io.release(); c->ssn_cnt.release();
     c->vox_work.release(); c->vox_io.release(); c->vox_stat.release();
+    c->noise.vals.release(); c->noise.off_dev.release(); c->noise.dist.release(); c->noise.out.release();
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto &m : c->f32.maps) free_map<float>(nullptr, m);
     for (auto &m : c->f64.maps) free_map<double>(nullptr, m);
@@ -373,14 +376,14 @@ static pgicp_problem one_problem(int map_id, const void *rd, int stride, int n, 
 int pgicp_align_f32(pgicp_ctx *c, int map_id, const float *rd, int stride, int n, int mem, const double T_init[16],
                     double T_out[16], pgicp_stats *stats)
 {
-    if (!T_init) return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null");
+    if (!T_init) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null"); }
     pgicp_problem p = one_problem(map_id, rd, stride, n, mem, T_init);
     return align_batch<float>(c, 1, &p, T_out, stats);
 }
 int pgicp_align_f64(pgicp_ctx *c, int map_id, const double *rd, int stride, int n, int mem, const double T_init[16],
                     double T_out[16], pgicp_stats *stats)
 {
-    if (!T_init) return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null");
+    if (!T_init) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null"); }
     pgicp_problem p = one_problem(map_id, rd, stride, n, mem, T_init);
     return align_batch<double>(c, 1, &p, T_out, stats);
 }
@@ -392,13 +395,13 @@ int pgicp_align_batch_f64(pgicp_ctx *c, int P, const pgicp_problem *pr, double *
 int pgicp_align_residual_batch_f32(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgicp_stats *stats, double *residual,
                                    double *ratio, int *status)
 {
-    if (!residual) return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null");
+    if (!residual) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null"); }
     return align_batch<float>(c, P, pr, T_out, stats, residual, ratio, status);
 }
 int pgicp_align_residual_batch_f64(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgicp_stats *stats, double *residual,
                                    double *ratio, int *status)
 {
-    if (!residual) return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null");
+    if (!residual) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null"); }
     return align_batch<double>(c, P, pr, T_out, stats, residual, ratio, status);
 }
 
@@ -645,6 +648,7 @@ int pgicp_debug_dump_read(unsigned *cnt, float *d2, long long n) { return knn_du
 int pgicp_debug_reading_order(pgicp_ctx *c, int problem, int32_t *order)
 {
     if (!c || problem < 0 || !order) return PGICP_ERR_ARG;
+    if (problem >= c->last_icp_P) return fail(c, PGICP_ERR_ARG, "pgicp_debug_reading_order: problem " + std::to_string(problem) + " is outside the last call's " + std::to_string(c->last_icp_P));
     HIPC(c, hipSetDevice(c->device));
     ProblemDev D;
     HIPC(c, hipMemcpy(&D, c->probs.as<ProblemDev>() + problem, sizeof D, hipMemcpyDeviceToHost));
@@ -655,6 +659,28 @@ int pgicp_debug_reading_order(pgicp_ctx *c, int problem, int32_t *order)
 }
 int pgicp_debug_last_matches_f32(pgicp_ctx *c, int problem, int32_t *ids, float *dist2) { return debug_last_matches<float>(c, problem, ids, dist2); }
 int pgicp_debug_last_matches_f64(pgicp_ctx *c, int problem, int32_t *ids, double *dist2) { return debug_last_matches<double>(c, problem, ids, dist2); }
+
+int pgicp_simple_sensor_noise_f32(pgicp_ctx *c, const float *xyz, int stride, int n, int mem, int sensor_type, double gain, float *out, int out_mem)
+{ return simple_sensor_noise<float>(c, xyz, stride, n, mem, sensor_type, gain, out, out_mem); }
+int pgicp_simple_sensor_noise_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int mem, int sensor_type, double gain, double *out, int out_mem)
+{ return simple_sensor_noise<double>(c, xyz, stride, n, mem, sensor_type, gain, out, out_mem); }
+int pgicp_arm_reading_noise_f32(pgicp_ctx *c, int P, const float *const *noise, const int *stride, const int *n, int mem)
+{ return arm_reading_noise<float>(c, P, noise, stride, n, mem); }
+int pgicp_arm_reading_noise_f64(pgicp_ctx *c, int P, const double *const *noise, const int *stride, const int *n, int mem)
+{ return arm_reading_noise<double>(c, P, noise, stride, n, mem); }
+int pgicp_last_noise_overlap(pgicp_ctx *c, int problem, double *overlap, int *n_elements)
+{
+    if (!c) return PGICP_ERR_ARG;
+    const pgicp_ctx::Noise &N = c->noise;
+    if (N.last_P < 0) return fail(c, PGICP_ERR_ARG, "pgicp_last_noise_overlap: the last ICP call was not armed (pgicp_arm_reading_noise)");
+    if (problem < 0 || problem >= N.last_P)
+        return fail(c, PGICP_ERR_ARG, "pgicp_last_noise_overlap: problem " + std::to_string(problem) + " is outside the last ICP call's " + std::to_string(N.last_P));
+    if (!N.last_ok[(size_t)problem])
+        return fail(c, PGICP_ERR_ARG, "pgicp_last_noise_overlap: problem " + std::to_string(problem) + " had no noise, or its ICP failed");
+    if (overlap) *overlap = N.last_overlap[(size_t)problem];
+    if (n_elements) *n_elements = N.last_nb[(size_t)problem];
+    return PGICP_OK;
+}
 
 int pgicp_profile_enable(pgicp_ctx *c, int on)
 {

@@ -57,6 +57,12 @@ ABI_SYMBOLS = [
     "pgicp_voxel_grid_f32", "pgicp_voxel_grid_f64",
 ]
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
+# every symbol the companion header include/pgicp_noise.h declares (checked by tests/test_noise_overlap_host.py)
+NOISE_SYMBOLS = (
+    "pgicp_simple_sensor_noise_f32", "pgicp_simple_sensor_noise_f64",
+    "pgicp_arm_reading_noise_f32", "pgicp_arm_reading_noise_f64", "pgicp_last_noise_overlap",
+)
+SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
 class Params(C.Structure):
@@ -529,30 +535,111 @@ class Context:
         self._check(self.lib.pgicp_map_size(self.h, C.c_int(map_id), C.byref(m)))
         return m.value
 
+    # ---- sensor noise (include/pgicp_noise.h) ---------------------------------
+    def simple_sensor_noise(self, xyz, sensor_type=0, gain=1.0, dtype=None, out=None):
+        """SimpleSensorNoiseDataPointsFilter's descriptor on the device (pgicp_simple_sensor_noise_*): one value per point.
+        numpy in -> numpy out, torch CUDA in -> torch CUDA out; `out`: a contiguous 1-D array / CUDA tensor of the cloud's dtype
+        to fill instead (host and device may be mixed)."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+        x = _Buf(xyz, dtype)
+        if out is None:
+            if x.mem == DEVICE and _is_torch(xyz):
+                import torch
+                out = torch.empty((x.n,), dtype=xyz.dtype, device=xyz.device)
+            else:
+                out = np.empty(x.n, dtype=x.dtype)
+        if _is_torch(out) and out.is_cuda:
+            assert out.dim() == 1 and out.is_contiguous() and out.shape[0] == x.n
+            assert np.dtype(str(out.dtype).replace("torch.", "")) == x.dtype
+            optr, omem = out.data_ptr(), DEVICE
+        else:
+            assert isinstance(out, np.ndarray) and out.ndim == 1 and out.flags.c_contiguous and out.shape[0] == x.n and out.dtype == x.dtype
+            optr, omem = out.ctypes.data, HOST
+        fn = getattr(self.lib, "pgicp_simple_sensor_noise" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(x.n), C.c_int(x.mem), C.c_int(int(sensor_type)),
+                       C.c_double(float(gain)), C.c_void_p(optr), C.c_int(omem)))
+        return out
+
+    def arm_reading_noise(self, noises, dtype):
+        """pgicp_arm_reading_noise_*: the `simpleSensorNoise` row of every reading of the NEXT align / align_batch /
+        align_residual_batch / icp_pair call (one-shot).  noises: one entry per problem -- a 1-D numpy array (any positive
+        stride: a row of a descriptor matrix), a 1-D torch CUDA tensor, or None (that problem has no noise); all in host
+        memory or all on the device.  dtype: the element type of the ICP call."""
+        dtype = np.dtype(dtype)
+        P = len(noises)
+        ptrs, strides, counts, keep, mems = [], [], [], [], set()
+        for v in noises:
+            if v is None:
+                ptrs.append(None), strides.append(1), counts.append(0)
+                continue
+            if _is_torch(v) and v.is_cuda:
+                if v.dim() != 1 or v.stride(0) < 1 or np.dtype(str(v.dtype).replace("torch.", "")) != dtype:
+                    raise ValueError("arm_reading_noise: a 1-D tensor of the call's dtype with a positive stride is needed")
+                ptrs.append(v.data_ptr()), strides.append(v.stride(0)), counts.append(v.shape[0]), mems.add(DEVICE)
+            else:
+                v = np.asarray(v.cpu() if _is_torch(v) else v).astype(dtype, copy=False)
+                if v.ndim != 1 or v.strides[0] <= 0 or v.strides[0] % v.itemsize != 0:
+                    raise ValueError("arm_reading_noise: values must be 1-D with a positive stride of whole elements")
+                ptrs.append(v.ctypes.data), strides.append(v.strides[0] // v.itemsize), counts.append(v.shape[0]), mems.add(HOST)
+            keep.append(v)
+        if len(mems) > 1:
+            raise ValueError("arm_reading_noise: the rows must all be in host memory or all on the device")
+        fn = getattr(self.lib, "pgicp_arm_reading_noise" + self._sfx(dtype))
+        self._check(fn(self.h, C.c_int(P), (C.c_void_p * max(P, 1))(*ptrs), (C.c_int * max(P, 1))(*strides),
+                       (C.c_int * max(P, 1))(*counts), C.c_int(mems.pop() if mems else HOST)))
+        del keep
+
+    def last_noise_overlap(self, problem=0):
+        """pgicp_last_noise_overlap: (overlap, n_elements) of `problem` of the last ICP call, which must have been armed."""
+        ov, nb = C.c_double(0), C.c_int(0)
+        self._check(self.lib.pgicp_last_noise_overlap(self.h, C.c_int(problem), C.byref(ov), C.byref(nb)))
+        return ov.value, nb.value
+
+    def _noise_into(self, stats, noises):
+        """overlap_noise / n_elements into the stats dicts of an armed call (None for a problem without noise or one that failed)"""
+        for p, st in enumerate(stats):
+            ov = nb = None
+            if noises[p] is not None and st["status"] == OK:
+                ov, nb = self.last_noise_overlap(p)
+            st["overlap_noise"], st["n_elements"] = ov, nb
+
     # ---- full ICP -----------------------------------------------------------
-    def align(self, map_id, reading, T_init, dtype=None, normals=None):
-        """normals: the reading's `normals` descriptor (a SurfaceNormalOutlierFilter in the chain needs it)"""
+    def align(self, map_id, reading, T_init, dtype=None, normals=None, noise=None):
+        """normals: the reading's `normals` descriptor (a SurfaceNormalOutlierFilter in the chain needs it); noise: its
+        `simpleSensorNoise` row -- the stats then carry overlap_noise (getOverlap()'s sensor-noise branch) and n_elements"""
         if normals is not None:
-            T, st = self.align_batch(map_id, [reading], [T_init], dtype=dtype, normals=[normals])
+            T, st = self.align_batch(map_id, [reading], [T_init], dtype=dtype, normals=[normals], noises=None if noise is None else [noise])
             return T[0], st[0]
         r = _Buf(reading, dtype)
         T_out = (C.c_double * 16)()
         st = Stats()
         fn = getattr(self.lib, "pgicp_align" + self._sfx(r.dtype))
+        if noise is not None:
+            self.arm_reading_noise([noise], r.dtype)
         self._check(fn(self.h, C.c_int(map_id), C.c_void_p(r.ptr), C.c_int(r.stride), C.c_int(r.n), C.c_int(r.mem),
                        _T16(T_init), T_out, C.byref(st)))
-        return np.array(T_out[:]).reshape(4, 4), st.as_dict()
+        sd = st.as_dict()
+        if noise is not None:
+            self._noise_into([sd], [noise])
+        return np.array(T_out[:]).reshape(4, 4), sd
 
-    def align_residual_batch(self, map_ids, readings, T_inits, dtype=None, normals=None, raw_stats=False):
+    def align_residual_batch(self, map_ids, readings, T_inits, dtype=None, normals=None, raw_stats=False, noises=None):
         """pgicp_align_residual_batch: the ICPs of a batch of loop-closure candidates and, fused, the residual check of every
         result (LoopCloser.hpp:98, 343-365).  Returns (T (P,4,4), stats, residual (P,), ratio (P,), status (P,)); never raises
         for a failed candidate (its residual is +inf)."""
-        return self.align_batch(map_ids, readings, T_inits, dtype=dtype, raise_on_error=False, normals=normals, _residual=True, _raw_stats=raw_stats)
+        return self.align_batch(map_ids, readings, T_inits, dtype=dtype, raise_on_error=False, normals=normals, _residual=True, _raw_stats=raw_stats,
+                                noises=noises)
 
-    def align_batch(self, map_ids, readings, T_inits, dtype=None, raise_on_error=True, normals=None, _residual=False, _raw_stats=False):
+    def align_batch(self, map_ids, readings, T_inits, dtype=None, raise_on_error=True, normals=None, _residual=False, _raw_stats=False,
+                    noises=None):
         """`_raw_stats`: the pgicp_stats records come back as ONE numpy record array (fields as in include/pgicp.h) instead of a
-        list of dicts -- a batch of 512 loop-closure candidates does not need 512 dictionaries to fill 512 edge records."""
+        list of dicts -- a batch of 512 loop-closure candidates does not need 512 dictionaries to fill 512 edge records.
+        `noises`: one `simpleSensorNoise` row per reading (or None for a reading without): the stats dicts then carry
+        overlap_noise and n_elements (with `_raw_stats`: read them with last_noise_overlap(p))."""
         P = len(readings)
+        if noises is not None and len(noises) != P:
+            raise ValueError("align_batch: one noise row (or None) per reading is needed")
         if isinstance(map_ids, int):
             map_ids = [map_ids] * P
         bufs = _bufs(readings, dtype)
@@ -572,6 +659,8 @@ class Context:
             pa["nstride"] = [b.stride for b in nbufs]
         T_out = np.empty((P, 4, 4), dtype=np.float64)
         sa = np.zeros(P, dtype=_STATS_DTYPE)
+        if noises is not None:
+            self.arm_reading_noise(noises, bufs[0].dtype)
         if _residual:
             res, ratio, rst = np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)
             fn = getattr(self.lib, "pgicp_align_residual_batch" + self._sfx(bufs[0].dtype))
@@ -592,11 +681,13 @@ class Context:
         stats = [dict(status=st, iterations=it, converged=bool(cv), max_iter_reached=bool(mx), overlap=ov, residual=rs, trim_limit=tl,
                       n_kept=nk, n_finite=nf, cov=cov[p])
                  for p, (st, it, cv, mx, ov, rs, tl, nk, nf) in enumerate(zip(*cols))]
+        if noises is not None:
+            self._noise_into(stats, noises)
         if _residual:
             return T_out, stats, res, ratio, rst
         return T_out, stats
 
-    def icp_pair(self, reading, ref_xyz, ref_nrm, T_init, dtype=None):
+    def icp_pair(self, reading, ref_xyz, ref_nrm, T_init, dtype=None, noise=None):
         r = _Buf(reading, dtype)
         x = _Buf(ref_xyz, r.dtype)
         nb = _Buf(ref_nrm, r.dtype)
@@ -604,10 +695,15 @@ class Context:
         T_out = (C.c_double * 16)()
         st = Stats()
         fn = getattr(self.lib, "pgicp_icp_pair" + self._sfx(r.dtype))
+        if noise is not None:
+            self.arm_reading_noise([noise], r.dtype)
         self._check(fn(self.h, C.c_void_p(r.ptr), C.c_int(r.stride), C.c_int(r.n), C.c_void_p(x.ptr), C.c_int(x.stride),
                        C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(x.n), C.c_int(r.mem), _T16(T_init), T_out,
                        C.byref(st)))
-        return np.array(T_out[:]).reshape(4, 4), st.as_dict()
+        sd = st.as_dict()
+        if noise is not None:
+            self._noise_into([sd], [noise])
+        return np.array(T_out[:]).reshape(4, 4), sd
 
     # ---- stages -----------------------------------------------------------
     def match(self, map_id, reading, T=None, dtype=None):
