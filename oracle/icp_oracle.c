@@ -1650,6 +1650,44 @@ void FN(orc_covariance_o)(const real *p, int n, int K, const real *ref_xyz, cons
 {
     FN(covariance_ko)(p, n, K > 1 ? K : 1, ref_xyz, ref_nrm, ids, w, dT, sensor_std_dev, order, cov);
 }
+/* atan2 in IEEE operations only (+, -, *, /; no FMA: -ffp-contract=off), after the published fdlibm atan: reduction at
+ * 7/16, 11/16, 19/16, 39/16, odd polynomial of degree 23.  Within 1 ulp of atan2 for finite arguments.  The covariance's
+ * small-angle parameters go through it on both sides, so that they do not depend on whose libm computed them. */
+#ifndef ORC_DOUBLE   /* type-independent: defined once, in the f32 object */
+double orc_atan2(double y, double x)
+{
+    static const double hi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00};
+    static const double lo[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17};
+    static const double aT[11] = {3.33333333333329318027e-01, -1.99999999998764832476e-01, 1.42857142725034663711e-01, -1.11111104054623557880e-01,
+                                  9.09088713343650656196e-02, -7.69187620504482999495e-02, 6.66107313738753120669e-02, -5.83357013379057348645e-02,
+                                  4.97687799461593236017e-02, -3.65315727442169155270e-02, 1.62858201153657823623e-02};
+    const double pi = 3.1415926535897931160e+00, pi_lo = 1.2246467991473531772e-16, half_pi = hi[3] + lo[3];
+    if (isnan(y) || isnan(x)) return y + x;
+    if (y == 0.0) return (x > 0.0 || (x == 0.0 && !signbit(x))) ? y : (signbit(y) ? -pi : pi);
+    if (x == 0.0) return y > 0.0 ? half_pi : -half_pi;
+    double t = fabs(y / x), z;
+    int id = -1;
+    if (t < 0.4375) { if (t < 1.862645149230957e-09) id = -2; }
+    else if (t < 0.6875) { id = 0; t = (2.0 * t - 1.0) / (2.0 + t); }
+    else if (t < 1.1875) { id = 1; t = (t - 1.0) / (t + 1.0); }
+    else if (t < 2.4375) { id = 2; t = (t - 1.5) / (1.0 + 1.5 * t); }
+    else if (t < 7.378697629483821e+19) { id = 3; t = -1.0 / t; }
+    else id = 4;
+    if (id == -2) z = t;
+    else if (id == 4) z = half_pi;
+    else {
+        const double u = t * t, w = u * u;
+        const double s1 = u * (aT[0] + w * (aT[2] + w * (aT[4] + w * (aT[6] + w * (aT[8] + w * aT[10])))));
+        const double s2 = w * (aT[1] + w * (aT[3] + w * (aT[5] + w * (aT[7] + w * aT[9]))));
+        z = id < 0 ? t - t * (s1 + s2) : hi[id] - ((t * (s1 + s2) - lo[id]) - t);
+    }
+    if (x > 0.0) return y > 0.0 ? z : -z;
+    return y > 0.0 ? pi - (z - pi_lo) : (z - pi_lo) - pi;
+}
+#else
+double orc_atan2(double y, double x);
+#endif
+
 /* one pair's terms: the upper triangles of H (21) and G (21) -- both are symmetric sums of symmetric terms, h[a] h[b] and
  * gr[a] gr[b] + gq[a] gq[b] are the same doubles either way round -- added through the reduction tree (tree_sum) */
 typedef struct { const real *p, *ref_xyz, *ref_nrm, *w; const int *ids; int K; double alpha, beta, gamma, t_x, t_y, t_z; } FN(cov_ctx);
@@ -1695,9 +1733,14 @@ static void FN(covariance_ko)(const real *p, int n, int K, const real *ref_xyz, 
 {
     double H[36], G[36], acc[42];
     FN(cov_ctx) c = {p, ref_xyz, ref_nrm, w, ids, K, 0, 0, 0, dT[3], dT[7], dT[11]};
-    c.beta = -asin(dT[8]);
-    c.alpha = atan2(dT[9], dT[10]);
-    c.gamma = atan2(dT[4] / cos(c.beta), dT[0] / cos(c.beta));
+    /* beta = -asin(r20), alpha = atan2(r21, r22), gamma = atan2(r10 / cos(beta), r00 / cos(beta)), with cos(beta) =
+     * sqrt(1 - r20^2) and the arctangents of orc_atan2: two math libraries do not owe each other the same last bit */
+    {
+        const double s = dT[8], cb = sqrt((1.0 - s) * (1.0 + s));
+        c.beta = -orc_atan2(s, cb);
+        c.alpha = orc_atan2(dT[9], dT[10]);
+        c.gamma = orc_atan2(dT[4] / cb, dT[0] / cb);
+    }
     FN(tree_sum)((size_t)n * K, K, 42, order, FN(cov_pair), &c, acc);
     {
         int k = 0;

@@ -429,6 +429,12 @@ class Oracle:
             out.update(last_ids=ids, last_d2=d2)
         return out
 
+    def atan2(self, y, x):
+        """orc_atan2: the arctangent in IEEE operations only that the covariance's small-angle parameters go through"""
+        f = self.lib.orc_atan2
+        f.restype = C.c_double
+        return f(C.c_double(y), C.c_double(x))
+
     # -- checker (type independent) ---------------------------------------
     def checker(self, max_iters, min_rot, min_trans, smooth):
         c = Checker()

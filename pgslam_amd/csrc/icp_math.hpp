@@ -364,6 +364,57 @@ PGICP_HD int solve_p2point(const double *sys, double *T)
 }
 
 // inverse of a general 6x6 (Gauss-Jordan, partial pivoting); returns false if singular
+// ---- the covariance's small-angle parameters: arctangents in +, -, *, / and sqrt only -------------------------------
+// asin / atan2 / cos of the device's math library and of the host's are each accurate to an ulp, and so not always the
+// same double: an increment that is not tiny (a run the Counter stops while it still moves) then gave a covariance whose
+// last bits depended on where it was computed.  These follow the published fdlibm atan (argument reduction at 7/16,
+// 11/16, 19/16, 39/16, an odd polynomial of degree 23); every operation is an IEEE one, no FMA is formed (the arithmetic
+// contract), so the device, the host and the oracle's restatement give the same bits.  Within 1 ulp of atan2 for finite
+// arguments, 2 of asin.
+PGICP_HD double det_atan_pos(double x)          // x >= 0
+{
+    const double hi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01, 1.57079632679489655800e+00};
+    const double lo[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17, 1.39033110312309984516e-17, 6.12323399573676603587e-17};
+    int id;
+    if (x < 0.4375) {
+        if (x < 1.862645149230957e-09) return x;        // 2^-29
+        id = -1;
+    } else if (x < 1.1875) {
+        if (x < 0.6875) { id = 0; x = (2.0 * x - 1.0) / (2.0 + x); }
+        else { id = 1; x = (x - 1.0) / (x + 1.0); }
+    } else if (x < 2.4375) { id = 2; x = (x - 1.5) / (1.0 + 1.5 * x); }
+    else if (x < 7.378697629483821e+19) { id = 3; x = -1.0 / x; }      // 2^66
+    else return hi[3] + lo[3];
+    const double z = x * x, w = z * z;
+    const double s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 +
+                      w * (6.66107313738753120669e-02 + w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
+    const double s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 +
+                      w * (-5.83357013379057348645e-02 + w * -3.65315727442169155270e-02))));
+    if (id < 0) return x - x * (s1 + s2);
+    return hi[id] - ((x * (s1 + s2) - lo[id]) - x);
+}
+
+PGICP_HD double det_atan2(double y, double x)
+{
+    const double pi = 3.1415926535897931160e+00, pi_lo = 1.2246467991473531772e-16, half_pi = 1.57079632679489655800e+00 + 6.12323399573676603587e-17;
+    if (y != y || x != x) return y + x;
+    if (y == 0.0) return (x > 0.0 || (x == 0.0 && 1.0 / x > 0.0)) ? y : (1.0 / y < 0.0 ? -pi : pi);      // (1 / -0 = -inf: the zero's sign)
+    if (x == 0.0) return y > 0.0 ? half_pi : -half_pi;
+    const double z = det_atan_pos(fabs(y / x));
+    if (x > 0.0) return y > 0.0 ? z : -z;
+    return y > 0.0 ? pi - (z - pi_lo) : (z - pi_lo) - pi;
+}
+
+// (alpha, beta, gamma) of an increment dT (row-major 4x4), as PointToPlaneWithCov reads them off its rotation:
+// beta = -asin(r20), alpha = atan2(r21, r22), gamma = atan2(r10 / cos(beta), r00 / cos(beta)); cos(beta) = sqrt(1 - r20^2) >= 0
+PGICP_HD void small_angles(const double *dT, double &alpha, double &beta, double &gamma)
+{
+    const double s = dT[8], c = sqrt((1.0 - s) * (1.0 + s));
+    beta = -det_atan2(s, c);
+    alpha = det_atan2(dT[9], dT[10]);
+    gamma = det_atan2(dT[4] / c, dT[0] / c);
+}
+
 PGICP_HD bool inverse6(const double *H, double *Hi)
 {
     double M[6][12];

@@ -572,9 +572,9 @@ __global__ __launch_bounds__(kReduceBlock) void k_cov_reduce(const ProblemDev *_
     const MapDev<T> M = maps[P.map];
     const T limit = (T)P.limit;
     // small-angle parameters of the last increment
-    const double beta = -asin(P.dT[8]);
-    const double alpha = atan2(P.dT[9], P.dT[10]);
-    const double gamma = atan2(P.dT[4] / cos(beta), P.dT[0] / cos(beta));
+    // (small_angles: arctangents in IEEE operations only -- the math library's asin / atan2 / cos are not the host's to the bit)
+    double alpha, beta, gamma;
+    small_angles(P.dT, alpha, beta, gamma);
     const double t_x = P.dT[3], t_y = P.dT[7], t_z = P.dT[11];
     double Tp[12];
 #pragma unroll
