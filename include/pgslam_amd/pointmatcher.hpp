@@ -28,6 +28,7 @@
 
 #include "../pgicp.h"
 #include "../pgicp_noise.h"
+#include "../pgicp_density.h"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -146,6 +147,11 @@ template <> struct Abi<float> {
     static int map_create_batch(pgicp_ctx *c, int k, const float *const *x, const int *xs, const float *const *n, const int *ns, const int *m, int center, int *ids) { return pgicp_map_create_batch_f32(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
     static int normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig) { return pgicp_surface_normals_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
     static int normals_ids(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig, int32_t *ids) { return pgicp_surface_normals_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
+    static int densities(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig, float *dens) { return pgicp_surface_densities_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, dens); }
+    static int max_density(pgicp_ctx *c, const float *dens, int n, double md, uint64_t sd, int32_t *idx, int *n_out) { return pgicp_max_density_f32(c, dens, n, PGICP_HOST, md, sd, idx, n_out); }
+    static int normals_max_density(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, double dmax, uint64_t sd, const float *d, int dr, float *ox, float *on,
+                                   float *oe, float *odn, float *od, int32_t *idx, int *n_out)
+    { return pgicp_normals_max_density_f32(c, x, xs, n, PGICP_HOST, knn, md, dmax, sd, d, dr, ox, on, 3, oe, odn, od, idx, n_out); }
     static int sampling_normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const float *d, int dr, int avg,
                                 float *ox, float *on, float *od, int32_t *idx, int *n_out)
     { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
@@ -181,6 +187,11 @@ template <> struct Abi<double> {
     static int map_create_batch(pgicp_ctx *c, int k, const double *const *x, const int *xs, const double *const *n, const int *ns, const int *m, int center, int *ids) { return pgicp_map_create_batch_f64(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
     static int normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig) { return pgicp_surface_normals_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
     static int normals_ids(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig, int32_t *ids) { return pgicp_surface_normals_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
+    static int densities(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig, double *dens) { return pgicp_surface_densities_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, dens); }
+    static int max_density(pgicp_ctx *c, const double *dens, int n, double md, uint64_t sd, int32_t *idx, int *n_out) { return pgicp_max_density_f64(c, dens, n, PGICP_HOST, md, sd, idx, n_out); }
+    static int normals_max_density(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double dmax, uint64_t sd, const double *d, int dr, double *ox, double *on,
+                                   double *oe, double *odn, double *od, int32_t *idx, int *n_out)
+    { return pgicp_normals_max_density_f64(c, x, xs, n, PGICP_HOST, knn, md, dmax, sd, d, dr, ox, on, 3, oe, odn, od, idx, n_out); }
     static int sampling_normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const double *d, int dr, int avg,
                                 double *ox, double *on, double *od, int32_t *idx, int *n_out)
     { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
@@ -617,33 +628,20 @@ struct PointMatcher {
             const int n = (int)c.features.cols();
             if (n == 0 || (!keepNormals && !keepEigenValues && !keepDensities)) return;
             Matrix nrm(3, n), eig(3, n);
-            std::vector<int32_t> ids(keepDensities ? (size_t)n * knn : 0);
             const double md = std::isfinite((double)maxDist) ? (double)maxDist : 1e300;
-            check(ctx, pgslam_amd::Abi<T>::normals_ids(ctx, c.features.data(), (int)c.features.rows(), n, knn, md, nrm.data(), 3,
-                                                       keepEigenValues ? eig.data() : nullptr, keepDensities ? ids.data() : nullptr));
-            if (keepNormals) c.setDescriptor("normals", nrm);
             if (keepDensities) {
                 // [EXT] computeDensity: neighbours found / volume of the sphere that holds them around their MEAN, in T (the oracle's
-                // orc_densities); from the neighbour ids of the device search
+                // orc_densities) -- an epilogue of the device's normals kernel (pgicp_surface_densities_*): no id table comes back
+                if (knn < 3 || knn > 32) throw std::runtime_error("SurfaceNormalDataPointsFilter: keepDensities needs knn in [3, 32]");
                 Matrix dens(1, n);
-                for (int i = 0; i < n; i++) {
-                    const int32_t *nb = ids.data() + (size_t)i * knn;
-                    int cnt = 0;
-                    T sx = 0, sy = 0, sz = 0;
-                    for (int j = 0; j < knn; j++) if (nb[j] >= 0) { sx += c.features(0, nb[j]); sy += c.features(1, nb[j]); sz += c.features(2, nb[j]); cnt++; }
-                    T r2 = 0;
-                    if (cnt > 0) {
-                        const T mx = sx / (T)cnt, my = sy / (T)cnt, mz = sz / (T)cnt;
-                        for (int j = 0; j < knn; j++) if (nb[j] >= 0) {
-                            const T dx = c.features(0, nb[j]) - mx, dy = c.features(1, nb[j]) - my, dz = c.features(2, nb[j]) - mz;
-                            const T q = (dx * dx + dy * dy) + dz * dz;
-                            if (q > r2) r2 = q;
-                        }
-                    }
-                    const T r = std::sqrt(r2);
-                    dens(0, i) = (T)cnt / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
-                }
+                check(ctx, pgslam_amd::Abi<T>::densities(ctx, c.features.data(), (int)c.features.rows(), n, knn, md, keepNormals ? nrm.data() : nullptr, 3,
+                                                         keepEigenValues ? eig.data() : nullptr, dens.data()));
+                if (keepNormals) c.setDescriptor("normals", nrm);
                 c.setDescriptor("densities", dens);
+            } else {
+                check(ctx, pgslam_amd::Abi<T>::normals(ctx, c.features.data(), (int)c.features.rows(), n, knn, md, nrm.data(), 3,
+                                                       keepEigenValues ? eig.data() : nullptr));
+                if (keepNormals) c.setDescriptor("normals", nrm);
             }
             if (keepEigenValues) c.setDescriptor("eigValues", eig);
         }
@@ -944,15 +942,51 @@ struct PointMatcher {
     //! [EXT] MaxDensityDataPointsFilter{maxDensity} (DataPointsFilters/MaxDensity.cpp): needs the `densities` descriptor
     //! (SurfaceNormalDataPointsFilter{keepDensities: 1}); keeps a point at or below maxDensity, a denser one with probability
     //! maxDensity / density -- times (1 - nbSaturatedPts / nbPointsIn) in INTEGER arithmetic for points at the cloud's largest
-    //! density, as upstream writes it.  The draw is the build's seeded one (not rand()-parity, see RandomSampling).
+    //! density, as upstream writes it.  The draw is the build's seeded one (not rand()-parity, see RandomSampling).  On the device
+    //! (pgicp_max_density_*, the same bits) when there is one, unless PGSLAM_HOST_MAX_DENSITY=1 or the parameters are ones
+    //! the device call refuses (maxDensity not > 0, a seed >= 2^53); then the host loop.  ranOnDevice(): which of the two the last inPlaceFilter (or fused pass) took.
     struct MaxDensityDataPointsFilter : DataPointsFilter {
         T maxDensity; unsigned long long seed;
+        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
+        bool onDevice = false;
+        std::vector<T> densBuf;                      // the device form's buffers, kept from call to call
+        std::vector<int32_t> idxBuf;
         explicit MaxDensityDataPointsFilter(T d = T(10), unsigned long long s = 1) : maxDensity(d), seed(s) {}
-        void inPlaceFilter(DataPoints &c) override
+        MaxDensityDataPointsFilter(const MaxDensityDataPointsFilter &) = delete;
+        MaxDensityDataPointsFilter &operator=(const MaxDensityDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        //! a device is present and PGSLAM_HOST_MAX_DENSITY=1 does not force the host loop
+        //! what pgicp_max_density_* refuses, checked here: every other refusal of the device call is an error and throws
+        bool deviceTakesParameters() const { return maxDensity > T(0) && seed < (1ULL << 53); }
+        static bool deviceWanted()
         {
-            if (!c.descriptorExists("densities")) throw std::runtime_error("MaxDensityDataPointsFilter: Error, no densities found in descriptors.");
+            const char *knob = std::getenv("PGSLAM_HOST_MAX_DENSITY");
+            static const bool have_device = pgicp_device_count() > 0;
+            return have_device && !(knob && std::strcmp(knob, "1") == 0);
+        }
+        //! keeps the columns idx[0 .. kept) (ascending), in order
+        static void keepColumns(DataPoints &c, const int32_t *idx, int kept)
+        {
+            int k = 0;
+            compactColumns(c, [&](int j) { if (k < kept && idx[k] == j) { k++; return true; } return false; });
+        }
+        //! the device form (pgicp_max_density_*); false (the cloud untouched) for parameters the device call refuses
+        bool deviceFilter(DataPoints &c)
+        {
+            if (!deviceTakesParameters()) return false;
+            const int n = (int)c.features.cols(), rd = c.getDescriptorStartingRow("densities");
+            if (densBuf.size() < (size_t)n) densBuf.resize((size_t)n);
+            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            for (int i = 0; i < n; i++) densBuf[(size_t)i] = c.descriptors(rd, i);
+            int kept = 0;
+            check(ctx, pgslam_amd::Abi<T>::max_density(ctx, densBuf.data(), n, (double)maxDensity, (uint64_t)seed, idxBuf.data(), &kept));
+            keepColumns(c, idxBuf.data(), kept);
+            return true;
+        }
+        //! the host form: upstream's three passes
+        void hostFilter(DataPoints &c)
+        {
             const int n = (int)c.features.cols();
-            if (n == 0) return;
             const int rd = c.getDescriptorStartingRow("densities");
             T last = c.descriptors(rd, 0);
             for (int i = 1; i < n; i++) if (c.descriptors(rd, i) > last) last = c.descriptors(rd, i);
@@ -965,6 +999,59 @@ struct PointMatcher {
                 if (density == last) accept = accept * (float)(1 - saturated / n);
                 return (double)(RandomSamplingDataPointsFilter::mix(seed * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0 < (double)accept;
             });
+        }
+        void inPlaceFilter(DataPoints &c) override
+        {
+            onDevice = false;
+            if (!c.descriptorExists("densities")) throw std::runtime_error("MaxDensityDataPointsFilter: Error, no densities found in descriptors.");
+            const int n = (int)c.features.cols();
+            if (n == 0) return;
+            if (deviceWanted() && deviceFilter(c)) { onDevice = true; return; }
+            hostFilter(c);
+        }
+        //! SurfaceNormalDataPointsFilter{keepDensities} directly ahead of this filter (DataPointsFilters::apply): both as ONE device
+        //! pass (pgicp_normals_max_density_*) -- one upload of the cloud, one download of the kept points, the same bits as the two
+        //! filters one after the other.  false: nothing was done (no device, the knob, a cloud that already carries one of the
+        //! descriptors the pair writes -- setDescriptor would reuse its rows --, or parameters or coordinates the device call
+        //! refuses, checked here) and the caller applies the two filters as before; any other refusal of the call throws.
+        bool fusedWith(SurfaceNormalDataPointsFilter &sn, DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            if (n == 0 || frows < 3 || !sn.keepDensities || !deviceWanted() || !deviceTakesParameters() || sn.knn < 3 || sn.knn > 32) return false;
+            for (const char *name : {"normals", "densities", "eigValues"}) if (c.descriptorExists(name)) return false;
+            // (a coordinate that is not finite: the device refuses the cloud, and the unfused pair says so as it always did)
+            for (int i = 0; i < n; i++)
+                if (!std::isfinite(c.features(0, i)) || !std::isfinite(c.features(1, i)) || !std::isfinite(c.features(2, i))) return false;
+            const bool kn = sn.keepNormals, ke = sn.keepEigenValues;
+            Matrix ox(frows, n), on(3, kn ? n : 0), oe(3, ke ? n : 0), od(1, n), oc(drows, drows > 0 ? n : 0);
+            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            const double md = std::isfinite((double)sn.maxDist) ? (double)sn.maxDist : 1e300;
+            int kept = 0;
+            const int st = pgslam_amd::Abi<T>::normals_max_density(sn.ctx, c.features.data(), frows, n, sn.knn, md, (double)maxDensity, (uint64_t)seed,
+                                                                   drows > 0 ? c.descriptors.data() : nullptr, drows, ox.data(), kn ? on.data() : nullptr,
+                                                                   ke ? oe.data() : nullptr, od.data(), drows > 0 ? oc.data() : nullptr, idxBuf.data(), &kept);
+            check(sn.ctx, st);
+            // rows 0-2 from the device, further feature rows the kept points' own; descriptors: the carried rows, then normals,
+            // densities, eigValues -- the order the unfused pair appends them in
+            const int nd = drows + (kn ? 3 : 0) + 1 + (ke ? 3 : 0);
+            Matrix f(frows, kept), d(nd, kept);
+            for (int o = 0; o < kept; o++) {
+                const int i = idxBuf[(size_t)o];
+                for (int r = 0; r < 3; r++) f(r, o) = ox(r, o);
+                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
+                int q = 0;
+                for (int r = 0; r < drows; r++) d(q++, o) = oc(r, o);
+                if (kn) for (int r = 0; r < 3; r++) d(q++, o) = on(r, o);
+                d(q++, o) = od(0, o);
+                if (ke) for (int r = 0; r < 3; r++) d(q++, o) = oe(r, o);
+            }
+            c.features = f;
+            c.descriptors = d;
+            if (kn) c.descriptorLabels.push_back(typename DataPoints::Label("normals", 3));
+            c.descriptorLabels.push_back(typename DataPoints::Label("densities", 1));
+            if (ke) c.descriptorLabels.push_back(typename DataPoints::Label("eigValues", 3));
+            onDevice = true;
+            return true;
         }
     };
     //! [EXT] SimpleSensorNoiseDataPointsFilter{sensorType, gain} (DataPointsFilters/SimpleSensorNoise.cpp, restated as recalled):
@@ -1103,7 +1190,19 @@ struct PointMatcher {
             }
         }
         void init() { for (auto &f : *this) f->init(); }
-        void apply(DataPoints &cloud) { for (auto &f : *this) f->inPlaceFilter(cloud); }
+        //! the filters in order; one pattern is fused: SurfaceNormalDataPointsFilter{keepDensities} directly followed by
+        //! MaxDensityDataPointsFilter runs as one device pass (MaxDensityDataPointsFilter::fusedWith), every other list as before
+        void apply(DataPoints &cloud)
+        {
+            for (size_t k = 0; k < this->size(); k++) {
+                if (k + 1 < this->size()) {
+                    auto *sn = dynamic_cast<SurfaceNormalDataPointsFilter *>((*this)[k].get());
+                    auto *md = dynamic_cast<MaxDensityDataPointsFilter *>((*this)[k + 1].get());
+                    if (sn && md && sn->keepDensities && md->fusedWith(*sn, cloud)) { k++; continue; }
+                }
+                (*this)[k]->inPlaceFilter(cloud);
+            }
+        }
         //! every filter of the list has a device form (and the list fits pgicp_filter_cloud): the list as its argument
         bool deviceSpecs(std::vector<pgicp_filter> &out) const
         {

@@ -123,6 +123,7 @@ struct pgicp_ctx {
     struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop; } fset[4];
     DevBuf ssn_work, ssn_io, ssn_cnt;   // pgicp_sampling_surface_normal_*: the build's scratch, host inputs' / outputs' device copies, counters
     DevBuf vox_work, vox_io, vox_stat;  // pgicp_voxel_grid_*: the sort's scratch, host inputs' / outputs' device copies, bounds and counters
+    DevBuf dens_work, dens_io, dens_stat;   // include/pgicp_density.h: the filter's scratch and the normals kernel's rows, host inputs' / outputs' device copies, DensStat
     DevBuf robust_dev;              // RobustOutlierFilter: the pairs' absolute deviations from the median (the second selection's input)
     DevBuf gd_stage;                // pgicp_map_set_values: host values packed for the copy, and the kernel's two flags
     // (ABI 6, added) VarTrimmedDistOutlierFilter (pgicp_set_var_trim): on, {minRatio, maxRatio, lambda}; the sort's two key

@@ -122,11 +122,14 @@ __device__ __forceinline__ void jacobi3(double a[3][3], double v[3][3])
     }
 }
 
-template <typename T, int K>
+// DENS (pgicp_density.h): the `densities` row as an epilogue -- the neighbours, their count and their mean are at hand, so the
+// largest squared distance to the mean rides in the scatter loop and no id table leaves the kernel; out_nrm may then be null.
+// The statement is the oracle's orc_densities, in T.  DENS = false is the kernel as it was.
+template <typename T, int K, bool DENS = false>
 __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__restrict__ maps, int map, int knn, T max_dist,
                                                           T eps_rank, T *__restrict__ out_nrm, int out_stride,
                                                           T *__restrict__ out_eig, int *__restrict__ out_ids,
-                                                          T *__restrict__ out_d2)
+                                                          T *__restrict__ out_d2, T *__restrict__ out_dens = nullptr)
 {
     const MapDev<T> M = maps[map];
     const int s0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -154,6 +157,7 @@ __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__rest
             sx += v.x; sy += v.y; sz += v.z; cnt++;
         }
     T c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
+    T r2 = 0;                                                        // DENS: the largest squared distance to the mean, by strict >
     if (cnt > 0) {
         const T mx = sx / (T)cnt, my = sy / (T)cnt, mz = sz / (T)cnt;
 #pragma unroll
@@ -162,7 +166,14 @@ __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__rest
                 const auto v = load_rec<T>(M.pts, L.slot[j]);
                 const T dx = v.x - mx, dy = v.y - my, dz = v.z - mz;
                 c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
+                if constexpr (DENS) { const T q = (dx * dx + dy * dy) + dz * dz; if (q > r2) r2 = q; }
             }
+    }
+    if constexpr (DENS) {
+        if (out_dens) {
+            const T r = sqrt_rn_t(r2);
+            out_dens[self] = (T)cnt / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
+        }
     }
     double A[3][3] = {{(double)c00, (double)c01, (double)c02}, {(double)c01, (double)c11, (double)c12}, {(double)c02, (double)c12, (double)c22}};
     double V[3][3];
@@ -184,8 +195,10 @@ __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__rest
         nz = (T)(lo == 0 ? V[2][0] : (lo == 1 ? V[2][1] : V[2][2]));
         w0 = (T)elo; w1 = (T)emid; w2 = (T)ehi;
     }
-    T *o = out_nrm + (long long)self * out_stride;
-    o[0] = nx; o[1] = ny; o[2] = nz;
+    if (!DENS || out_nrm) {
+        T *o = out_nrm + (long long)self * out_stride;
+        o[0] = nx; o[1] = ny; o[2] = nz;
+    }
     if (out_eig) { out_eig[3LL * self] = w0; out_eig[3LL * self + 1] = w1; out_eig[3LL * self + 2] = w2; }
     if (out_ids || out_d2) {
 #pragma unroll

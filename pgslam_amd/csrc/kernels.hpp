@@ -155,4 +155,21 @@ template <typename T>
 void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<T> &g, int bits, int centroid, const T *desc, int drows, int average,
                        const VoxScratch &w, T *out_xyz, int os, T *out_desc, int *kept_idx, int *out_count, VoxStat *stat);
 
+// include/pgicp_density.h (k_density.inc): the densities as an epilogue of the normals kernel, and MaxDensityDataPointsFilter
+struct DensStat {
+    unsigned long long key;         // the largest order-preserving key of a non-NaN density (0: none seen)
+    int saturated;                  // #{dens[i] == last}
+    int first_nan;                  // dens[0] is a NaN: `last` is a NaN, nothing equals it
+};
+template <typename T>
+int launch_surface_densities(hipStream_t st, const MapDev<T> *maps, int map, int m, int knn, T max_dist, T eps_rank, T *out_nrm,
+                             int out_stride, T *out_eig, T *out_dens);
+template <typename T>
+void launch_max_density(hipStream_t st, const T *dens, int n, T max_density, unsigned long long seed, DensStat *stat, int *keep, int *pos,
+                        int *block_sums);
+template <typename T>
+void launch_density_compact(hipStream_t st, int n, const int *keep, const int *pos, const T *xyz, int stride, const T *desc, int drows,
+                            const T *nrm, const T *eig, const T *dens, T *out_xyz, T *out_desc, T *out_nrm, int out_nstride, T *out_eig,
+                            T *out_dens, int *kept_idx);
+
 }  // namespace pgicp

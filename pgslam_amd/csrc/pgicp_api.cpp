@@ -6,6 +6,7 @@
 // There is no CPU compute path here: every stage runs on the GPU.
 #include "pgicp.h"
 #include "pgicp_noise.h"
+#include "pgicp_density.h"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -36,6 +37,7 @@ using namespace pgicp;
 #include "api_filters_uploads.inc"    // pgicp_filter_cloud*, batched map ABI, last-call diagnostics, map transfer, pgicp_upload_*
 #include "api_sampling.inc"           // pgicp_sampling_surface_normal_* (SamplingSurfaceNormalDataPointsFilter)
 #include "api_voxel.inc"              // pgicp_voxel_grid_* (VoxelGridDataPointsFilter)
+#include "api_density.inc"            // pgicp_surface_densities_*, pgicp_max_density_*, pgicp_normals_max_density_* (pgicp_density.h)
 
 extern "C" {
 
@@ -160,6 +162,7 @@ void pgicp_ctx_destroy(pgicp_ctx *c)
     }
     c->ssn_work.release(); c->ssn_io.release(); c->ssn_cnt.release();
     c->vox_work.release(); c->vox_io.release(); c->vox_stat.release();
+    c->dens_work.release(); c->dens_io.release(); c->dens_stat.release();
     c->noise.vals.release(); c->noise.off_dev.release(); c->noise.dist.release(); c->noise.out.release();
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto &m : c->f32.maps) free_map<float>(nullptr, m);
@@ -524,6 +527,27 @@ int pgicp_voxel_grid_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int
                          int *n_out)
 { return voxel_grid<double>(c, xyz, stride, n, mem, v_size, use_centroid, desc, drows, average_descriptors, out_xyz, out_stride, out_desc, kept_idx,
                             out_count, n_out); }
+
+int pgicp_surface_densities_f32(pgicp_ctx *c, const float *xyz, int stride, int n, int mem, int knn, double max_dist, float *out_nrm, int out_stride,
+                                float *out_eig, float *out_dens)
+{ return surface_densities<float>(c, xyz, stride, n, mem, knn, max_dist, out_nrm, out_stride, out_eig, out_dens); }
+int pgicp_surface_densities_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int mem, int knn, double max_dist, double *out_nrm, int out_stride,
+                                double *out_eig, double *out_dens)
+{ return surface_densities<double>(c, xyz, stride, n, mem, knn, max_dist, out_nrm, out_stride, out_eig, out_dens); }
+int pgicp_max_density_f32(pgicp_ctx *c, const float *dens, int n, int mem, double max_density_, uint64_t seed, int32_t *kept_idx, int *n_out)
+{ return max_density<float>(c, dens, n, mem, max_density_, seed, kept_idx, n_out); }
+int pgicp_max_density_f64(pgicp_ctx *c, const double *dens, int n, int mem, double max_density_, uint64_t seed, int32_t *kept_idx, int *n_out)
+{ return max_density<double>(c, dens, n, mem, max_density_, seed, kept_idx, n_out); }
+int pgicp_normals_max_density_f32(pgicp_ctx *c, const float *xyz, int stride, int n, int mem, int knn, double max_dist, double max_density_, uint64_t seed,
+                                  const float *desc, int drows, float *out_xyz, float *out_nrm, int out_nstride, float *out_eig, float *out_dens,
+                                  float *out_desc, int32_t *kept_idx, int *n_out)
+{ return normals_max_density<float>(c, xyz, stride, n, mem, knn, max_dist, max_density_, seed, desc, drows, out_xyz, out_nrm, out_nstride, out_eig, out_dens,
+                                    out_desc, kept_idx, n_out); }
+int pgicp_normals_max_density_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int mem, int knn, double max_dist, double max_density_, uint64_t seed,
+                                  const double *desc, int drows, double *out_xyz, double *out_nrm, int out_nstride, double *out_eig, double *out_dens,
+                                  double *out_desc, int32_t *kept_idx, int *n_out)
+{ return normals_max_density<double>(c, xyz, stride, n, mem, knn, max_dist, max_density_, seed, desc, drows, out_xyz, out_nrm, out_nstride, out_eig, out_dens,
+                                     out_desc, kept_idx, n_out); }
 
 int pgicp_transform_f32(pgicp_ctx *c, const double T[16], const float *in, int is, float *out, int os, int n, int ro, int mem)
 { return transform<float>(c, T, in, is, out, os, n, ro, mem); }

@@ -62,6 +62,11 @@ NOISE_SYMBOLS = (
     "pgicp_simple_sensor_noise_f32", "pgicp_simple_sensor_noise_f64",
     "pgicp_arm_reading_noise_f32", "pgicp_arm_reading_noise_f64", "pgicp_last_noise_overlap",
 )
+# every symbol the companion header include/pgicp_density.h declares (checked by tests/test_density_host.py)
+DENSITY_SYMBOLS = (
+    "pgicp_surface_densities_f32", "pgicp_surface_densities_f64", "pgicp_max_density_f32", "pgicp_max_density_f64",
+    "pgicp_normals_max_density_f32", "pgicp_normals_max_density_f64",
+)
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -939,6 +944,92 @@ class Context:
                        C.c_int(drows), C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(od), ptr(oi), ptr(oc), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k], descriptors=od[:k] if od is not None else None, kept_idx=oi[:k], count=oc[:k])
+
+    # ---- densities and MaxDensity (include/pgicp_density.h) ------------------------
+    def surface_densities(self, xyz, knn=10, max_dist=float("inf"), dtype=None, want_normals=True, want_eigen=True):
+        """SurfaceNormalDataPointsFilter{keepDensities: 1} on the device (pgicp_surface_densities_*): one kernel, no neighbour
+        table.  numpy in -> numpy out, torch CUDA in -> torch CUDA out.  Returns dict(normals (n,3) or None, eigen_values (n,3)
+        ascending or None, densities (n,))."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+        x = _Buf(xyz, dtype)
+        n = x.n
+        md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape: torch.empty(shape, dtype=xyz.dtype, device=xyz.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            mk = lambda shape: np.empty(shape, dtype=x.dtype)
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        nrm = mk((n, 3)) if want_normals else None
+        eig = mk((n, 3)) if want_eigen else None
+        dens = mk((n,))
+        fn = getattr(self.lib, "pgicp_surface_densities" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+                       ptr(nrm), C.c_int(3), ptr(eig), ptr(dens)))
+        return dict(normals=nrm, eigen_values=eig, densities=dens)
+
+    def max_density(self, densities, max_density=10.0, seed=1, dtype=None):
+        """MaxDensityDataPointsFilter's stage on the device (pgicp_max_density_*): the ascending indices (int32) of the points it
+        keeps.  numpy in -> numpy out, torch CUDA in -> torch CUDA out."""
+        if _is_torch(densities) and densities.is_cuda:
+            import torch
+            d = densities.contiguous()
+            n, mem, dt = int(d.shape[0]), DEVICE, np.dtype(str(d.dtype).replace("torch.", ""))
+            idx = torch.empty((max(n, 1),), dtype=torch.int32, device=d.device)
+            pd, pi = C.c_void_p(d.data_ptr()), C.c_void_p(idx.data_ptr())
+        else:
+            d = np.ascontiguousarray(np.asarray(densities), dtype=dtype)
+            assert d.ndim == 1 and d.dtype in (np.float32, np.float64)
+            n, mem, dt = len(d), HOST, d.dtype
+            idx = np.empty(max(n, 1), dtype=np.int32)
+            pd, pi = C.c_void_p(d.ctypes.data), C.c_void_p(idx.ctypes.data)
+        n_out = C.c_int(0)
+        fn = getattr(self.lib, "pgicp_max_density" + self._sfx(dt))
+        self._check(fn(self.h, pd, C.c_int(n), C.c_int(mem), C.c_double(float(max_density)), C.c_uint64(int(seed)), pi, C.byref(n_out)))
+        return idx[:n_out.value]
+
+    def normals_max_density(self, xyz, knn=10, max_dist=float("inf"), max_density=10.0, seed=1, descriptors=None, dtype=None):
+        """SurfaceNormal{keepDensities} -> MaxDensity as one device pass (pgicp_normals_max_density_*).  numpy in -> numpy out,
+        torch CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
+        normals (k,3), eigen_values (k,3), densities (k,), descriptors (k,drows) or None, kept_idx (k,) int32) for the k kept
+        points, in ascending input index."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+        x = _Buf(xyz, dtype)
+        n = x.n
+        md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
+        d = None
+        drows = 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
+                assert d.ndim == 2 and d.shape[0] == n
+            drows = int(d.shape[1])
+        m = max(n, 1)
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape, dt=None: torch.empty(shape, dtype=dt or xyz.dtype, device=xyz.device)
+            oi = mk((m,), torch.int32)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            mk = lambda shape: np.empty(shape, dtype=x.dtype)
+            oi = np.empty(m, dtype=np.int32)
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        ox, on, oe, od = mk((m, x.stride)), mk((m, 3)), mk((m, 3)), mk((m,))
+        oc = mk((m, drows)) if d is not None else None
+        n_out = C.c_int(0)
+        fn = getattr(self.lib, "pgicp_normals_max_density" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+                       C.c_double(float(max_density)), C.c_uint64(int(seed)), ptr(d), C.c_int(drows), ptr(ox), ptr(on), C.c_int(3), ptr(oe),
+                       ptr(od), ptr(oc), ptr(oi), C.byref(n_out)))
+        k = n_out.value
+        return dict(xyz=ox[:k, :3], normals=on[:k], eigen_values=oe[:k], densities=od[:k],
+                    descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k])
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
