@@ -121,9 +121,10 @@ struct pgicp_ctx {
     // reading, for the next three calls: a localizer that pre-processes scan k + 1 while scan k aligns, and now and then a
     // scan that was not pre-processed ahead, has three calls between making a reading and aligning it)
     struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop; } fset[4];
-    DevBuf ssn_work, ssn_io, ssn_cnt;   // pgicp_sampling_surface_normal_*: the build's scratch, host inputs' / outputs' device copies, counters
-    DevBuf vox_work, vox_io, vox_stat;  // pgicp_voxel_grid_*: the sort's scratch, host inputs' / outputs' device copies, bounds and counters
-    DevBuf dens_work, dens_io, dens_stat;   // include/pgicp_density.h: the filter's scratch and the normals kernel's rows, host inputs' / outputs' device copies, DensStat
+    // pgicp_sampling_surface_normal_*, pgicp_voxel_grid_* and include/pgicp_density.h share three buffers: the scratch of the call
+    // running, the device copies of its host inputs / outputs, its counters.  The calls of a context are serialised on its stream
+    // and none hands a pointer into these back, so every call carves them anew and they hold the largest call's need.
+    DevBuf dpf_work, dpf_io, dpf_stat;
     DevBuf robust_dev;              // RobustOutlierFilter: the pairs' absolute deviations from the median (the second selection's input)
     DevBuf gd_stage;                // pgicp_map_set_values: host values packed for the copy, and the kernel's two flags
     // (ABI 6, added) VarTrimmedDistOutlierFilter (pgicp_set_var_trim): on, {minRatio, maxRatio, lambda}; the sort's two key
@@ -533,6 +534,75 @@ int to_device(pgicp_ctx *c, const T *p, int stride, int n, int mem, DevBuf &stag
     XFER(c, h2d(c, (char *)stage.p + stage_off_bytes, p, bytes));
     *out = (const T *)((char *)stage.p + stage_off_bytes);
     return PGICP_OK;
+}
+
+// ---- staging of the cloud-in, cloud-out filters (pgicp_ctx::dpf_*) ----
+// Size `buf` for a layout and point the layout into it: `layout(Carve &)` names every array once and is run twice.
+template <class Layout>
+int carve_buf(pgicp_ctx *c, DevBuf &buf, Layout &&layout)
+{
+    Carve measure;
+    layout(measure);
+    HIPC(c, buf.ensure(measure.used));
+    Carve cv(buf.p);
+    layout(cv);
+    return PGICP_OK;
+}
+
+// The cloud a filter reads: strided coordinates and optional descriptor rows.  carve() names their device copies in the I/O
+// buffer (host memory); upload_cloud() fills those, or -- device memory -- points at the caller's arrays and makes the stream
+// wait for an upload they may belong to (the caller holds an UploadUse).
+template <typename T>
+struct CloudIn {
+    const T *xyz, *desc;
+    void carve(Carve &cv, int stride, int n, int drows) { xyz = cv.take<T>((size_t)(n - 1) * stride + 3); desc = cv.take<T>((size_t)drows * n, drows > 0); }
+};
+template <typename T>
+int upload_cloud(pgicp_ctx *c, int mem, const T *xyz, int stride, int n, const T *desc, int drows, CloudIn<T> &in)
+{
+    if (mem == PGICP_DEVICE) {
+        for (const T *p : {xyz, desc})
+            if (p && (c->up[0].pending || c->up[1].pending)) c->up_seen |= upload_wait(c, p);
+        in.xyz = xyz; in.desc = desc;
+        return PGICP_OK;
+    }
+    XFER(c, h2d(c, (void *)in.xyz, xyz, sizeof(T) * ((size_t)(n - 1) * stride + 3)));
+    if (desc) XFER(c, h2d(c, (void *)in.desc, desc, sizeof(T) * (size_t)drows * n));
+    return PGICP_OK;
+}
+
+// A call's counters back on the host: one round trip, after which everything queued so far has run.
+static int read_back(pgicp_ctx *c, void *host, const void *dev, size_t bytes)
+{
+    XFER(c, d2h(c, host, dev, bytes));
+    HIPC(c, stream_sync(c));
+    HIPC(c, hipGetLastError());
+    return PGICP_OK;
+}
+
+// Rows of 3 values a point from a device array at `dev_stride` to a host array at `stride`.  Packed on both sides it is one d2h;
+// otherwise the rows travel into a temporary, and land() -- the sync that completes every fetch queued before it -- spreads them.
+template <typename T>
+struct RowSpread {
+    struct Job { T *out; int stride, dev_stride, count; std::vector<T> tmp; };
+    std::vector<Job> jobs;
+    int land(pgicp_ctx *c)
+    {
+        HIPC(c, stream_sync(c));
+        for (const Job &j : jobs)
+            for (int k = 0; k < j.count; k++) std::memcpy(j.out + (size_t)k * j.stride, j.tmp.data() + (size_t)k * j.dev_stride, 3 * sizeof(T));
+        jobs.clear();
+        return PGICP_OK;
+    }
+};
+template <typename T>
+int fetch_rows3(pgicp_ctx *c, T *out, int stride, const T *dev, int count, RowSpread<T> &late, int dev_stride = 3)
+{
+    if (!out || count <= 0) return PGICP_OK;
+    const size_t vals = (size_t)(count - 1) * dev_stride + 3;
+    if (stride == 3 && dev_stride == 3) return d2h(c, out, dev, sizeof(T) * vals);
+    late.jobs.push_back({out, stride, dev_stride, count, std::vector<T>(vals)});
+    return d2h(c, late.jobs.back().tmp.data(), dev, sizeof(T) * vals);
 }
 
 static int pinned_ensure(pgicp_ctx *c, char **buf, size_t *cap, size_t bytes)

@@ -51,7 +51,7 @@ int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat, int
     HIPC(c, S.in_f.ensure(bf)); HIPC(c, S.out_f.ensure(bf));
     if (dev_desc) { HIPC(c, S.in_d.ensure(bd)); HIPC(c, S.out_d.ensure(bd)); }
     HIPC(c, S.keep.ensure(sizeof(int) * ((size_t)n + 1))); HIPC(c, S.pos.ensure(sizeof(int) * ((size_t)n + 1)));
-    HIPC(c, S.bsum.ensure(sizeof(int) * ((size_t)n / kScanChunkHost + 4)));
+    HIPC(c, S.bsum.ensure(sizeof(int) * scan_scratch_ints(n)));
     const bool want_idx = kept_idx || ident;
     if (want_idx) HIPC(c, S.idx.ensure(sizeof(int) * (size_t)n));
     XFER(c, h2d(c, S.in_f.p, feat, bf));
@@ -139,7 +139,7 @@ int filter_cloud_dev(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat,
     const int cap = std::min(dropped_cap, n);
     HIPC(c, S.in_f.ensure(bf)); HIPC(c, S.out_f.ensure(bf));
     HIPC(c, S.keep.ensure(sizeof(int) * ((size_t)n + 1))); HIPC(c, S.pos.ensure(sizeof(int) * ((size_t)n + 1)));
-    HIPC(c, S.bsum.ensure(sizeof(int) * ((size_t)n / kScanChunkHost + 4)));
+    HIPC(c, S.bsum.ensure(sizeof(int) * scan_scratch_ints(n)));
     HIPC(c, S.drop.ensure(sizeof(int) * (size_t)std::max(cap, 1)));
     XFER(c, h2d(c, S.in_f.p, feat, bf));
     launch_filter_cloud<T>(c->stream, S.in_f.as<T>(), frows, frows, nullptr, 0, n, nf, types, params, nullptr, -1, -1, S.keep.as<int>(), S.pos.as<int>(),

@@ -106,7 +106,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
         HIPC(c, c->active.ensure(sizeof(int) * (size_t)P));
         HIPC(c, c->qcounts.ensure(sizeof(int) * nbins));
         HIPC(c, c->qstart.ensure(sizeof(int) * (nbins + 1)));
-        HIPC(c, c->qblock.ensure(sizeof(int) * (nbins / kScanChunkHost + 2)));
+        HIPC(c, c->qblock.ensure(sizeof(int) * scan_scratch_ints(nbins)));
     }
     HIPC(c, S.slot.ensure(sizeof(int) * (size_t)L.total * L.knn));
     HIPC(c, S.d2.ensure(sizeof(T) * (size_t)L.total * L.knn));

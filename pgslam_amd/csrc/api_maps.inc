@@ -279,7 +279,7 @@ int map_create_batch(pgicp_ctx *c, int n, const MapSrc<T> *src, int mem, int cen
     const size_t n_scratch = (size_t)std::max(tot_b + 2, tot_c);
     HIPC(c, c->tmp_a.ensure(sizeof(int) * (size_t)tot_m));                               // fine-cell keys: by point, then by slot
     HIPC(c, c->tmp_b.ensure(sizeof(int) * n_scratch));                                   // bin counts, then sweep scratch
-    HIPC(c, c->tmp_c.ensure(sizeof(int) * ((size_t)std::max(tot_b + 1, succ ? tot_m + 1 : 0LL) / kScanChunkHost + 2)));  // the scans' block sums
+    HIPC(c, c->tmp_c.ensure(sizeof(int) * scan_scratch_ints((size_t)std::max(tot_b + 1, succ ? tot_m + 1 : 0LL))));  // the scans' block sums
     if (succ) {                                                                           // first-of-cell flags, and their ranks
         HIPC(c, c->tmp_f.ensure(sizeof(int) * (size_t)(tot_m + 1)));
         HIPC(c, c->tmp_r.ensure(sizeof(int) * (size_t)(tot_m + 1)));

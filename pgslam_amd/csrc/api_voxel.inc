@@ -30,46 +30,29 @@ int voxel_grid(pgicp_ctx *c, const T *xyz, int stride, int n, int mem, const dou
     HIPC(c, hipSetDevice(c->device));
     UploadUse uu(c);
     const int dr = desc ? drows : 0;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t sz[kVoxArrays];
-    const size_t work = voxel_grid_scratch(n, sz);
-    const size_t b_in = up(sizeof(T) * ((size_t)(n - 1) * stride + 3)), b_din = up(sizeof(T) * (size_t)dr * n),
-                 b_ox = up(sizeof(T) * 3 * (size_t)n), b_od = b_din, b_oi = up(sizeof(int) * (size_t)n);
-    HIPC(c, c->vox_work.ensure(work + 256));
-    if (mem == PGICP_HOST) HIPC(c, c->vox_io.ensure(b_in + b_din + b_ox + b_od + 2 * b_oi));
-    HIPC(c, c->vox_stat.ensure(sizeof(VoxStat)));
+    // scratch of the sort, then (host memory) the inputs' device copies and the outputs packed: 3 values a point
     VoxScratch w;
-    {
-        char *p = (char *)c->vox_work.p;
-        void **slots[kVoxArrays] = {(void **)&w.key[0], (void **)&w.key[1], (void **)&w.idx[0], (void **)&w.idx[1], (void **)&w.hist, (void **)&w.hoff,
-                                    (void **)&w.bsum, (void **)&w.head, (void **)&w.hs, (void **)&w.start, (void **)&w.first, (void **)&w.vox_of,
-                                    (void **)&w.pos, (void **)&w.heavy};
-        for (int k = 0; k < kVoxArrays; k++) { *slots[k] = p; p += sz[k]; }
-    }
-    const T *d_xyz = xyz, *d_desc = desc;
+    XFER(c, carve_buf(c, c->dpf_work, [&](Carve &cv) { w = vox_scratch(cv, n); }));
+    HIPC(c, c->dpf_stat.ensure(sizeof(VoxStat)));
+    CloudIn<T> in;
     T *d_ox = out_xyz, *d_od = out_desc;
     int32_t *d_oi = kept_idx, *d_oc = out_count;
     int os = out_stride;
     if (mem == PGICP_HOST) {
-        char *p = (char *)c->vox_io.p;
-        XFER(c, h2d(c, p, xyz, sizeof(T) * ((size_t)(n - 1) * stride + 3)));
-        d_xyz = (const T *)p;
-        if (desc) { XFER(c, h2d(c, p + b_in, desc, sizeof(T) * (size_t)dr * n)); d_desc = (const T *)(p + b_in); }
-        d_ox = (T *)(p + b_in + b_din);                      // the outputs packed: 3 values a point
-        d_od = desc ? (T *)(p + b_in + b_din + b_ox) : nullptr;
-        d_oi = (int32_t *)(p + b_in + b_din + b_ox + b_od);
-        d_oc = (int32_t *)(p + b_in + b_din + b_ox + b_od + b_oi);
+        XFER(c, carve_buf(c, c->dpf_io, [&](Carve &cv) {
+            in.carve(cv, stride, n, dr);
+            d_ox = cv.take<T>(3 * (size_t)n);
+            d_od = cv.take<T>((size_t)dr * n, desc);
+            d_oi = cv.take<int32_t>((size_t)n);
+            d_oc = cv.take<int32_t>((size_t)n);
+        }));
         os = 3;
-    } else {
-        uu.touch(xyz);
-        if (desc) uu.touch(desc);
     }
-    VoxStat *stat = c->vox_stat.as<VoxStat>();
+    XFER(c, upload_cloud<T>(c, mem, xyz, stride, n, desc, dr, in));
+    VoxStat *stat = c->dpf_stat.as<VoxStat>();
     VoxStat h;
-    launch_voxel_bounds<T>(c->stream, d_xyz, stride, n, stat);
-    XFER(c, d2h(c, &h, stat, sizeof h));
-    HIPC(c, stream_sync(c));
-    HIPC(c, hipGetLastError());
+    launch_voxel_bounds<T>(c->stream, in.xyz, stride, n, stat);
+    XFER(c, read_back(c, &h, stat, sizeof h));
     if (h.bad) return fail(c, PGICP_ERR_ARG, "pgicp_voxel_grid: a coordinate is NaN or infinite");
     // rules 1-2 in T; deviation (a): a grid with a numDiv >= 2^31 or a product of divisions >= 2^62 is refused
     for (int a = 0; a < 3; a++) {
@@ -87,22 +70,17 @@ int voxel_grid(pgicp_ctx *c, const T *xyz, int stride, int n, int mem, const dou
     const int bits = 64 - __builtin_clzll(top);
     {
         ProfScope ps(c, PGICP_PROF_NORMALS, n);
-        launch_voxel_grid<T>(c->stream, d_xyz, stride, n, g, bits, use_centroid ? 1 : 0, d_desc, dr, average ? 1 : 0, w, d_ox, os, d_od, d_oi, d_oc, stat);
+        launch_voxel_grid<T>(c->stream, in.xyz, stride, n, g, bits, use_centroid ? 1 : 0, in.desc, dr, average ? 1 : 0, w, d_ox, os, d_od, d_oi, d_oc, stat);
     }
     int kept = 0;
-    XFER(c, d2h(c, &kept, &stat->kept, sizeof kept));
-    HIPC(c, stream_sync(c));
-    HIPC(c, hipGetLastError());
+    XFER(c, read_back(c, &kept, &stat->kept, sizeof kept));
     if (mem == PGICP_HOST && kept > 0) {
-        std::vector<T> tx;
-        T *hx = out_xyz;
-        if (out_stride != 3) { tx.resize(3 * (size_t)kept); hx = tx.data(); }
-        XFER(c, d2h(c, hx, d_ox, sizeof(T) * 3 * (size_t)kept));
+        RowSpread<T> late;
+        XFER(c, fetch_rows3<T>(c, out_xyz, out_stride, d_ox, kept, late));
         if (desc) XFER(c, d2h(c, out_desc, d_od, sizeof(T) * (size_t)dr * kept));
         if (kept_idx) XFER(c, d2h(c, kept_idx, d_oi, sizeof(int32_t) * (size_t)kept));
         if (out_count) XFER(c, d2h(c, out_count, d_oc, sizeof(int32_t) * (size_t)kept));
-        HIPC(c, stream_sync(c));
-        for (size_t k = 0; k < tx.size() / 3; k++) std::memcpy(out_xyz + k * out_stride, hx + 3 * k, 3 * sizeof(T));
+        XFER(c, late.land(c));
     }
     *n_out = kept;
     return PGICP_OK;

@@ -173,7 +173,6 @@ __device__ __forceinline__ void sel_band_of(const ProblemDev &P, int second, T &
 // the correctly rounded square root in T (libpointmatcher's std::sqrt / Eigen's .norm() on the host)
 __device__ __forceinline__ float sqrt_rn_t(float v) { return __builtin_sqrtf(v); }    // (correctly rounded; __fsqrt_rn is the native 1-ulp one)
 __device__ __forceinline__ double sqrt_rn_t(double v) { return __builtin_sqrt(v); }
-constexpr int kScanChunk = 4096;   // elements per block (1024 threads x 4)
 
 __device__ __forceinline__ int block_exclusive_scan_1024(int v, int *lds /*>=17 ints*/, int &total)
 {
@@ -259,6 +258,18 @@ __global__ __launch_bounds__(1024) void k_scan_final(const int *__restrict__ in,
         ex += v[k];
     }
     if (base <= n - 1 && n - 1 < base + 4) out[n] = ex;    // the thread holding the last element
+}
+
+// Exclusive scan of in[0 .. len) into out[0 .. len]: out[len] is the total.  len >= 1 (every caller returns early on an empty
+// input).  block_sums: scan_scratch_ints(len) ints, one per block.  A block per kScanChunk elements suffices, also when len is a
+// multiple of the chunk: k_scan_final has the thread that holds element len - 1 write out[len] after its own, and a block past
+// that element would read and write nothing.
+static void launch_exclusive_scan(hipStream_t st, const int *in, int len, int *out, int *block_sums)
+{
+    const int nb = (int)scan_scratch_ints((size_t)len);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, in, len, block_sums);
+    hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, block_sums, nb);
+    hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, in, len, (const int *)block_sums, out, (int *)nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------

@@ -118,7 +118,7 @@ int launch_surface_densities(hipStream_t st, const MapDev<T> *maps, int map, int
     return 0;
 }
 
-// keep: n + 1 ints, pos: n + 1 ints (pos[n] ends up holding the number kept), block_sums: n / kScanChunk + 4 ints
+// keep: n + 1 ints, pos: n + 1 ints (pos[n] ends up holding the number kept), block_sums: scan_scratch_ints(n) ints
 template <typename T>
 void launch_max_density(hipStream_t st, const T *dens, int n, T max_density, unsigned long long seed, DensStat *stat, int *keep, int *pos,
                         int *block_sums)
@@ -128,10 +128,7 @@ void launch_max_density(hipStream_t st, const T *dens, int n, T max_density, uns
     hipLaunchKernelGGL(k_md_max<T>, dim3(cdiv(n, 256 * kMdItems)), block, 0, st, dens, n, stat);
     hipLaunchKernelGGL(k_md_count<T>, grid, block, 0, st, dens, n, stat);
     hipLaunchKernelGGL(k_md_keep<T>, grid, block, 0, st, dens, n, max_density, seed, (const DensStat *)stat, keep);
-    const int nb = cdiv(n + 1, kScanChunk);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, (const int *)keep, n, block_sums);
-    hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, block_sums, nb);
-    hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, (const int *)keep, n, (const int *)block_sums, pos, (int *)nullptr, 0);
+    launch_exclusive_scan(st, keep, n, pos, block_sums);
 }
 
 // the compaction after launch_max_density: coordinates (at `stride`, in and out), carried descriptor rows and kept indices through

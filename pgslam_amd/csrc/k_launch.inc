@@ -33,11 +33,7 @@ void launch_grid_build_batch(hipStream_t st, const BuildDesc<T> *descs, int n, l
     (void)hipMemsetAsync(occ, 0, sizeof(unsigned) * tot_o, st);
     (void)hipMemsetAsync(sc_count, 0, sizeof(int) * tot_s, st);
     hipLaunchKernelGGL(k_mbin<T>, dim3(cdiv(max_m, kBinBlock), n), dim3(kBinBlock), 0, st, descs, fkey, bins_a, arrival, cpts, cnrm);
-    const int nb = cdiv(tot_b + 1, kScanChunk);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, (const int *)bins_a, (int)(tot_b + 1), block_sums);
-    hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, block_sums, nb);
-    hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, (const int *)bins_a, (int)(tot_b + 1), (const int *)block_sums,
-                       bins_b, (int *)nullptr, 0);
+    launch_exclusive_scan(st, bins_a, (int)(tot_b + 1), bins_b, block_sums);
     const dim3 per_point(cdiv(max_m, 256), n);
     hipLaunchKernelGGL(k_mscatter<T>, per_point, dim3(256), 0, st, descs, (const int *)fkey, (const int *)bins_b, (const int *)arrival, words);
     hipLaunchKernelGGL(k_mchunk_sort<T>, kChunk == 1024 ? dim3(cdiv(max_m, 1024), n) : per_point, dim3(256), 0, st, descs, words);
@@ -47,11 +43,7 @@ void launch_grid_build_batch(hipStream_t st, const BuildDesc<T> *descs, int n, l
     (void)slot_of;
     if (sw) {
         hipLaunchKernelGGL(k_mflags<T>, per_point, dim3(256), 0, st, descs, (const int *)fkey, flag_scratch, tot_m);
-        const int nbr = cdiv(tot_m + 1, kScanChunk);          // (block_sums: the bins' scan is done with it)
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nbr), dim3(1024), 0, st, (const int *)flag_scratch, (int)(tot_m + 1), block_sums);
-        hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, block_sums, nbr);
-        hipLaunchKernelGGL(k_scan_final, dim3(nbr), dim3(1024), 0, st, (const int *)flag_scratch, (int)(tot_m + 1), (const int *)block_sums,
-                           rank_scratch, (int *)nullptr, 0);
+        launch_exclusive_scan(st, flag_scratch, (int)(tot_m + 1), rank_scratch, block_sums);     // (block_sums: the bins' scan is done with it)
         hipLaunchKernelGGL(k_mostart, dim3(cdiv(tot_m + 1, 256)), dim3(256), 0, st, (const int *)flag_scratch, (const int *)rank_scratch, tot_m, ostart);
         hipLaunchKernelGGL((k_mfill<T, true>), dim3(cdiv(max_bins, kFillGroup), n), dim3(256), 0, st, descs, (const int *)bins_b, (const int *)fkey, cell_start_f,
                            cell_start, occ, sc_count, sw, (const int *)rank_scratch);
@@ -88,11 +80,7 @@ void launch_query_sort(hipStream_t st, const ProblemDev *probs, const SrcDesc *s
     const dim3 grid(cdiv(max_n, 256), P);
     // `order` carries the arrival positions until k_qplace overwrites it with the final permutation
     hipLaunchKernelGGL(k_qbin<T>, dim3(cdiv(max_n, kBinBlock), P), dim3(kBinBlock), 0, st, probs, src, maps, rd_pre, max_rows, bin_shift, qkey, counts, order, nrm_pre);
-    const int nb = cdiv(nbins, kScanChunk);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, (const int *)counts, (int)nbins, block_sums);
-    hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, block_sums, nb);
-    hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, (const int *)counts, (int)nbins, (const int *)block_sums,
-                       qstart, (int *)nullptr, 0);
+    launch_exclusive_scan(st, counts, (int)nbins, qstart, block_sums);
     hipLaunchKernelGGL(k_qscatter, grid, dim3(256), 0, st, probs, max_rows, 3 * bin_shift, (const int *)qkey, (const int *)qstart, (const int *)order, qtmp);
     hipLaunchKernelGGL(k_qchunk_sort, kChunk == 1024 ? dim3(cdiv(max_n, 1024), P) : grid, dim3(256), 0, st, probs, qtmp);
     hipLaunchKernelGGL(k_qplace<T>, dim3(cdiv(max_n, kPlaceSpan), P), dim3(256), 0, st, probs, max_rows, 3 * bin_shift, (const int *)qstart,
@@ -447,25 +435,19 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     for (int k = 0; k < fl.n; ++k) { fl.f[k].type = types[k]; for (int j = 0; j < 8; ++j) fl.f[k].p[j] = params[8 * k + j]; }
     const dim3 grid(cdiv(n, 256)), block(256);
     hipLaunchKernelGGL(k_fill_int, dim3(cdiv(n + 1, 256)), block, 0, st, keep, n + 1, 1);
-    auto scan = [&]() {
-        const int nb = cdiv(n + 1, kScanChunk);
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, (const int *)keep, n, block_sums);
-        hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, block_sums, nb);
-        hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, (const int *)keep, n, (const int *)block_sums, pos, (int *)nullptr, 0);
-    };
     int k = 0;
     while (k < fl.n) {
         int e = k;
         while (e < fl.n && fl.f[e].type != PGICP_F_FIX_STEP && fl.f[e].type != PGICP_F_RANDOM_SAMPLING && fl.f[e].type != PGICP_F_MAX_POINT_COUNT) ++e;
         if (e > k) hipLaunchKernelGGL(k_filter_points<T>, grid, block, 0, st, feat, fstride, frows, n, fl, k, e, keep);
         if (e < fl.n) {
-            scan();
+            launch_exclusive_scan(st, keep, n, pos, block_sums);
             hipLaunchKernelGGL(k_filter_index, grid, block, 0, st, n, fl.f[e], (const int *)pos, keep);
             ++e;
         }
         k = e;
     }
-    scan();
+    launch_exclusive_scan(st, keep, n, pos, block_sums);
     Mat34 M;
     for (int i = 0; i < 12; i++) M.v[i] = T16 ? T16[i] : (i % 5 == 0 ? 1.0 : 0.0);
     hipLaunchKernelGGL(k_filter_compact<T>, grid, block, 0, st, feat, fstride, frows, desc, drows, n, (const int *)keep, (const int *)pos, M,

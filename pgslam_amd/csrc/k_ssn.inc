@@ -19,12 +19,6 @@
 //   5. the kept points are compacted in index order.
 // The arithmetic contract of kernels.hip holds (no contraction); every comparison is T's.
 
-template <typename T>
-struct SsnSeg {
-    int first, count, cut, pad;
-    T lo[3], hi[3];
-};
-struct SsnBox { int first, count, axis; };   // axis 3: the identity order (a root of at most knn points)
 
 // orderable key of a coordinate: unsigned order == T's order, -0.0 and +0.0 the same key
 template <typename T>
@@ -290,12 +284,7 @@ int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, 
     const long long n3 = 3LL * n;
     (void)hipMemsetAsync(counters, 0, 4 * sizeof(int), st);
     (void)hipMemsetAsync(w.keep, 0, sizeof(int) * (size_t)n, st);
-    auto scan = [&](const int *in, int len, int *out) {
-        const int nb = cdiv(len + 1, kScanChunk);
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, in, len, w.bsum);
-        hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, w.bsum, nb);
-        hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, in, len, (const int *)w.bsum, out, (int *)nullptr, 0);
-    };
+    auto scan = [&](const int *in, int len, int *out) { launch_exclusive_scan(st, in, len, out, w.bsum); };
     SsnBox *boxes = (SsnBox *)w.boxes;
     int *lst = w.lst[0];
     if (n <= knn) {
@@ -343,19 +332,6 @@ int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, 
                        out_nrm, ns, out_desc, kept_idx);
     (void)hipMemcpyAsync(counters + 3, w.pos + n, sizeof(int), hipMemcpyDeviceToDevice, st);
     return 0;
-}
-
-// the scratch a call of n points needs, in bytes per array (SsnScratch)
-size_t sampling_normals_scratch(int n, int elem, size_t *sizes /* [kSsnArrays] */)
-{
-    const size_t n1 = (size_t)n + 1, n3 = 3 * (size_t)n + 1;
-    const size_t seg = elem == 4 ? sizeof(SsnSeg<float>) : sizeof(SsnSeg<double>);
-    const size_t v[kSsnArrays] = {n3 * elem, n3 * elem, n3 * 4, n3 * 4, n3 * 4, n3 * 4, n3 * 4, (n3 / kScanChunk + 4) * 4,
-                                  n1 * 4, n1 * 4, n1 * 4, (n1 + 2) * seg, (n1 + 2) * seg, n1 * sizeof(SsnBox), n1 * 4, n1 * 4,
-                                  n1 * 3 * elem, n1 * 3 * elem, n1 * 4};
-    size_t total = 0;
-    for (int k = 0; k < kSsnArrays; k++) { sizes[k] = (v[k] + 255) & ~(size_t)255; total += sizes[k]; }
-    return total;
 }
 
 template int launch_sampling_normals<float>(hipStream_t, const float *, int, int, int, int, float, float, unsigned long long, const float *, int, int,

@@ -16,7 +16,6 @@
 //      while the block loads the next 512.
 // No floating-point atomics: the order of every sum is the statement's.  The arithmetic contract of kernels.hip holds.
 
-constexpr int kVoxTile = 4096;       // pairs per block of the radix passes: 256 threads x 16 rounds
 constexpr int kVoxHeavy = 64;        // a voxel of more points is summed by a block (k_vox_heavy)
 constexpr int kVoxRows = 8;          // rows one pass of k_vox_heavy stages
 
@@ -288,17 +287,6 @@ void launch_voxel_bounds(hipStream_t st, const T *X, int xs, int n, VoxStat *sta
     hipLaunchKernelGGL(k_vox_bounds<T>, dim3(nb), dim3(256), 0, st, X, xs, n, stat);
 }
 
-// the scratch of a call of n points, in bytes per array (VoxScratch)
-size_t voxel_grid_scratch(int n, size_t *sizes /* [kVoxArrays] */)
-{
-    const size_t n1 = (size_t)n + 1, nb = (size_t)cdiv(n, kVoxTile) + 1, hist = 256 * nb + 1;
-    const size_t v[kVoxArrays] = {n1 * 8, n1 * 8, n1 * 4, n1 * 4, hist * 4, hist * 4, (std::max(hist, n1) / kScanChunk + 4) * 4,
-                                  n1 * 4, n1 * 4, (n1 + 1) * 4, n1 * 4, n1 * 4, n1 * 4, n1 * sizeof(int2)};
-    size_t total = 0;
-    for (int k = 0; k < kVoxArrays; k++) { sizes[k] = (v[k] + 255) & ~(size_t)255; total += sizes[k]; }
-    return total;
-}
-
 // steps 2-5, after the host has checked the bounds and derived the grid (`bits`: the bits a key can have)
 template <typename T>
 void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<T> &g, int bits, int centroid, const T *desc, int drows, int average,
@@ -306,12 +294,7 @@ void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<
 {
     if (n <= 0) return;
     const dim3 b256(256);
-    auto scan = [&](const int *in, int len, int *out) {
-        const int nb = cdiv(len + 1, kScanChunk);
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(1024), 0, st, in, len, w.bsum);
-        hipLaunchKernelGGL(k_scan_sums_inplace, dim3(1), dim3(1024), 0, st, w.bsum, nb);
-        hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(1024), 0, st, in, len, (const int *)w.bsum, out, (int *)nullptr, 0);
-    };
+    auto scan = [&](const int *in, int len, int *out) { launch_exclusive_scan(st, in, len, out, w.bsum); };
     hipLaunchKernelGGL(k_vox_keys<T>, dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, g, w.key[0], w.idx[0]);
     int cur = 0;
     const int nt = cdiv(n, kVoxTile);

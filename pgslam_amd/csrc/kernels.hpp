@@ -111,12 +111,34 @@ template <typename T>
 void launch_unpermute(hipStream_t st, const MapDev<T> *maps, int map, const int *order, const int *slot, const T *d2, int n, int knn,
                       int *ids_out, T *d2_out);
 
-constexpr int kScanChunkHost = 4096;
+// The exclusive scan (launch_exclusive_scan, k_build.inc): elements per block (1024 threads x 4), and the ints of block sums a
+// scan of `len` elements needs -- one per block
+constexpr int kScanChunk = 4096;
+inline size_t scan_scratch_ints(size_t len) { return (len + kScanChunk - 1) / kScanChunk; }
 
-// pgicp_sampling_surface_normal_*: the device scratch of one call (sampling_normals_scratch gives the bytes of each array, in
-// this order); counters (4 ints, device): [0] boxes made, [1] boxes fused, [2] a coordinate is not finite, [3] points kept
-constexpr int kSsnArrays = 19;
+// Carves a buffer into arrays aligned to 256 bytes.  With a null base it only measures: a layout names every array once and is
+// run twice, to size the buffer and then to point into it.  (!want: the space is kept, the caller gets no pointer to it)
+struct Carve {
+    char *p;
+    size_t used = 0;
+    explicit Carve(void *base = nullptr) : p((char *)base) {}
+    template <class U> U *take(size_t count, bool want = true)
+    {
+        U *r = p && want ? (U *)(p + used) : nullptr;
+        used += (sizeof(U) * count + 255) & ~(size_t)255;
+        return r;
+    }
+};
+
+// pgicp_sampling_surface_normal_*: the device scratch of one call; counters (4 ints, device): [0] boxes made, [1] boxes fused,
+// [2] a coordinate is not finite, [3] points kept
 constexpr int kSsnMaxKnn = 1024;        // (one thread fuses a box: its loops are sequential, nothing is sized by knn)
+template <typename T>
+struct SsnSeg {
+    int first, count, cut, pad;
+    T lo[3], hi[3];
+};
+struct SsnBox { int first, count, axis; };   // axis 3: the identity order (a root of at most knn points)
 struct SsnScratch {
     void *keys[2];
     int *lst[2], *flag[2], *scan, *bsum, *seg_of[2], *side;
@@ -125,14 +147,33 @@ struct SsnScratch {
     void *bnrm, *bmean;
     int *pos;
 };
-size_t sampling_normals_scratch(int n, int elem, size_t *sizes);
+template <typename T>
+SsnScratch ssn_scratch(Carve &cv, int n)
+{
+    const size_t n1 = (size_t)n + 1, n3 = 3 * (size_t)n + 1;
+    SsnScratch w;
+    for (auto &k : w.keys) k = cv.take<T>(n3);
+    for (auto &l : w.lst) l = cv.take<int>(n3);
+    for (auto &f : w.flag) f = cv.take<int>(n3);
+    w.scan = cv.take<int>(n3);
+    w.bsum = cv.take<int>(scan_scratch_ints(n3));
+    for (auto &s : w.seg_of) s = cv.take<int>(n1);
+    w.side = cv.take<int>(n1);
+    for (auto &s : w.seg) s = cv.take<SsnSeg<T>>(n1 + 2);
+    w.boxes = cv.take<SsnBox>(n1);
+    w.keep = cv.take<int>(n1);
+    w.box_of = cv.take<int>(n1);
+    w.bnrm = cv.take<T>(3 * n1);
+    w.bmean = cv.take<T>(3 * n1);
+    w.pos = cv.take<int>(n1);
+    return w;
+}
 template <typename T>
 int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
                             const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
                             T *out_desc, int *kept_idx, int *counters);
 
 // pgicp_voxel_grid_*: the bounds and counters of a call (device), the grid the host derives from the bounds, and the scratch
-// (voxel_grid_scratch gives the bytes of each array, in this order)
 struct VoxStat {
     unsigned long long lo[3], hi[3];    // order-preserving keys of each axis's min / max (-0.0 as +0.0)
     int bad, kept, nheavy, pad;         // a coordinate is not finite; voxels (points out); voxels summed by k_vox_heavy
@@ -142,13 +183,30 @@ struct VoxGrid {
     T v[3], minB[3];
     unsigned long long nd[3];           // numDiv of each axis (< 2^31)
 };
-constexpr int kVoxArrays = 14;
+constexpr int kVoxTile = 4096;       // pairs per block of the radix passes: 256 threads x 16 rounds
 struct VoxScratch {
     unsigned long long *key[2];
     int *idx[2], *hist, *hoff, *bsum, *head, *hs, *start, *first, *vox_of, *pos;
     int2 *heavy;
 };
-size_t voxel_grid_scratch(int n, size_t *sizes);
+inline VoxScratch vox_scratch(Carve &cv, int n)
+{
+    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kVoxTile - 1) / kVoxTile + 1, hist = 256 * tiles + 1;
+    VoxScratch w;
+    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
+    for (auto &i : w.idx) i = cv.take<int>(n1);
+    w.hist = cv.take<int>(hist);
+    w.hoff = cv.take<int>(hist);
+    w.bsum = cv.take<int>(scan_scratch_ints(hist > n1 ? hist : n1));
+    w.head = cv.take<int>(n1);
+    w.hs = cv.take<int>(n1);
+    w.start = cv.take<int>(n1 + 1);
+    w.first = cv.take<int>(n1);
+    w.vox_of = cv.take<int>(n1);
+    w.pos = cv.take<int>(n1);
+    w.heavy = cv.take<int2>(n1);
+    return w;
+}
 template <typename T>
 void launch_voxel_bounds(hipStream_t st, const T *X, int xs, int n, VoxStat *stat);
 template <typename T>
@@ -161,6 +219,24 @@ struct DensStat {
     int saturated;                  // #{dens[i] == last}
     int first_nan;                  // dens[0] is a NaN: `last` is a NaN, nothing equals it
 };
+// the scratch of the filter -- keep (n + 1), pos (n + 1), the scan's block sums -- then, for a call that runs the normals kernel
+// first (`rows`), that kernel's rows in input order
+template <typename T>
+struct DensWork { int *keep, *pos, *bsum; T *nrm, *eig, *dens; };
+template <typename T>
+DensWork<T> dens_scratch(Carve &cv, int n, bool rows)
+{
+    DensWork<T> w{};
+    w.keep = cv.take<int>((size_t)n + 1);
+    w.pos = cv.take<int>((size_t)n + 1);
+    w.bsum = cv.take<int>(scan_scratch_ints(n));
+    if (rows) {
+        w.nrm = cv.take<T>(3 * (size_t)n);
+        w.eig = cv.take<T>(3 * (size_t)n);
+        w.dens = cv.take<T>((size_t)n);
+    }
+    return w;
+}
 template <typename T>
 int launch_surface_densities(hipStream_t st, const MapDev<T> *maps, int map, int m, int knn, T max_dist, T eps_rank, T *out_nrm,
                              int out_stride, T *out_eig, T *out_dens);

@@ -160,9 +160,7 @@ void pgicp_ctx_destroy(pgicp_ctx *c)
         if (c->up[s].uploaded) (void)hipEventDestroy(c->up[s].uploaded);
         if (c->up[s].consumed) (void)hipEventDestroy(c->up[s].consumed);
     }
-    c->ssn_work.release(); c->ssn_io.release(); c->ssn_cnt.release();
-    c->vox_work.release(); c->vox_io.release(); c->vox_stat.release();
-    c->dens_work.release(); c->dens_io.release(); c->dens_stat.release();
+    c->dpf_work.release(); c->dpf_io.release(); c->dpf_stat.release();
     c->noise.vals.release(); c->noise.off_dev.release(); c->noise.dist.release(); c->noise.out.release();
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto &m : c->f32.maps) free_map<float>(nullptr, m);

@@ -759,6 +759,62 @@ def run_voxel(ctx, aux, dtype):
             "c.xyz": r2["xyz"], "c.kept_idx": r2["kept_idx"], "c.count": r2["count"]}
 
 
+# the densities and MaxDensity (include/pgicp_density.h), at surface_normals' size; the references of tests/test_gpu_density.py
+DENS_KNN, DENS_SEED = 10, 5
+
+
+def _dens_cloud(dtype):
+    return np.ascontiguousarray(two_scans()["ref_xyz"][:4000].astype(dtype))
+
+
+def _densities_oracle(out, oracles, dtype):
+    o, xyz = _orc(oracles, dtype), _dens_cloud(dtype)
+    assert same_bits(out["densities"], o.densities(xyz, o.surface_normals(xyz, DENS_KNN)["ids"]))
+
+
+@case("surface_densities", ["pgicp_surface_densities*"], oracle=_densities_oracle, dtypes=(F32, F64))
+def run_surface_densities(ctx, aux, dtype):
+    set_chain(ctx)
+    r = ctx.surface_densities(_dens_cloud(dtype), knn=DENS_KNN, dtype=dtype)
+    return {"normals": r["normals"], "eigen_values": r["eigen_values"], "densities": r["densities"]}
+
+
+def _max_density_oracle(out, oracles, dtype):
+    sfx = "_f32" if dtype == F32 else "_f64"
+    dens = oracles[2]("surface_densities" + sfx)["densities"]           # (that case is checked against the oracle)
+    md = float(np.median(dens))
+    keep = np.flatnonzero(_orc(oracles, dtype).max_density_keep(dens, max_density=md, seed=DENS_SEED)).astype(np.int32)
+    assert float(out["md"]) == md and 0 < len(keep) < len(dens) and np.array_equal(out["kept_idx"], keep)
+
+
+@case("max_density", ["pgicp_max_density*", "pgicp_surface_densities*"], oracle=_max_density_oracle, dtypes=(F32, F64))
+def run_max_density(ctx, aux, dtype):
+    set_chain(ctx)
+    dens = ctx.surface_densities(_dens_cloud(dtype), knn=DENS_KNN, dtype=dtype, want_normals=False, want_eigen=False)["densities"]
+    md = float(np.median(dens))
+    return {"md": np.array(md), "kept_idx": ctx.max_density(dens, max_density=md, seed=DENS_SEED)}
+
+
+def _normals_max_density_oracle(out, oracles, dtype):
+    """tests/test_gpu_density.py::fused_equals_stages: the fused call's rows are the stage calls' rows of the kept points"""
+    sfx = "_f32" if dtype == F32 else "_f64"
+    st, keep = oracles[2]("surface_densities" + sfx), oracles[2]("max_density" + sfx)["kept_idx"]
+    xyz = _dens_cloud(dtype)
+    assert np.array_equal(out["kept_idx"], keep) and same_bits(out["xyz"], xyz[keep])
+    for k in ("normals", "eigen_values", "densities"):
+        assert same_bits(out[k], st[k][keep]), k
+    assert same_bits(out["descriptors"], two_scans()["ref_nrm"][:4000].astype(dtype)[keep])
+
+
+@case("normals_max_density", ["pgicp_normals_max_density*"], oracle=_normals_max_density_oracle, dtypes=(F32, F64))
+def run_normals_max_density(ctx, aux, dtype):
+    set_chain(ctx)
+    xyz = _dens_cloud(dtype)
+    md = float(np.median(ctx.surface_densities(xyz, knn=DENS_KNN, dtype=dtype, want_normals=False, want_eigen=False)["densities"]))
+    r = ctx.normals_max_density(xyz, knn=DENS_KNN, max_density=md, seed=DENS_SEED, descriptors=two_scans()["ref_nrm"][:4000].astype(dtype), dtype=dtype)
+    return {k: np.ascontiguousarray(r[k]) for k in ("xyz", "normals", "eigen_values", "densities", "descriptors", "kept_idx")}
+
+
 FILTERS = [(icp.FILTER_MIN_DIST, 1.0, 0), (icp.FILTER_MAX_DIST, 40.0, 0), (icp.FILTER_BOUNDING_BOX, -2.0, -1.0, -5.0, 0.5, 1.0, 5.0, 1),
            (icp.FILTER_RANDOM_SAMPLING, 0.9, 7)]
 
@@ -1069,6 +1125,13 @@ EXCLUDED = {
 
 def reached():
     return sorted({a for c in CASES.values() for a in c.api})
+
+
+def declared():
+    """the entry points the catalogue answers for: what include/pgicp.h and include/pgicp_density.h declare"""
+    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("pgicp.h", "pgicp_density.h"))
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"\b(pgicp_[a-z0-9_]+)\s*\(", src)))
 
 
 ERROR_CASES = [n for n, c in CASES.items() if c.error]

@@ -107,6 +107,18 @@ def test_max_density_against_the_oracle(ctx, oracle32, oracle64, dense_clouds, T
     assert len(ctx.max_density(np.zeros(0, dtype=T))) == 0
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8192, 4_194_305])
+def test_kept_indices_at_the_edges_of_the_scan(ctx, oracle32, n):
+    """kept_idx comes out of the three-launch exclusive scan (launch_exclusive_scan), which has no entry point of its own: a
+    chunk of 4096 elements less one, exactly, plus one, two chunks, and one element past 1024 chunks, where the scan of the
+    block sums carries into its second trip.  (n = 1: `one_above` / `one_below` of density_arrays.)  Roughly half the points
+    are kept: a fifth lies below maxDensity, a denser point stays with probability maxDensity / density."""
+    dens = np.random.default_rng(n).uniform(1.0, 100.0, n).astype(np.float32)
+    want = check_max_density(ctx, oracle32, dens, 20.0, 3, f"n={n}")
+    assert 0.4 * n < len(want) < 0.6 * n
+
+
 def fused_equals_stages(ctx, xyz, T, knn, md, seed, desc, device):
     import torch
     to = (lambda a: torch.from_numpy(a).cuda()) if device else (lambda a: a)

@@ -102,13 +102,11 @@ def test_baseline_against_the_oracle(oracle32, oracle64, name):
 def test_every_case_calls_what_it_declares():
     """tests/test_history_catalogue.py counts an entry point as reached where a case DECLARES it: here every declaration is held
     against what the case looked up on the library during its baseline run, and the header's list against the union of it"""
-    import re
     for name, c in CASES.items():
         baseline(name)
         missing = set(c.api) - _CALLED[name]
         assert not missing, f"{name} declares {sorted(missing)} and does not call them"
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pgicp.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(pgicp_[a-z0-9_]+)\s*\(", src))
+    declared = set(hc.declared())
     called = set().union(*(_CALLED[n] for n in CASES))
     assert not declared - called - set(hc.EXCLUDED), sorted(declared - called - set(hc.EXCLUDED))
 
@@ -501,6 +499,15 @@ def test_an_error_exit_followed_by_ordinary_calls(walk, err):
 def test_scratch_grown_by_the_largest_case_serves_the_smallest(walk):
     for name in ("align_batch_8big_f32", "outlier_weights_trimmed_f32", "align_batch_8big_f32", "transform_f32", "align_batch_4big_f64",
                  "match_knn1_brute_f32"):
+        walk.step(name)
+
+
+@gpu
+def test_the_filter_families_share_their_scratch(walk):
+    """SamplingSurfaceNormal, VoxelGrid and the densities carve the same three buffers: every call lays out what another family's
+    call left behind -- the largest layout first, then smaller ones of the other families, both precisions"""
+    for name in ("sampling_surface_normal_f64", "max_density_f32", "voxel_grid_f64", "normals_max_density_f32", "surface_densities_f64",
+                 "voxel_grid_f32", "sampling_surface_normal_f32", "normals_max_density_f64"):
         walk.step(name)
 
 

@@ -1,22 +1,13 @@
-"""The catalogue of tests/history_cases.py reaches every entry point include/pgicp.h declares, or names it in an exclusion list
+"""The catalogue of tests/history_cases.py reaches every entry point include/pgicp.h and include/pgicp_density.h declare, or names it in an exclusion list
 with a reason.  The exclusion list holds administrative entry points only -- nothing that computes on a cloud.  (No GPU needed:
 the header is parsed the way tests/test_abi.py parses it; tests/test_gpu_history.py runs the cases.)"""
-import os
 import re
 
 import history_cases as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared():
-    src = open(os.path.join(ROOT, "include", "pgicp.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pgicp_[a-z0-9_]+)\s*\(", src)))
-
 
 def test_every_declared_entry_point_is_reached_or_excluded_with_a_reason():
-    declared = set(_declared())
+    declared = set(hc.declared())
     reached, excluded = set(hc.reached()), set(hc.EXCLUDED)
     assert not declared - reached - excluded, sorted(declared - reached - excluded)
     assert not (reached | excluded) - declared, sorted((reached | excluded) - declared)           # no stale names
@@ -25,7 +16,7 @@ def test_every_declared_entry_point_is_reached_or_excluded_with_a_reason():
 
 
 def test_nothing_that_computes_on_a_cloud_is_excluded():
-    compute = re.compile(r"align|icp_pair|match|outlier|error_stats|partial_chain|transform|build_local_map|normal|voxel|filter|upload|"
+    compute = re.compile(r"align|icp_pair|match|outlier|error_stats|partial_chain|transform|build_local_map|normal|voxel|densit|filter|upload|"
                          r"map_create|map_set_values|map_transfer|map_destroy|map_size|var_trim|set_params|reading_order|last_matches")
     assert not [n for n in hc.EXCLUDED if compute.search(n)]
 
