@@ -29,6 +29,8 @@
 #include "../pgicp.h"
 #include "../pgicp_noise.h"
 #include "../pgicp_density.h"
+#include "../pgicp_covsample.h"
+#include "covsample_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -155,6 +157,8 @@ template <> struct Abi<float> {
     static int sampling_normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const float *d, int dr, int avg,
                                 float *ox, float *on, float *od, int32_t *idx, int *n_out)
     { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
+    static int covariance_sampling(pgicp_ctx *c, const float *x, int xs, const float *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
+    { return pgicp_covariance_sampling_f32(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
     static int voxel_grid(pgicp_ctx *c, const float *x, int xs, int n, const double *v, int cen, const float *d, int dr, int avg, float *ox, float *od, int32_t *idx, int *n_out)
     { return pgicp_voxel_grid_f32(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
     static int partial(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
@@ -195,6 +199,8 @@ template <> struct Abi<double> {
     static int sampling_normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const double *d, int dr, int avg,
                                 double *ox, double *on, double *od, int32_t *idx, int *n_out)
     { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
+    static int covariance_sampling(pgicp_ctx *c, const double *x, int xs, const double *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
+    { return pgicp_covariance_sampling_f64(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
     static int voxel_grid(pgicp_ctx *c, const double *x, int xs, int n, const double *v, int cen, const double *d, int dr, int avg, double *ox, double *od, int32_t *idx, int *n_out)
     { return pgicp_voxel_grid_f64(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
     static int partial(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
@@ -939,6 +945,87 @@ struct PointMatcher {
             hostFilter(c);
         }
     };
+    //! [EXT] CovarianceSamplingDataPointsFilter{nbSample, torqueNorm} (DataPointsFilters/CovarianceSampling.cpp): the stability
+    //! sampler of Gelfand et al. 2003 -- the nbSample points that best constrain the six degrees of freedom of the point-to-plane
+    //! solve, in pick order.  Needs the `normals` descriptor.  The statement, with its marked deviations, is in
+    //! include/pgicp_covsample.h.  3-D clouds only.  On the device (pgicp_covariance_sampling_*) when there is one, unless
+    //! PGSLAM_HOST_INPUT_STAGE=1; else the host form of the same statement (covsample_host.hpp): the same picks bit for bit given
+    //! the same frame -- the host form sums its frame in index order, the device in a tree, so the two frames may differ in
+    //! their last bits.  No deviceSpec: a chain that holds it takes the per-filter path (the picks come in pick order,
+    //! pgicp_filter_cloud only drops points).  ranOnDevice(): which of the two the last inPlaceFilter took; lastFrame: its frame.
+    struct CovarianceSamplingDataPointsFilter : DataPointsFilter {
+        enum TorqueNormMethod { L1 = 0, Lavg = 1, Lmax = 2 };
+        std::size_t nbSample; TorqueNormMethod normalizationMethod;
+        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
+        bool onDevice = false;
+        pgicp_cov_frame lastFrame{};
+        std::vector<int32_t> idxBuf;
+        explicit CovarianceSamplingDataPointsFilter(std::size_t nb = 5000, int torqueNorm = 1) : nbSample(nb), normalizationMethod((TorqueNormMethod)torqueNorm)
+        {
+            if (nb < 1 || nb > 2147483647u) throw std::runtime_error("CovarianceSamplingDataPointsFilter: nbSample must be in [1, INT_MAX]");
+            if (torqueNorm < 0 || torqueNorm > 2) throw std::runtime_error("CovarianceSamplingDataPointsFilter: torqueNorm must be 0 (L = 1), 1 (Lavg) or 2 (Lmax)");
+        }
+        CovarianceSamplingDataPointsFilter(const CovarianceSamplingDataPointsFilter &) = delete;
+        CovarianceSamplingDataPointsFilter &operator=(const CovarianceSamplingDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        static bool deviceWanted()
+        {
+            const char *knob = std::getenv("PGSLAM_HOST_INPUT_STAGE");
+            static const bool have_device = pgicp_device_count() > 0;
+            return have_device && !(knob && std::strcmp(knob, "1") == 0);
+        }
+        //! the columns idx[0 .. kept), in that order (features and descriptors)
+        static void gatherColumns(DataPoints &c, const int32_t *idx, int kept)
+        {
+            const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            Matrix f(frows, kept), d(drows, kept);
+            for (int o = 0; o < kept; o++) {
+                const int i = idx[o];
+                for (int r = 0; r < frows; r++) f(r, o) = c.features(r, i);
+                for (int r = 0; r < drows; r++) d(r, o) = c.descriptors(r, i);
+            }
+            c.features = f;
+            c.descriptors = d;
+        }
+        //! the picks of the host form given a frame (nbSample < the cloud's size)
+        void hostPicks(const DataPoints &c, const pgicp_cov_frame &frame, std::vector<int32_t> &picks) const
+        {
+            const int rn = c.getDescriptorStartingRow("normals");
+            pgslam_amd::covsample::host_select<T>((int)c.features.cols(), [&](int i, int a) { return c.features(a, i); },
+                                                  [&](int i, int a) { return c.descriptors(rn + a, i); }, (int)nbSample, frame, picks);
+        }
+        void hostFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), rn = c.getDescriptorStartingRow("normals");
+            if (!pgslam_amd::covsample::host_frame<T>(n, [&](int i, int a) { return c.features(a, i); }, [&](int i, int a) { return c.descriptors(rn + a, i); },
+                                                      (int)normalizationMethod, lastFrame))
+                throw std::runtime_error("CovarianceSamplingDataPointsFilter: a coordinate or a normal component is NaN or infinite, or every point lies at the mean "
+                                         "(put a RemoveNaNDataPointsFilter ahead of it)");
+            std::vector<int32_t> picks;
+            hostPicks(c, lastFrame, picks);
+            gatherColumns(c, picks.data(), (int)picks.size());
+        }
+        void deviceFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            const int rn = c.getDescriptorStartingRow("normals");
+            if (idxBuf.size() < nbSample) idxBuf.resize(nbSample);
+            int kept = 0;
+            check(ctx, pgslam_amd::Abi<T>::covariance_sampling(ctx, c.features.data(), frows, c.descriptors.data() + rn, drows, n, (int)nbSample,
+                                                               (int)normalizationMethod, idxBuf.data(), &kept, &lastFrame));
+            gatherColumns(c, idxBuf.data(), kept);
+        }
+        void inPlaceFilter(DataPoints &c) override
+        {
+            onDevice = false;
+            if (!c.descriptorExists("normals") || c.getDescriptorDimension("normals") != 3)
+                throw std::runtime_error("CovarianceSamplingDataPointsFilter: Error, cannot find normals in descriptors.");
+            if (c.features.rows() != 4) throw std::runtime_error("CovarianceSamplingDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            if ((std::size_t)c.features.cols() <= nbSample) return;                 // the no-op: the cloud as it is
+            if (deviceWanted()) { deviceFilter(c); onDevice = true; return; }
+            hostFilter(c);
+        }
+    };
     //! [EXT] MaxDensityDataPointsFilter{maxDensity} (DataPointsFilters/MaxDensity.cpp): needs the `densities` descriptor
     //! (SurfaceNormalDataPointsFilter{keepDensities: 1}); keeps a point at or below maxDensity, a denser one with probability
     //! maxDensity / density -- times (1 - nbSaturatedPts / nbPointsIn) in INTEGER arithmetic for points at the cloud's largest
@@ -1140,6 +1227,14 @@ struct PointMatcher {
                         if (!(vs > 0.0) || !std::isfinite(vs) || !((T)vs > T(0)) || !std::isfinite((T)vs))
                             throw std::runtime_error(m.name + ": vSizeX, vSizeY and vSizeZ must be finite and > 0");
                     this->push_back(std::make_shared<VoxelGridDataPointsFilter>((T)vx, (T)vy, (T)vz, get("useCentroid") != 0.0, get("averageExistingDescriptors") != 0.0));
+                } else if (m.name == "CovarianceSamplingDataPointsFilter") {
+                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
+                    for (auto &kv : m.params)
+                        if (kv.first != "nbSample" && kv.first != "torqueNorm") throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    const double nb = get("nbSample", "5000"), tn = get("torqueNorm", "1");
+                    if (!(nb >= 1.0 && nb <= 2147483647.0) || nb != std::floor(nb) || (tn != 0.0 && tn != 1.0 && tn != 2.0))
+                        throw std::runtime_error(m.name + ": nbSample must be an integer in [1, INT_MAX], torqueNorm 0, 1 or 2");
+                    this->push_back(std::make_shared<CovarianceSamplingDataPointsFilter>((std::size_t)nb, (int)tn));
                 } else if (m.name == "MaxDensityDataPointsFilter") {
                     auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double md = get("maxDensity", "10"), seed = get("seed", "1");
@@ -1185,7 +1280,7 @@ struct PointMatcher {
                 } else
                     throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name +
                                              "' (supported: Identity, MinDist, MaxDist, BoundingBox, RemoveNaN, SurfaceNormal, "
-                                             "SamplingSurfaceNormal, VoxelGrid, MaxDensity, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
+                                             "SamplingSurfaceNormal, VoxelGrid, MaxDensity, CovarianceSampling, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
                                              "(seeded samplers, not rand()-parity))");
             }
         }

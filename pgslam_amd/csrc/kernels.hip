@@ -192,5 +192,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_voxel.inc"
 #include "k_noise.inc"
 #include "k_density.inc"
+#include "k_covsample.inc"
 
 }  // namespace pgicp

@@ -248,4 +248,54 @@ void launch_density_compact(hipStream_t st, int n, const int *keep, const int *p
                             const T *nrm, const T *eig, const T *dens, T *out_xyz, T *out_desc, T *out_nrm, int out_nstride, T *out_eig,
                             T *out_dens, int *kept_idx);
 
+// include/pgicp_covsample.h (k_covsample.inc): CovarianceSamplingDataPointsFilter
+constexpr int kCovBlocks = 1024;        // the most blocks of a frame reduction: one row of partials each
+constexpr int kCovSums = 21;            // the distinct sums of C; no reduction carries more values
+struct CovStat {
+    double r1[10];                      // pass 1 folded: coordinate sums, #non-finite points, -min and max of each axis
+    double nsum;                        // pass 2 folded: the sum of the norms
+    double sums[kCovSums];              // pass 3 folded: C's upper triangle, row-major
+    double c[3], L, inv;                // the centre, L and T(1) / L: values of T
+    unsigned long long prefix[6];       // the selection: each list's key prefix so far, in the end the threshold key
+    int rank[6];                        // ... and the rank sought among the keys under the prefix, in the end the ties to take
+    int cursor[6];                      // candidates emitted into each list
+    int bad, pad;                       // an input of the values pass is not finite
+};
+template <typename T>
+struct CovFrameDev { T c[3], inv, X[36]; };     // X column-major
+struct CovScratch {
+    double *part;                       // kCovBlocks rows of at most kCovSums doubles
+    void *v;                            // n x 6 values of T
+    int *hist, *eq, *pos, *bsum;        // passes x 6 x 256 counts; the tie flags [list][point], their scan, its block sums
+    int *cand_idx; void *cand_v;        // [list][m] indices, [list][m][6] values of T
+    int *picks;                         // m
+};
+// n points, m = min(n, nbSample) candidates a list
+template <typename T>
+CovScratch cov_scratch(Carve &cv, int n, int m)
+{
+    const size_t n6 = 6 * (size_t)n;
+    CovScratch w;
+    w.part = cv.take<double>((size_t)kCovBlocks * kCovSums);
+    w.v = cv.take<T>(n6);
+    w.hist = cv.take<int>(sizeof(T) * 6 * 256);
+    w.eq = cv.take<int>(n6 + 1);
+    w.pos = cv.take<int>(n6 + 2);
+    w.bsum = cv.take<int>(scan_scratch_ints(n6));
+    w.cand_idx = cv.take<int>(6 * (size_t)m);
+    w.cand_v = cv.take<T>(36 * (size_t)m);
+    w.picks = cv.take<int>((size_t)m);
+    return w;
+}
+// passes 1-3 and their folds: CovStat's r1, nsum, sums, c, L, inv (stat zeroed by the caller)
+template <typename T>
+void launch_cov_frame(hipStream_t st, const T *X, int xs, const T *N, int ns, int n, int torque_norm, const CovScratch &w, CovStat *stat);
+// pass 4: the values, each list's first m entries (unordered) into cand_idx / cand_v
+template <typename T>
+void launch_cov_select(hipStream_t st, const T *X, int xs, const T *N, int ns, int n, const CovFrameDev<T> &F, int m, const CovScratch &w, CovStat *stat);
+// pass 5: out[j] = in[picks[j]] (picks == null: the identity); any output may be null
+template <typename T>
+void launch_cov_gather(hipStream_t st, const int *picks, int m, int n, const T *X, int xs, const T *N, int ns, const T *desc, int drows, T *out_xyz,
+                       int os, T *out_nrm, int ons, T *out_desc, int *kept_idx);
+
 }  // namespace pgicp

@@ -7,6 +7,8 @@
 #include "pgicp.h"
 #include "pgicp_noise.h"
 #include "pgicp_density.h"
+#include "pgicp_covsample.h"
+#include "pgslam_amd/covsample_host.hpp"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -38,6 +40,7 @@ using namespace pgicp;
 #include "api_sampling.inc"           // pgicp_sampling_surface_normal_* (SamplingSurfaceNormalDataPointsFilter)
 #include "api_voxel.inc"              // pgicp_voxel_grid_* (VoxelGridDataPointsFilter)
 #include "api_density.inc"            // pgicp_surface_densities_*, pgicp_max_density_*, pgicp_normals_max_density_* (pgicp_density.h)
+#include "api_covsample.inc"          // pgicp_covariance_sampling_*, pgicp_covariance_sampling_framed_* (pgicp_covsample.h)
 
 extern "C" {
 

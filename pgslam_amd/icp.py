@@ -67,6 +67,11 @@ DENSITY_SYMBOLS = (
     "pgicp_surface_densities_f32", "pgicp_surface_densities_f64", "pgicp_max_density_f32", "pgicp_max_density_f64",
     "pgicp_normals_max_density_f32", "pgicp_normals_max_density_f64",
 )
+# every symbol the companion header include/pgicp_covsample.h declares (checked by tests/test_covariance_sampling_host.py)
+COVSAMPLE_SYMBOLS = (
+    "pgicp_covariance_sampling_f32", "pgicp_covariance_sampling_f64",
+    "pgicp_covariance_sampling_framed_f32", "pgicp_covariance_sampling_framed_f64",
+)
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -103,6 +108,24 @@ class Filter(C.Structure):
 
 FILTER_IDENTITY, FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_REMOVE_NAN, FILTER_FIX_STEP, FILTER_RANDOM_SAMPLING, \
     FILTER_MAX_POINT_COUNT = range(8)
+
+
+class CovFrame(C.Structure):
+    """pgicp_cov_frame (include/pgicp_covsample.h); basis is column-major"""
+    _fields_ = [("center", C.c_double * 3), ("L", C.c_double), ("eigenvalues", C.c_double * 6), ("basis", C.c_double * 36)]
+
+    def as_dict(self):
+        return dict(center=np.array(self.center[:]), L=float(self.L), eigenvalues=np.array(self.eigenvalues[:]),
+                    basis=np.array(self.basis[:]).reshape(6, 6).T.copy())
+
+    @classmethod
+    def from_dict(cls, d):
+        f = cls()
+        f.center[:] = [float(x) for x in d["center"]]
+        f.L = float(d["L"])
+        f.eigenvalues[:] = [float(x) for x in d.get("eigenvalues", np.zeros(6))]
+        f.basis[:] = [float(x) for x in np.asarray(d["basis"], dtype=np.float64).reshape(6, 6).T.ravel()]
+        return f
 
 
 class Edge(C.Structure):
@@ -1030,6 +1053,62 @@ class Context:
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], eigen_values=oe[:k], densities=od[:k],
                     descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k])
+
+    # ---- CovarianceSampling (include/pgicp_covsample.h) ------------------------
+    def covariance_sampling(self, xyz, normals, nb_sample=5000, torque_norm=1, descriptors=None, dtype=None, frame=None):
+        """CovarianceSamplingDataPointsFilter on the device (pgicp_covariance_sampling_*, statement in include/pgicp_covsample.h).
+        numpy in -> numpy out, torch CUDA in -> torch CUDA out.  `normals` (n, >= 3) and `descriptors` ((n, drows) or None) in the
+        same memory as xyz.  Returns dict(xyz (k,3), normals (k,3), descriptors (k,drows) or None, kept_idx (k,) int32, frame) for
+        the k = min(n, nb_sample) picks, in pick order; frame = dict(center (3,), L, eigenvalues (6,) ascending, basis (6,6):
+        eigenvectors as columns).  `frame` given: the selection stage alone (pgicp_covariance_sampling_framed_*) -- kept_idx is
+        the stage's, the rows are gathered from it here, the frame comes back as given."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+            normals = np.zeros((1, 3), dtype=xyz.dtype)[:0]
+        x = _Buf(xyz, dtype)
+        nb = _Buf(normals, x.dtype if x.mem == HOST else None)
+        n = x.n
+        assert nb.n == n and nb.mem == x.mem and nb.dtype == x.dtype
+        d = None
+        drows = 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
+                assert d.ndim == 2 and d.shape[0] == n
+            drows = int(d.shape[1])
+        m = max(min(n, int(nb_sample)), 1)
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape, dt=None: torch.empty(shape, dtype=dt or xyz.dtype, device=xyz.device)
+            oi = mk((m,), torch.int32)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            mk = lambda shape: np.empty(shape, dtype=x.dtype)
+            oi = np.empty(m, dtype=np.int32)
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        n_out = C.c_int(0)
+        if frame is not None:
+            fr = CovFrame.from_dict(frame)
+            fn = getattr(self.lib, "pgicp_covariance_sampling_framed" + self._sfx(x.dtype))
+            self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
+                           C.c_int(int(nb_sample)), C.byref(fr), ptr(oi), C.byref(n_out)))
+            k = n_out.value
+            idx = oi[:k]
+            sel = idx.long() if x.mem == DEVICE else idx
+            return dict(xyz=x.keep[sel][:, :3], normals=nb.keep[sel][:, :3], descriptors=d[sel] if d is not None else None, kept_idx=idx,
+                        frame=fr.as_dict())
+        ox, on = mk((m, x.stride)), mk((m, 3))
+        oc = mk((m, drows)) if d is not None else None
+        fr = CovFrame()
+        fn = getattr(self.lib, "pgicp_covariance_sampling" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
+                       C.c_int(int(nb_sample)), C.c_int(int(torque_norm)), ptr(d), C.c_int(drows), ptr(ox), ptr(on), C.c_int(3), ptr(oc), ptr(oi),
+                       C.byref(n_out), C.byref(fr)))
+        k = n_out.value
+        return dict(xyz=ox[:k, :3], normals=on[:k], descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k], frame=fr.as_dict())
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
