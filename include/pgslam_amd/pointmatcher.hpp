@@ -31,6 +31,8 @@
 #include "../pgicp_density.h"
 #include "../pgicp_covsample.h"
 #include "covsample_host.hpp"
+#include "../pgicp_octree.h"
+#include "octree_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -159,6 +161,8 @@ template <> struct Abi<float> {
     { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
     static int covariance_sampling(pgicp_ctx *c, const float *x, int xs, const float *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pgicp_covariance_sampling_f32(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
+    static int octree_grid(pgicp_ctx *c, const float *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const float *d, int dr, float *ox, float *od, int32_t *idx, int *n_out)
+    { return pgicp_octree_grid_f32(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
     static int voxel_grid(pgicp_ctx *c, const float *x, int xs, int n, const double *v, int cen, const float *d, int dr, int avg, float *ox, float *od, int32_t *idx, int *n_out)
     { return pgicp_voxel_grid_f32(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
     static int partial(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
@@ -201,6 +205,8 @@ template <> struct Abi<double> {
     { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
     static int covariance_sampling(pgicp_ctx *c, const double *x, int xs, const double *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pgicp_covariance_sampling_f64(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
+    static int octree_grid(pgicp_ctx *c, const double *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const double *d, int dr, double *ox, double *od, int32_t *idx, int *n_out)
+    { return pgicp_octree_grid_f64(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
     static int voxel_grid(pgicp_ctx *c, const double *x, int xs, int n, const double *v, int cen, const double *d, int dr, int avg, double *ox, double *od, int32_t *idx, int *n_out)
     { return pgicp_voxel_grid_f64(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
     static int partial(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
@@ -1026,6 +1032,66 @@ struct PointMatcher {
             hostFilter(c);
         }
     };
+    //! [EXT] OctreeGridDataPointsFilter{maxPointByNode, maxSizeByNode, samplingMethod, buildParallel} (DataPointsFilters/
+    //! OctreeGrid.cpp): one point per non-empty leaf of an octree over the cloud -- the leaf's first point (0), a seeded random one
+    //! (1), its centroid (2: descriptors averaged, further feature rows the first point's) or its medoid (3) -- in depth-first leaf
+    //! order.  The statement, with its marked deviations, is in include/pgicp_octree.h.  3-D clouds only.  On the device
+    //! (pgicp_octree_grid_*, the same bits) when there is one, unless PGSLAM_HOST_INPUT_STAGE=1; else the host form of the same
+    //! statement (octree_host.hpp).  No deviceSpec: a chain that holds it takes the per-filter path (it reorders points).
+    //! `seed` (method 1) is a build-owned extra parameter, as RandomSampling's.  From YAML maxPointByNode or maxSizeByNode must be
+    //! given (neither: the defaults keep every distinct point, refused as an omission).  ranOnDevice(): which of the two the last
+    //! inPlaceFilter took.
+    struct OctreeGridDataPointsFilter : DataPointsFilter {
+        enum SamplingMethod { FIRST_PTS = 0, RAND_PTS = 1, CENTROID = 2, MEDOID = 3 };
+        std::size_t maxPointByNode; T maxSizeByNode; SamplingMethod samplingMethod; bool buildParallel; unsigned long long seed;
+        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
+        bool onDevice = false;
+        std::vector<T> oxBuf, odBuf;                 // the device form's outputs, kept from call to call
+        std::vector<int32_t> idxBuf;
+        explicit OctreeGridDataPointsFilter(std::size_t maxPts = 1, T maxSize = T(0), int method = 0, bool parallel = true, unsigned long long seed_ = 1)
+            : maxPointByNode(maxPts), maxSizeByNode(maxSize), samplingMethod((SamplingMethod)method), buildParallel(parallel), seed(seed_)
+        {
+            if (maxPts < 1 || maxPts > 2147483647u) throw std::runtime_error("OctreeGridDataPointsFilter: maxPointByNode must be in [1, INT_MAX]");
+            if (!(maxSize >= T(0)) || !std::isfinite(maxSize)) throw std::runtime_error("OctreeGridDataPointsFilter: maxSizeByNode must be finite and >= 0");
+            if (method < 0 || method > 3) throw std::runtime_error("OctreeGridDataPointsFilter: samplingMethod must be 0 (first), 1 (random), 2 (centroid) or 3 (medoid)");
+            if (seed_ >= (1ULL << 53)) throw std::runtime_error("OctreeGridDataPointsFilter: seed must be in [0, 2^53)");
+        }
+        OctreeGridDataPointsFilter(const OctreeGridDataPointsFilter &) = delete;
+        OctreeGridDataPointsFilter &operator=(const OctreeGridDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        void deviceFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            if (oxBuf.size() < 3 * (size_t)n) oxBuf.resize(3 * (size_t)n);
+            if (odBuf.size() < (size_t)drows * n) odBuf.resize((size_t)drows * n);
+            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            int kept = 0;
+            const int st = pgslam_amd::Abi<T>::octree_grid(ctx, c.features.data(), frows, n, (int)maxPointByNode, (double)maxSizeByNode, (int)samplingMethod, seed,
+                                                           drows > 0 ? c.descriptors.data() : nullptr, drows, oxBuf.data(), drows > 0 ? odBuf.data() : nullptr,
+                                                           idxBuf.data(), &kept);
+            if (st == PGICP_ERR_ARG)
+                throw std::runtime_error("OctreeGridDataPointsFilter: a coordinate is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
+            check(ctx, st);
+            VoxelGridDataPointsFilter::assemble(c, oxBuf.data(), odBuf.data(), idxBuf.data(), kept);
+        }
+        void hostFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), drows = (int)c.descriptors.rows();
+            pgslam_amd::octree::Result<T> res;
+            if (!pgslam_amd::octree::host_filter<T>(n, [&](int i, int a) { return c.features(a, i); }, drows, [&](int i, int r) { return c.descriptors(r, i); },
+                                                    (int)maxPointByNode, maxSizeByNode, (int)samplingMethod, seed, res))
+                throw std::runtime_error("OctreeGridDataPointsFilter: a coordinate is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
+            VoxelGridDataPointsFilter::assemble(c, res.xyz.data(), res.desc.data(), res.kept.data(), (int)res.kept.size());
+        }
+        void inPlaceFilter(DataPoints &c) override
+        {
+            onDevice = false;
+            if (c.features.rows() != 4) throw std::runtime_error("OctreeGridDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            if (c.features.cols() == 0) return;
+            if (CovarianceSamplingDataPointsFilter::deviceWanted()) { deviceFilter(c); onDevice = true; return; }
+            hostFilter(c);
+        }
+    };
     //! [EXT] MaxDensityDataPointsFilter{maxDensity} (DataPointsFilters/MaxDensity.cpp): needs the `densities` descriptor
     //! (SurfaceNormalDataPointsFilter{keepDensities: 1}); keeps a point at or below maxDensity, a denser one with probability
     //! maxDensity / density -- times (1 - nbSaturatedPts / nbPointsIn) in INTEGER arithmetic for points at the cloud's largest
@@ -1178,6 +1244,12 @@ struct PointMatcher {
             const auto chain = pgslam_amd::yaml_lite::parse(ss);
             if (chain.has("filters")) load(chain.sections.at("filters"));
         }
+        static std::string supportedNames()
+        {
+            return " (supported: Identity, MinDist, MaxDist, BoundingBox, RemoveNaN, SurfaceNormal, "
+                   "SamplingSurfaceNormal, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
+                   "(seeded samplers, not rand()-parity))";
+        }
         void load(const std::vector<pgslam_amd::yaml_lite::Module> &mods)
         {
             using pgslam_amd::yaml_lite::to_double;
@@ -1235,6 +1307,26 @@ struct PointMatcher {
                     if (!(nb >= 1.0 && nb <= 2147483647.0) || nb != std::floor(nb) || (tn != 0.0 && tn != 1.0 && tn != 2.0))
                         throw std::runtime_error(m.name + ": nbSample must be an integer in [1, INT_MAX], torqueNorm 0, 1 or 2");
                     this->push_back(std::make_shared<CovarianceSamplingDataPointsFilter>((std::size_t)nb, (int)tn));
+                } else if (m.name == "OctreeGridDataPointsFilter") {
+                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
+                    for (auto &kv : m.params)
+                        if (kv.first != "maxPointByNode" && kv.first != "maxSizeByNode" && kv.first != "samplingMethod" && kv.first != "buildParallel" &&
+                            kv.first != "seed")
+                            throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    // with neither limit given the defaults hold (maxPointByNode 1, maxSizeByNode 0): one leaf a distinct point -- the
+                    // cloud comes back whole, reordered, only coincident points merged.  As a list entry that is an omission far more
+                    // often than a choice, so, as VoxelGrid refuses one or two sizes alone, that form is refused rather than run
+                    if (!m.params.count("maxPointByNode") && !m.params.count("maxSizeByNode"))
+                        throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name + "' without maxPointByNode or maxSizeByNode: the defaults "
+                                                 "(1 and 0) keep every distinct point, give at least one of the two" + supportedNames());
+                    const double mp = get("maxPointByNode", "1"), ms = get("maxSizeByNode", "0"), sm = get("samplingMethod", "0"), seed = get("seed", "1");
+                    if (!(mp >= 1.0 && mp <= 2147483647.0) || mp != std::floor(mp) || !(ms >= 0.0) || !std::isfinite(ms) || !std::isfinite((T)ms) ||
+                        (sm != 0.0 && sm != 1.0 && sm != 2.0 && sm != 3.0) || !(seed >= 0.0 && seed < 9007199254740992.0))
+                        throw std::runtime_error(m.name + ": maxPointByNode must be an integer in [1, INT_MAX], maxSizeByNode finite and >= 0, "
+                                                          "samplingMethod 0, 1, 2 or 3, seed in [0, 2^53)");
+                    // (buildParallel: accepted and ignored, the result does not depend on it)
+                    this->push_back(std::make_shared<OctreeGridDataPointsFilter>((std::size_t)mp, (T)ms, (int)sm, get("buildParallel", "1") != 0.0,
+                                                                                  (unsigned long long)seed));
                 } else if (m.name == "MaxDensityDataPointsFilter") {
                     auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double md = get("maxDensity", "10"), seed = get("seed", "1");
@@ -1278,10 +1370,7 @@ struct PointMatcher {
                     if (!(mc >= 1.0 && mc <= 2147483647.0) || !(seed >= 0.0 && seed < 9007199254740992.0)) throw std::runtime_error(m.name + ": maxCount must be in [1, INT_MAX], seed in [0, 2^53)");
                     this->push_back(std::make_shared<MaxPointCountDataPointsFilter>((unsigned)mc, (unsigned long long)seed));
                 } else
-                    throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name +
-                                             "' (supported: Identity, MinDist, MaxDist, BoundingBox, RemoveNaN, SurfaceNormal, "
-                                             "SamplingSurfaceNormal, VoxelGrid, MaxDensity, CovarianceSampling, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
-                                             "(seeded samplers, not rand()-parity))");
+                    throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name + "'" + supportedNames());
             }
         }
         void init() { for (auto &f : *this) f->init(); }

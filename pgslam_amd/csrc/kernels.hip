@@ -193,5 +193,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_noise.inc"
 #include "k_density.inc"
 #include "k_covsample.inc"
+#include "k_octree.inc"
 
 }  // namespace pgicp

@@ -213,6 +213,36 @@ template <typename T>
 void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<T> &g, int bits, int centroid, const T *desc, int drows, int average,
                        const VoxScratch &w, T *out_xyz, int os, T *out_desc, int *kept_idx, int *out_count, VoxStat *stat);
 
+// include/pgicp_octree.h (k_octree.inc): OctreeGridDataPointsFilter.  The root the host derives from the bounds (VoxStat, from
+// launch_voxel_bounds) and the levels of a path code; the scratch of a call: the sort's buffers as VoxelGrid's, then per sorted
+// position the leaf depth, the head flag and its scan, per leaf the start and depth, and the heavy leaves' list
+template <typename T>
+struct OctRoot { T c[3], r; int levels; };
+struct OctScratch {
+    unsigned long long *key[2];
+    int *idx[2], *hist, *hoff, *bsum, *depth, *head, *hs, *start, *ldepth, *heavy;
+};
+inline OctScratch oct_scratch(Carve &cv, int n)
+{
+    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kVoxTile - 1) / kVoxTile + 1, hist = 256 * tiles + 1;
+    OctScratch w;
+    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
+    for (auto &i : w.idx) i = cv.take<int>(n1);
+    w.hist = cv.take<int>(hist);
+    w.hoff = cv.take<int>(hist);
+    w.bsum = cv.take<int>(scan_scratch_ints(hist > n1 ? hist : n1));
+    w.depth = cv.take<int>(n1);
+    w.head = cv.take<int>(n1);
+    w.hs = cv.take<int>(n1);
+    w.start = cv.take<int>(n1 + 1);
+    w.ldepth = cv.take<int>(n1);
+    w.heavy = cv.take<int>(n1);
+    return w;
+}
+template <typename T>
+void launch_octree_grid(hipStream_t st, const T *X, int xs, int n, const OctRoot<T> &R, int max_pts, int method, unsigned long long seed, const T *desc,
+                        int drows, const OctScratch &w, T *out_xyz, int os, T *out_desc, int *kept_idx, int *out_count, int *out_depth, VoxStat *stat);
+
 // include/pgicp_density.h (k_density.inc): the densities as an epilogue of the normals kernel, and MaxDensityDataPointsFilter
 struct DensStat {
     unsigned long long key;         // the largest order-preserving key of a non-NaN density (0: none seen)

@@ -72,6 +72,8 @@ COVSAMPLE_SYMBOLS = (
     "pgicp_covariance_sampling_f32", "pgicp_covariance_sampling_f64",
     "pgicp_covariance_sampling_framed_f32", "pgicp_covariance_sampling_framed_f64",
 )
+# every symbol the companion header include/pgicp_octree.h declares (checked by tests/test_octree_grid_host.py)
+OCTREE_SYMBOLS = ("pgicp_octree_grid_f32", "pgicp_octree_grid_f64")
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -1109,6 +1111,47 @@ class Context:
                        C.byref(n_out), C.byref(fr)))
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k], frame=fr.as_dict())
+
+    # ---- OctreeGrid (include/pgicp_octree.h) ------------------------
+    def octree_grid(self, xyz, max_point_by_node=1, max_size_by_node=0.0, sampling_method=0, seed=1, descriptors=None, dtype=None):
+        """OctreeGridDataPointsFilter on the device (pgicp_octree_grid_*, statement in include/pgicp_octree.h).  numpy in -> numpy
+        out, torch CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  sampling_method: 0
+        first point, 1 random (seeded), 2 centroid, 3 medoid.  Returns dict(xyz (k,3), descriptors (k,drows) or None, kept_idx (k,)
+        int32: the leaf's first point for method 2, the kept point otherwise, count (k,) int32: the leaf's points, depth (k,)
+        int32: the leaf's depth) for the k non-empty leaves, in depth-first leaf order."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+        x = _Buf(xyz, dtype)
+        n = x.n
+        d = None
+        drows = 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
+                assert d.ndim == 2 and d.shape[0] == n
+            drows = int(d.shape[1])
+        m = max(n, 1)
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
+            ox, oi, oc, op = mk((m, 3), xyz.dtype), mk((m,), torch.int32), mk((m,), torch.int32), mk((m,), torch.int32)
+            od = mk((m, drows), xyz.dtype) if d is not None else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            ox = np.empty((m, 3), dtype=x.dtype)
+            oi, oc, op = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+            od = np.empty((m, drows), dtype=x.dtype) if d is not None else None
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        n_out = C.c_int(0)
+        fn = getattr(self.lib, "pgicp_octree_grid" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(int(max_point_by_node)),
+                       C.c_double(float(max_size_by_node)), C.c_int(int(sampling_method)), C.c_ulonglong(int(seed)), ptr(d), C.c_int(drows), ptr(ox),
+                       C.c_int(3), ptr(od), ptr(oi), ptr(oc), ptr(op), C.byref(n_out)))
+        k = n_out.value
+        return dict(xyz=ox[:k], descriptors=od[:k] if od is not None else None, kept_idx=oi[:k], count=oc[:k], depth=op[:k])
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
