@@ -33,6 +33,8 @@
 #include "covsample_host.hpp"
 #include "../pgicp_octree.h"
 #include "octree_host.hpp"
+#include "../pgicp_normalspace.h"
+#include "normalspace_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -161,6 +163,8 @@ template <> struct Abi<float> {
     { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
     static int covariance_sampling(pgicp_ctx *c, const float *x, int xs, const float *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pgicp_covariance_sampling_f32(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
+    static int normal_space(pgicp_ctx *c, const float *x, int xs, const float *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
+    { return pgicp_normal_space_sampling_f32(c, x, xs, nr, ns, n, PGICP_HOST, nb, eps, seed, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, nullptr, n_out); }
     static int octree_grid(pgicp_ctx *c, const float *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const float *d, int dr, float *ox, float *od, int32_t *idx, int *n_out)
     { return pgicp_octree_grid_f32(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
     static int voxel_grid(pgicp_ctx *c, const float *x, int xs, int n, const double *v, int cen, const float *d, int dr, int avg, float *ox, float *od, int32_t *idx, int *n_out)
@@ -205,6 +209,8 @@ template <> struct Abi<double> {
     { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
     static int covariance_sampling(pgicp_ctx *c, const double *x, int xs, const double *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pgicp_covariance_sampling_f64(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
+    static int normal_space(pgicp_ctx *c, const double *x, int xs, const double *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
+    { return pgicp_normal_space_sampling_f64(c, x, xs, nr, ns, n, PGICP_HOST, nb, eps, seed, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, nullptr, n_out); }
     static int octree_grid(pgicp_ctx *c, const double *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const double *d, int dr, double *ox, double *od, int32_t *idx, int *n_out)
     { return pgicp_octree_grid_f64(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
     static int voxel_grid(pgicp_ctx *c, const double *x, int xs, int n, const double *v, int cen, const double *d, int dr, int avg, double *ox, double *od, int32_t *idx, int *n_out)
@@ -1092,6 +1098,63 @@ struct PointMatcher {
             hostFilter(c);
         }
     };
+    //! [EXT] NormalSpaceDataPointsFilter{nbSample, epsilon, seed} (DataPointsFilters/NormalSpace.cpp): normal-space sampling
+    //! (Rusinkiewicz & Levoy 2001) -- the normals bucketed on the sphere by steps of epsilon radians, each pick uniform over the
+    //! non-empty buckets and then a random point of that bucket, in pick order.  Needs the `normals` descriptor.  The statement,
+    //! with its marked deviations, is in include/pgicp_normalspace.h.  3-D clouds only.  On the device
+    //! (pgicp_normal_space_sampling_*) when there is one, unless PGSLAM_HOST_INPUT_STAGE=1; else the host form of the same
+    //! statement (normalspace_host.hpp): the same picks.  No deviceSpec: a chain that holds it takes the per-filter path (the
+    //! picks come in pick order).  `seed` is a build-owned extra parameter, as RandomSampling's.  From YAML nbSample must be given
+    //! (upstream's default of 5000 bears no relation to the cloud's size).  ranOnDevice(): which of the two the last
+    //! inPlaceFilter took.
+    struct NormalSpaceDataPointsFilter : DataPointsFilter {
+        std::size_t nbSample; double epsilon; unsigned long long seed;        // (epsilon: a double in both precisions, as the statement reads it)
+        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
+        bool onDevice = false;
+        std::vector<int32_t> idxBuf;
+        explicit NormalSpaceDataPointsFilter(std::size_t nb = 5000, double eps = 0.09, unsigned long long seed_ = 1) : nbSample(nb), epsilon(eps), seed(seed_)
+        {
+            pgslam_amd::normalspace::Grid g;
+            if (nb < 1 || nb > 2147483647u) throw std::runtime_error("NormalSpaceDataPointsFilter: nbSample must be in [1, INT_MAX]");
+            if (!pgslam_amd::normalspace::make_grid(eps, g))
+                throw std::runtime_error("NormalSpaceDataPointsFilter: epsilon must be finite, > 0, <= pi and give at most 65536 buckets (about 1 degree or more)");
+            if (seed_ >= (1ULL << 53)) throw std::runtime_error("NormalSpaceDataPointsFilter: seed must be in [0, 2^53)");
+        }
+        NormalSpaceDataPointsFilter(const NormalSpaceDataPointsFilter &) = delete;
+        NormalSpaceDataPointsFilter &operator=(const NormalSpaceDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        void hostFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), rn = c.getDescriptorStartingRow("normals");
+            std::vector<int32_t> picks, buckets;
+            if (!pgslam_amd::normalspace::host_select<T>(n, [&](int i, int a) { return c.descriptors(rn + a, i); }, (int)nbSample, epsilon, seed, picks, buckets))
+                throw std::runtime_error("NormalSpaceDataPointsFilter: a normal component is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
+            CovarianceSamplingDataPointsFilter::gatherColumns(c, picks.data(), (int)picks.size());
+        }
+        void deviceFilter(DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            const int rn = c.getDescriptorStartingRow("normals");
+            if (idxBuf.size() < nbSample) idxBuf.resize(nbSample);
+            int kept = 0;
+            const int st = pgslam_amd::Abi<T>::normal_space(ctx, c.features.data(), frows, c.descriptors.data() + rn, drows, n, (int)nbSample, epsilon, seed,
+                                                            idxBuf.data(), &kept);
+            if (st == PGICP_ERR_ARG)
+                throw std::runtime_error("NormalSpaceDataPointsFilter: a normal component is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
+            check(ctx, st);
+            CovarianceSamplingDataPointsFilter::gatherColumns(c, idxBuf.data(), kept);
+        }
+        void inPlaceFilter(DataPoints &c) override
+        {
+            onDevice = false;
+            if (!c.descriptorExists("normals") || c.getDescriptorDimension("normals") != 3)
+                throw std::runtime_error("NormalSpaceDataPointsFilter: Error, cannot find normals in descriptors.");
+            if (c.features.rows() != 4) throw std::runtime_error("NormalSpaceDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            if ((std::size_t)c.features.cols() <= nbSample) return;                 // the no-op: the cloud as it is
+            if (CovarianceSamplingDataPointsFilter::deviceWanted()) { deviceFilter(c); onDevice = true; return; }
+            hostFilter(c);
+        }
+    };
     //! [EXT] MaxDensityDataPointsFilter{maxDensity} (DataPointsFilters/MaxDensity.cpp): needs the `densities` descriptor
     //! (SurfaceNormalDataPointsFilter{keepDensities: 1}); keeps a point at or below maxDensity, a denser one with probability
     //! maxDensity / density -- times (1 - nbSaturatedPts / nbPointsIn) in INTEGER arithmetic for points at the cloud's largest
@@ -1247,7 +1310,7 @@ struct PointMatcher {
         static std::string supportedNames()
         {
             return " (supported: Identity, MinDist, MaxDist, BoundingBox, RemoveNaN, SurfaceNormal, "
-                   "SamplingSurfaceNormal, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
+                   "SamplingSurfaceNormal, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, NormalSpace, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
                    "(seeded samplers, not rand()-parity))";
         }
         void load(const std::vector<pgslam_amd::yaml_lite::Module> &mods)
@@ -1327,6 +1390,22 @@ struct PointMatcher {
                     // (buildParallel: accepted and ignored, the result does not depend on it)
                     this->push_back(std::make_shared<OctreeGridDataPointsFilter>((std::size_t)mp, (T)ms, (int)sm, get("buildParallel", "1") != 0.0,
                                                                                   (unsigned long long)seed));
+                } else if (m.name == "NormalSpaceDataPointsFilter") {
+                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
+                    for (auto &kv : m.params)
+                        if (kv.first != "nbSample" && kv.first != "epsilon" && kv.first != "seed") throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    // upstream's default of 5000 bears no relation to the cloud's size: as a list entry without nbSample it is an
+                    // omission far more often than a choice, so, as VoxelGrid and OctreeGrid refuse their bare forms, it is refused
+                    if (!m.params.count("nbSample"))
+                        throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name + "' without nbSample: the default (5000) bears no relation "
+                                                 "to the cloud's size, give nbSample (an integer >= 1)" + supportedNames());
+                    const double nb = get("nbSample", "5000"), eps = get("epsilon", "0.09"), seed = get("seed", "1");
+                    pgslam_amd::normalspace::Grid g;
+                    if (!(nb >= 1.0 && nb <= 2147483647.0) || nb != std::floor(nb) || !pgslam_amd::normalspace::make_grid(eps, g) ||
+                        !(seed >= 0.0 && seed < 9007199254740992.0))
+                        throw std::runtime_error(m.name + ": nbSample must be an integer in [1, INT_MAX], epsilon finite, > 0, <= pi and of at most 65536 "
+                                                          "buckets (about 1 degree or more), seed in [0, 2^53)");
+                    this->push_back(std::make_shared<NormalSpaceDataPointsFilter>((std::size_t)nb, eps, (unsigned long long)seed));
                 } else if (m.name == "MaxDensityDataPointsFilter") {
                     auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double md = get("maxDensity", "10"), seed = get("seed", "1");

@@ -194,5 +194,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_density.inc"
 #include "k_covsample.inc"
 #include "k_octree.inc"
+#include "k_normalspace.inc"
 
 }  // namespace pgicp

@@ -328,4 +328,34 @@ template <typename T>
 void launch_cov_gather(hipStream_t st, const int *picks, int m, int n, const T *X, int xs, const T *N, int ns, const T *desc, int drows, T *out_xyz,
                        int os, T *out_nrm, int ons, T *out_desc, int *kept_idx);
 
+// include/pgicp_normalspace.h (k_normalspace.inc): NormalSpaceDataPointsFilter.  The scratch of a call: the sort's buffers as
+// VoxelGrid's, the buckets' counts with the not-finite flag behind them (counts[nb_bucket]), and the picks' sorted positions
+constexpr int kNsLdsBuckets = 8192;     // a grid of at most this many buckets is counted in LDS, block by block
+struct NsGrid { double epsilon; int n_phi, n_theta, nb_bucket; };
+struct NsScratch {
+    unsigned long long *key[2];
+    int *idx[2], *hist, *hoff, *bsum, *counts, *pos;
+};
+// n points, m = min(n, nbSample) picks
+inline NsScratch ns_scratch(Carve &cv, int n, int m, int nb_bucket)
+{
+    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kVoxTile - 1) / kVoxTile + 1, hist = 256 * tiles + 1;
+    NsScratch w;
+    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
+    for (auto &i : w.idx) i = cv.take<int>(n1);
+    w.hist = cv.take<int>(hist);
+    w.hoff = cv.take<int>(hist);
+    w.bsum = cv.take<int>(scan_scratch_ints(hist));
+    w.counts = cv.take<int>((size_t)nb_bucket + 1);
+    w.pos = cv.take<int>((size_t)m);
+    return w;
+}
+// the keys, the counts (zeroed here) and the stable sort of (key, index); returns which of key[] / idx[] holds the sorted order
+template <typename T>
+int launch_ns_sort(hipStream_t st, const T *N, int ns, int n, const NsGrid &g, unsigned long long seed, const NsScratch &w);
+// out[j] = in[sidx[pos[j]]], bucket_out[j] = skey[pos[j]] >> 24 (pos == null: the identity, bucket -1); any output may be null
+template <typename T>
+void launch_ns_gather(hipStream_t st, const int *pos, const unsigned long long *skey, const int *sidx, int m, int n, const T *X, int xs, const T *N,
+                      int ns, const T *desc, int drows, T *out_xyz, int os, T *out_nrm, int ons, T *out_desc, int *kept_idx, int *bucket_out);
+
 }  // namespace pgicp

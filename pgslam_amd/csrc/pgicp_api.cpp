@@ -11,6 +11,8 @@
 #include "pgslam_amd/covsample_host.hpp"
 #include "pgicp_octree.h"
 #include "pgslam_amd/octree_host.hpp"
+#include "pgicp_normalspace.h"
+#include "pgslam_amd/normalspace_host.hpp"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -44,6 +46,7 @@ using namespace pgicp;
 #include "api_density.inc"            // pgicp_surface_densities_*, pgicp_max_density_*, pgicp_normals_max_density_* (pgicp_density.h)
 #include "api_covsample.inc"          // pgicp_covariance_sampling_*, pgicp_covariance_sampling_framed_* (pgicp_covsample.h)
 #include "api_octree.inc"             // pgicp_octree_grid_* (pgicp_octree.h)
+#include "api_normalspace.inc"        // pgicp_normal_space_sampling_* (pgicp_normalspace.h)
 
 extern "C" {
 

@@ -74,6 +74,8 @@ COVSAMPLE_SYMBOLS = (
 )
 # every symbol the companion header include/pgicp_octree.h declares (checked by tests/test_octree_grid_host.py)
 OCTREE_SYMBOLS = ("pgicp_octree_grid_f32", "pgicp_octree_grid_f64")
+# every symbol the companion header include/pgicp_normalspace.h declares (checked by tests/test_cpp_normal_space.py)
+NORMALSPACE_SYMBOLS = ("pgicp_normal_space_sampling_f32", "pgicp_normal_space_sampling_f64")
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -1152,6 +1154,49 @@ class Context:
                        C.c_int(3), ptr(od), ptr(oi), ptr(oc), ptr(op), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k], descriptors=od[:k] if od is not None else None, kept_idx=oi[:k], count=oc[:k], depth=op[:k])
+
+    # ---- NormalSpace (include/pgicp_normalspace.h) ------------------------
+    def normal_space_sampling(self, xyz, normals, nb_sample, epsilon=0.09, seed=1, descriptors=None, dtype=None):
+        """NormalSpaceDataPointsFilter on the device (pgicp_normal_space_sampling_*, statement in include/pgicp_normalspace.h).
+        numpy in -> numpy out, torch CUDA in -> torch CUDA out.  `normals` (n, >= 3) and `descriptors` ((n, drows) or None) in the
+        same memory as xyz.  Returns dict(xyz (k,3), normals (k,3), descriptors (k,drows) or None, kept_idx (k,) int32, bucket (k,)
+        int32: the pick's bucket, -1 for the no-op) for the k = min(n, nb_sample) picks, in pick order."""
+        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
+            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
+            normals = np.zeros((1, 3), dtype=xyz.dtype)[:0]
+        x = _Buf(xyz, dtype)
+        nb = _Buf(normals, x.dtype if x.mem == HOST else None)
+        n = x.n
+        assert nb.n == n and nb.mem == x.mem and nb.dtype == x.dtype
+        d = None
+        drows = 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
+                assert d.ndim == 2 and d.shape[0] == n
+            drows = int(d.shape[1])
+        m = max(min(n, max(int(nb_sample), 0)), 1)
+        if x.mem == DEVICE:
+            import torch
+            mk = lambda shape, dt=None: torch.empty(shape, dtype=dt or xyz.dtype, device=xyz.device)
+            oi, ob = mk((m,), torch.int32), mk((m,), torch.int32)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            mk = lambda shape: np.empty(shape, dtype=x.dtype)
+            oi, ob = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        ox, on = mk((m, x.stride)), mk((m, 3))
+        oc = mk((m, drows)) if d is not None else None
+        n_out = C.c_int(0)
+        fn = getattr(self.lib, "pgicp_normal_space_sampling" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
+                       C.c_int(int(nb_sample)), C.c_double(float(epsilon)), C.c_ulonglong(int(seed)), ptr(d), C.c_int(drows), ptr(ox), ptr(on),
+                       C.c_int(3), ptr(oc), ptr(oi), ptr(ob), C.byref(n_out)))
+        k = n_out.value
+        return dict(xyz=ox[:k, :3], normals=on[:k], descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k], bucket=ob[:k])
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
