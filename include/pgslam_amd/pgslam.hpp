@@ -732,8 +732,7 @@ public:
         // in one device call: the residual pass starts from the last iteration's correspondences
         std::vector<double> residual(P, 1.0 / 0.0);
         if (noisy) PM::check(ctx, pgslam_amd::Abi<T>::arm_noise(ctx, P, noise_rows.data(), noise_strides.data(), noise_n.data()));
-        const int rc = sizeof(T) == 4 ? pgicp_align_residual_batch_f32(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr)
-                                      : pgicp_align_residual_batch_f64(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr);
+        const int rc = pgslam_amd::Abi<T>::align_residual_batch(ctx, P, pr.data(), Tout.data(), st.data(), residual.data());
         if (rc != PGICP_OK && rc != PGICP_ERR_NO_MATCH && rc != PGICP_ERR_NAN && rc != PGICP_ERR_BOUND) PM::check(ctx, rc);
         TakeNoiseOverlap(ctx, noise_rows, st);
         for (int k = 0; k < P; k++) {
@@ -792,8 +791,7 @@ private:
         }
         // whatever throws below (a partially failed map_create_batch, pushParams, PM::check): the maps made so far go back to the pool
         MapGuard guard{ctx, maps};
-        PM::check(ctx, sizeof(T) == 4 ? pgicp_map_create_batch_f32(ctx, P, (const float *const *)xyz.data(), xs.data(), (const float *const *)nrm.data(), ns.data(), ms.data(), PGICP_DEVICE, 1, maps.data())
-                                      : pgicp_map_create_batch_f64(ctx, P, (const double *const *)xyz.data(), xs.data(), (const double *const *)nrm.data(), ns.data(), ms.data(), PGICP_DEVICE, 1, maps.data()));
+        PM::check(ctx, pgslam_amd::Abi<T>::map_create_batch_dev(ctx, P, xyz.data(), xs.data(), nrm.data(), ns.data(), ms.data(), 1, maps.data()));
         chain_.pushParams();
         for (int k = 0; k < P; k++) {
             const Candidate &c = queue_[mine[k]];
@@ -818,8 +816,7 @@ private:
             noisy = true;
         }
         if (noisy) PM::check(ctx, pgslam_amd::Abi<T>::arm_noise(ctx, P, noise_rows.data(), noise_strides.data(), noise_n.data()));
-        const int rc = sizeof(T) == 4 ? pgicp_align_residual_batch_f32(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr)
-                                      : pgicp_align_residual_batch_f64(ctx, P, pr.data(), Tout.data(), st.data(), residual.data(), nullptr, nullptr);
+        const int rc = pgslam_amd::Abi<T>::align_residual_batch(ctx, P, pr.data(), Tout.data(), st.data(), residual.data());
         if (rc != PGICP_OK && rc != PGICP_ERR_NO_MATCH && rc != PGICP_ERR_NAN && rc != PGICP_ERR_BOUND) PM::check(ctx, rc);
         TakeNoiseOverlap(ctx, noise_rows, st);
         for (int k = 0; k < P; k++) {

@@ -20,10 +20,12 @@
 #include <istream>
 #include <limits>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../pgicp.h"
@@ -133,98 +135,67 @@ struct DeviceCloud {
     }
 };
 
-template <typename T> struct Abi;
-template <> struct Abi<float> {
-    static int map_create(pgicp_ctx *c, const float *x, int xs, const float *n, int ns, int m, int center, int *id) { return pgicp_map_create_f32(c, x, xs, n, ns, m, PGICP_HOST, center, id); }
-    static int align(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Ti, double *To, pgicp_stats *st) { return pgicp_align_f32(c, id, r, s, n, PGICP_HOST, Ti, To, st); }
-    static int align_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Ti, double *To, pgicp_stats *st) { return pgicp_align_f32(c, id, r, s, n, PGICP_DEVICE, Ti, To, st); }
-    static int align_nrm(pgicp_ctx *c, int id, const float *r, int s, int n, const float *nr, int ns, const double *Ti, double *To, pgicp_stats *st)
+//! one of the two entry points of a pgicp_*_f32 / pgicp_*_f64 pair, by the cloud's scalar; any other T does not compile
+template <typename T, typename F32, typename F64>
+constexpr auto pick(F32 *f32, F64 *f64)
+{
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "pgslam_amd: T must be float or double");
+    if constexpr (std::is_same<T, float>::value) return f32; else return f64;
+}
+//! the C ABI by scalar type: each forwarder fixes the memory (PGICP_HOST, or PGICP_DEVICE for *_dev), the packed output
+//! strides and the optional arguments its callers leave out
+template <typename T> struct Abi {
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "pgslam_amd: T must be float or double");
+    static int map_create(pgicp_ctx *c, const T *x, int xs, const T *n, int ns, int m, int center, int *id) { return pick<T>(pgicp_map_create_f32, pgicp_map_create_f64)(c, x, xs, n, ns, m, PGICP_HOST, center, id); }
+    static int align(pgicp_ctx *c, int id, const T *r, int s, int n, const double *Ti, double *To, pgicp_stats *st) { return pick<T>(pgicp_align_f32, pgicp_align_f64)(c, id, r, s, n, PGICP_HOST, Ti, To, st); }
+    static int align_dev(pgicp_ctx *c, int id, const T *r, int s, int n, const double *Ti, double *To, pgicp_stats *st) { return pick<T>(pgicp_align_f32, pgicp_align_f64)(c, id, r, s, n, PGICP_DEVICE, Ti, To, st); }
+    static int align_nrm(pgicp_ctx *c, int id, const T *r, int s, int n, const T *nr, int ns, const double *Ti, double *To, pgicp_stats *st)
     {
         pgicp_problem p;
         std::memset(&p, 0, sizeof p);
         p.map_id = id; p.reading = r; p.stride = s; p.n = n; p.mem = PGICP_HOST; p.normals = nr; p.nstride = ns;
         std::memcpy(p.T_init, Ti, sizeof p.T_init);
-        return pgicp_align_batch_f32(c, 1, &p, To, st);
+        return pick<T>(pgicp_align_batch_f32, pgicp_align_batch_f64)(c, 1, &p, To, st);
     }
-    static int upload(pgicp_ctx *c, const float *host, int stride, int n, const float **dev) { return pgicp_upload_f32(c, 1, &host, &stride, &n, PGICP_HOST, dev); }
-    static int match(pgicp_ctx *c, int id, const float *r, int s, int n, int32_t *ids, float *d2) { return pgicp_match_f32(c, id, r, s, n, PGICP_HOST, nullptr, ids, d2); }
-    static int weights(pgicp_ctx *c, const float *d2, int n, float *w, float *lim, int *nf) { return pgicp_outlier_weights_f32(c, d2, n, PGICP_HOST, w, lim, nf); }
-    static int stats(pgicp_ctx *c, int id, const float *r, int s, int n, const int32_t *ids, const float *w, double *ratio, double *res, double *sys) { return pgicp_error_stats_f32(c, id, r, s, n, PGICP_HOST, ids, w, ratio, res, sys); }
-    static int map_create_batch(pgicp_ctx *c, int k, const float *const *x, const int *xs, const float *const *n, const int *ns, const int *m, int center, int *ids) { return pgicp_map_create_batch_f32(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
-    static int normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig) { return pgicp_surface_normals_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
-    static int normals_ids(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig, int32_t *ids) { return pgicp_surface_normals_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
-    static int densities(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, float *out, int os, float *eig, float *dens) { return pgicp_surface_densities_f32(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, dens); }
-    static int max_density(pgicp_ctx *c, const float *dens, int n, double md, uint64_t sd, int32_t *idx, int *n_out) { return pgicp_max_density_f32(c, dens, n, PGICP_HOST, md, sd, idx, n_out); }
-    static int normals_max_density(pgicp_ctx *c, const float *x, int xs, int n, int knn, double md, double dmax, uint64_t sd, const float *d, int dr, float *ox, float *on,
-                                   float *oe, float *odn, float *od, int32_t *idx, int *n_out)
-    { return pgicp_normals_max_density_f32(c, x, xs, n, PGICP_HOST, knn, md, dmax, sd, d, dr, ox, on, 3, oe, odn, od, idx, n_out); }
-    static int sampling_normals(pgicp_ctx *c, const float *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const float *d, int dr, int avg,
-                                float *ox, float *on, float *od, int32_t *idx, int *n_out)
-    { return pgicp_sampling_surface_normal_f32(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
-    static int covariance_sampling(pgicp_ctx *c, const float *x, int xs, const float *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
-    { return pgicp_covariance_sampling_f32(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
-    static int normal_space(pgicp_ctx *c, const float *x, int xs, const float *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
-    { return pgicp_normal_space_sampling_f32(c, x, xs, nr, ns, n, PGICP_HOST, nb, eps, seed, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, nullptr, n_out); }
-    static int octree_grid(pgicp_ctx *c, const float *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const float *d, int dr, float *ox, float *od, int32_t *idx, int *n_out)
-    { return pgicp_octree_grid_f32(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
-    static int voxel_grid(pgicp_ctx *c, const float *x, int xs, int n, const double *v, int cen, const float *d, int dr, int avg, float *ox, float *od, int32_t *idx, int *n_out)
-    { return pgicp_voxel_grid_f32(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
-    static int partial(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
-    static int partial_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f32(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
-    static int partial_seeded_dev(pgicp_ctx *c, int id, const float *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pgicp_partial_chain_seeded_f32(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
-    static int transform(pgicp_ctx *c, const double *Tm, const float *in, int is, float *out, int os, int n, int ro) { return pgicp_transform_f32(c, Tm, in, is, out, os, n, ro, PGICP_HOST); }
-    static int local_map(pgicp_ctx *c, int k, const float *const *x, const float *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, float *ox, int os, float *on, int ons) { return pgicp_build_local_map_f32(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_HOST); }
-    static int local_map_dev(pgicp_ctx *c, int k, const float *const *x, const float *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, float *ox, int os, float *on, int ons) { return pgicp_build_local_map_f32(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_DEVICE); }
-    static int map_create_dev(pgicp_ctx *c, const float *x, int xs, const float *n, int ns, int m, int center, int *id) { return pgicp_map_create_f32(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
-    static int transform_dev(pgicp_ctx *c, const double *T16, const float *in, int is, float *out, int os, int n, int rotate_only) { return pgicp_transform_f32(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
-    static int arm_noise(pgicp_ctx *c, int k, const float *const *rows, const int *strides, const int *n) { return pgicp_arm_reading_noise_f32(c, k, rows, strides, n, PGICP_HOST); }
-    static int set_values(pgicp_ctx *c, int id, const float *v, int stride) { return pgicp_map_set_values_f32(c, id, v, stride, PGICP_HOST); }
-};
-template <> struct Abi<double> {
-    static int map_create(pgicp_ctx *c, const double *x, int xs, const double *n, int ns, int m, int center, int *id) { return pgicp_map_create_f64(c, x, xs, n, ns, m, PGICP_HOST, center, id); }
-    static int align(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Ti, double *To, pgicp_stats *st) { return pgicp_align_f64(c, id, r, s, n, PGICP_HOST, Ti, To, st); }
-    static int align_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Ti, double *To, pgicp_stats *st) { return pgicp_align_f64(c, id, r, s, n, PGICP_DEVICE, Ti, To, st); }
-    static int align_nrm(pgicp_ctx *c, int id, const double *r, int s, int n, const double *nr, int ns, const double *Ti, double *To, pgicp_stats *st)
-    {
-        pgicp_problem p;
-        std::memset(&p, 0, sizeof p);
-        p.map_id = id; p.reading = r; p.stride = s; p.n = n; p.mem = PGICP_HOST; p.normals = nr; p.nstride = ns;
-        std::memcpy(p.T_init, Ti, sizeof p.T_init);
-        return pgicp_align_batch_f64(c, 1, &p, To, st);
-    }
-    static int upload(pgicp_ctx *c, const double *host, int stride, int n, const double **dev) { return pgicp_upload_f64(c, 1, &host, &stride, &n, PGICP_HOST, dev); }
-    static int match(pgicp_ctx *c, int id, const double *r, int s, int n, int32_t *ids, double *d2) { return pgicp_match_f64(c, id, r, s, n, PGICP_HOST, nullptr, ids, d2); }
-    static int weights(pgicp_ctx *c, const double *d2, int n, double *w, double *lim, int *nf) { return pgicp_outlier_weights_f64(c, d2, n, PGICP_HOST, w, lim, nf); }
-    static int stats(pgicp_ctx *c, int id, const double *r, int s, int n, const int32_t *ids, const double *w, double *ratio, double *res, double *sys) { return pgicp_error_stats_f64(c, id, r, s, n, PGICP_HOST, ids, w, ratio, res, sys); }
-    static int map_create_batch(pgicp_ctx *c, int k, const double *const *x, const int *xs, const double *const *n, const int *ns, const int *m, int center, int *ids) { return pgicp_map_create_batch_f64(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
-    static int normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig) { return pgicp_surface_normals_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
-    static int normals_ids(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig, int32_t *ids) { return pgicp_surface_normals_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
-    static int densities(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double *out, int os, double *eig, double *dens) { return pgicp_surface_densities_f64(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, dens); }
-    static int max_density(pgicp_ctx *c, const double *dens, int n, double md, uint64_t sd, int32_t *idx, int *n_out) { return pgicp_max_density_f64(c, dens, n, PGICP_HOST, md, sd, idx, n_out); }
-    static int normals_max_density(pgicp_ctx *c, const double *x, int xs, int n, int knn, double md, double dmax, uint64_t sd, const double *d, int dr, double *ox, double *on,
-                                   double *oe, double *odn, double *od, int32_t *idx, int *n_out)
-    { return pgicp_normals_max_density_f64(c, x, xs, n, PGICP_HOST, knn, md, dmax, sd, d, dr, ox, on, 3, oe, odn, od, idx, n_out); }
-    static int sampling_normals(pgicp_ctx *c, const double *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const double *d, int dr, int avg,
-                                double *ox, double *on, double *od, int32_t *idx, int *n_out)
-    { return pgicp_sampling_surface_normal_f64(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
-    static int covariance_sampling(pgicp_ctx *c, const double *x, int xs, const double *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
-    { return pgicp_covariance_sampling_f64(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
-    static int normal_space(pgicp_ctx *c, const double *x, int xs, const double *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
-    { return pgicp_normal_space_sampling_f64(c, x, xs, nr, ns, n, PGICP_HOST, nb, eps, seed, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, nullptr, n_out); }
-    static int octree_grid(pgicp_ctx *c, const double *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const double *d, int dr, double *ox, double *od, int32_t *idx, int *n_out)
-    { return pgicp_octree_grid_f64(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
-    static int voxel_grid(pgicp_ctx *c, const double *x, int xs, int n, const double *v, int cen, const double *d, int dr, int avg, double *ox, double *od, int32_t *idx, int *n_out)
-    { return pgicp_voxel_grid_f64(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
-    static int partial(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
-    static int partial_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, double *ratio, double *res) { return pgicp_partial_chain_f64(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
-    static int partial_seeded_dev(pgicp_ctx *c, int id, const double *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pgicp_partial_chain_seeded_f64(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
-    static int transform(pgicp_ctx *c, const double *Tm, const double *in, int is, double *out, int os, int n, int ro) { return pgicp_transform_f64(c, Tm, in, is, out, os, n, ro, PGICP_HOST); }
-    static int local_map(pgicp_ctx *c, int k, const double *const *x, const double *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, double *ox, int os, double *on, int ons) { return pgicp_build_local_map_f64(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_HOST); }
-    static int local_map_dev(pgicp_ctx *c, int k, const double *const *x, const double *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, double *ox, int os, double *on, int ons) { return pgicp_build_local_map_f64(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_DEVICE); }
-    static int map_create_dev(pgicp_ctx *c, const double *x, int xs, const double *n, int ns, int m, int center, int *id) { return pgicp_map_create_f64(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
-    static int transform_dev(pgicp_ctx *c, const double *T16, const double *in, int is, double *out, int os, int n, int rotate_only) { return pgicp_transform_f64(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
-    static int arm_noise(pgicp_ctx *c, int k, const double *const *rows, const int *strides, const int *n) { return pgicp_arm_reading_noise_f64(c, k, rows, strides, n, PGICP_HOST); }
-    static int set_values(pgicp_ctx *c, int id, const double *v, int stride) { return pgicp_map_set_values_f64(c, id, v, stride, PGICP_HOST); }
+    static int upload(pgicp_ctx *c, const T *host, int stride, int n, const T **dev) { return pick<T>(pgicp_upload_f32, pgicp_upload_f64)(c, 1, &host, &stride, &n, PGICP_HOST, dev); }
+    static int match(pgicp_ctx *c, int id, const T *r, int s, int n, int32_t *ids, T *d2) { return pick<T>(pgicp_match_f32, pgicp_match_f64)(c, id, r, s, n, PGICP_HOST, nullptr, ids, d2); }
+    static int weights(pgicp_ctx *c, const T *d2, int n, T *w, T *lim, int *nf) { return pick<T>(pgicp_outlier_weights_f32, pgicp_outlier_weights_f64)(c, d2, n, PGICP_HOST, w, lim, nf); }
+    static int stats(pgicp_ctx *c, int id, const T *r, int s, int n, const int32_t *ids, const T *w, double *ratio, double *res, double *sys) { return pick<T>(pgicp_error_stats_f32, pgicp_error_stats_f64)(c, id, r, s, n, PGICP_HOST, ids, w, ratio, res, sys); }
+    static int map_create_batch(pgicp_ctx *c, int k, const T *const *x, const int *xs, const T *const *n, const int *ns, const int *m, int center, int *ids) { return pick<T>(pgicp_map_create_batch_f32, pgicp_map_create_batch_f64)(c, k, x, xs, n, ns, m, PGICP_HOST, center, ids); }
+    static int normals(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, T *out, int os, T *eig) { return pick<T>(pgicp_surface_normals_f32, pgicp_surface_normals_f64)(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
+    static int normals_ids(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, T *out, int os, T *eig, int32_t *ids) { return pick<T>(pgicp_surface_normals_f32, pgicp_surface_normals_f64)(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
+    static int densities(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, T *out, int os, T *eig, T *dens) { return pick<T>(pgicp_surface_densities_f32, pgicp_surface_densities_f64)(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, dens); }
+    static int max_density(pgicp_ctx *c, const T *dens, int n, double md, uint64_t sd, int32_t *idx, int *n_out) { return pick<T>(pgicp_max_density_f32, pgicp_max_density_f64)(c, dens, n, PGICP_HOST, md, sd, idx, n_out); }
+    static int normals_max_density(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, double dmax, uint64_t sd, const T *d, int dr, T *ox, T *on,
+                                   T *oe, T *odn, T *od, int32_t *idx, int *n_out)
+    { return pick<T>(pgicp_normals_max_density_f32, pgicp_normals_max_density_f64)(c, x, xs, n, PGICP_HOST, knn, md, dmax, sd, d, dr, ox, on, 3, oe, odn, od, idx, n_out); }
+    static int sampling_normals(pgicp_ctx *c, const T *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const T *d, int dr, int avg,
+                                T *ox, T *on, T *od, int32_t *idx, int *n_out)
+    { return pick<T>(pgicp_sampling_surface_normal_f32, pgicp_sampling_surface_normal_f64)(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
+    static int covariance_sampling(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
+    { return pick<T>(pgicp_covariance_sampling_f32, pgicp_covariance_sampling_f64)(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
+    static int normal_space(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
+    { return pick<T>(pgicp_normal_space_sampling_f32, pgicp_normal_space_sampling_f64)(c, x, xs, nr, ns, n, PGICP_HOST, nb, eps, seed, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, nullptr, n_out); }
+    static int octree_grid(pgicp_ctx *c, const T *x, int xs, int n, int mp, double ms, int method, unsigned long long seed, const T *d, int dr, T *ox, T *od, int32_t *idx, int *n_out)
+    { return pick<T>(pgicp_octree_grid_f32, pgicp_octree_grid_f64)(c, x, xs, n, PGICP_HOST, mp, ms, method, seed, d, dr, ox, 3, od, idx, nullptr, nullptr, n_out); }
+    static int voxel_grid(pgicp_ctx *c, const T *x, int xs, int n, const double *v, int cen, const T *d, int dr, int avg, T *ox, T *od, int32_t *idx, int *n_out)
+    { return pick<T>(pgicp_voxel_grid_f32, pgicp_voxel_grid_f64)(c, x, xs, n, PGICP_HOST, v, cen, d, dr, avg, ox, 3, od, idx, nullptr, n_out); }
+    static int partial(pgicp_ctx *c, int id, const T *r, int s, int n, const double *Tm, double *ratio, double *res) { return pick<T>(pgicp_partial_chain_f32, pgicp_partial_chain_f64)(c, id, r, s, n, PGICP_HOST, Tm, ratio, res); }
+    static int partial_dev(pgicp_ctx *c, int id, const T *r, int s, int n, const double *Tm, double *ratio, double *res) { return pick<T>(pgicp_partial_chain_f32, pgicp_partial_chain_f64)(c, id, r, s, n, PGICP_DEVICE, Tm, ratio, res); }
+    static int partial_seeded_dev(pgicp_ctx *c, int id, const T *r, int s, int n, const double *Tm, pgicp_ctx *src, int ns, const int32_t *a, const int32_t *b, double *ratio, double *res) { return pick<T>(pgicp_partial_chain_seeded_f32, pgicp_partial_chain_seeded_f64)(c, id, r, s, n, PGICP_DEVICE, Tm, src, ns, a, b, ratio, res); }
+    static int transform(pgicp_ctx *c, const double *Tm, const T *in, int is, T *out, int os, int n, int ro) { return pick<T>(pgicp_transform_f32, pgicp_transform_f64)(c, Tm, in, is, out, os, n, ro, PGICP_HOST); }
+    static int local_map(pgicp_ctx *c, int k, const T *const *x, const T *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, T *ox, int os, T *on, int ons) { return pick<T>(pgicp_build_local_map_f32, pgicp_build_local_map_f64)(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_HOST); }
+    static int local_map_dev(pgicp_ctx *c, int k, const T *const *x, const T *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, T *ox, int os, T *on, int ons) { return pick<T>(pgicp_build_local_map_f32, pgicp_build_local_map_f64)(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_DEVICE); }
+    static int map_create_dev(pgicp_ctx *c, const T *x, int xs, const T *n, int ns, int m, int center, int *id) { return pick<T>(pgicp_map_create_f32, pgicp_map_create_f64)(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
+    static int transform_dev(pgicp_ctx *c, const double *T16, const T *in, int is, T *out, int os, int n, int rotate_only) { return pick<T>(pgicp_transform_f32, pgicp_transform_f64)(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
+    static int arm_noise(pgicp_ctx *c, int k, const T *const *rows, const int *strides, const int *n) { return pick<T>(pgicp_arm_reading_noise_f32, pgicp_arm_reading_noise_f64)(c, k, rows, strides, n, PGICP_HOST); }
+    static int set_values(pgicp_ctx *c, int id, const T *v, int stride) { return pick<T>(pgicp_map_set_values_f32, pgicp_map_set_values_f64)(c, id, v, stride, PGICP_HOST); }
+    static int map_create_batch_dev(pgicp_ctx *c, int k, const T *const *x, const int *xs, const T *const *n, const int *ns, const int *m, int center, int *ids) { return pick<T>(pgicp_map_create_batch_f32, pgicp_map_create_batch_f64)(c, k, x, xs, n, ns, m, PGICP_DEVICE, center, ids); }
+    static int align_residual_batch(pgicp_ctx *c, int k, const pgicp_problem *p, double *To, pgicp_stats *st, double *residual) { return pick<T>(pgicp_align_residual_batch_f32, pgicp_align_residual_batch_f64)(c, k, p, To, st, residual, nullptr, nullptr); }
+    static int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *x, int xs, const T *d, int dr, int n, const double *T16, int r0, int r1, T *ox, T *od, int *n_out, const T **dev)
+    { return pick<T>(pgicp_filter_cloud_f32, pgicp_filter_cloud_f64)(c, nf, f, x, xs, d, dr, n, T16, r0, r1, ox, od, nullptr, n_out, dev); }
+    static int filter_cloud_dev(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *x, int xs, int n, int32_t *dropped, int cap, int *n_dropped, int *n_out, const T **dev)
+    { return pick<T>(pgicp_filter_cloud_dev_f32, pgicp_filter_cloud_dev_f64)(c, nf, f, x, xs, n, dropped, cap, n_dropped, n_out, dev); }
 };
 
 }  // namespace pgslam_amd
@@ -454,6 +425,75 @@ struct PointMatcher {
         c.features.conservativeResize(c.features.rows(), k);
         if (c.descriptors.rows()) c.descriptors.conservativeResize(c.descriptors.rows(), k);
     }
+    //! the build's seeded draw for item j, uniform in [0, 1): SplitMix64's finaliser of seed and index (reproducible, not
+    //! rand()-parity); what every sampling filter compares with its probability
+    static unsigned long long mix64(unsigned long long z)
+    {
+        z += 0x9E3779B97F4A7C15ULL; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        return z ^ (z >> 31);
+    }
+    static double seededDraw(unsigned long long seed, int j) { return (double)(mix64(seed * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0; }
+    //! keeps the columns idx[0 .. kept) (ascending), in order
+    static void keepColumns(DataPoints &c, const int32_t *idx, int kept)
+    {
+        int k = 0;
+        compactColumns(c, [&](int j) { if (k < kept && idx[k] == j) { k++; return true; } return false; });
+    }
+    //! the columns idx[0 .. kept), in that order (features and descriptors)
+    static void gatherColumns(DataPoints &c, const int32_t *idx, int kept)
+    {
+        const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+        Matrix f(frows, kept), d(drows, kept);
+        for (int o = 0; o < kept; o++) {
+            const int i = idx[o];
+            for (int r = 0; r < frows; r++) f(r, o) = c.features(r, i);
+            for (int r = 0; r < drows; r++) d(r, o) = c.descriptors(r, i);
+        }
+        c.features = f;
+        c.descriptors = d;
+    }
+    //! one column per idx[0 .. kept): rows 0-2 from `ox` (3 a point), rows 3.. of point idx[o], descriptors from `od` (drows a point)
+    static void assemble(DataPoints &c, const T *ox, const T *od, const int32_t *idx, int kept)
+    {
+        const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+        Matrix f(frows, kept), d(drows, kept);
+        for (int o = 0; o < kept; o++) {
+            const int i = idx[o];
+            for (int r = 0; r < 3; r++) f(r, o) = ox[3 * (size_t)o + r];
+            for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
+            for (int r = 0; r < drows; r++) d(r, o) = od[(size_t)drows * o + r];
+        }
+        c.features = f;
+        if (drows > 0) c.descriptors = d;
+    }
+    //! What the filters with a device form AND a host form of one statement share.  `ctx` is made when the filter first runs on
+    //! the device, not when a YAML file is read (so the filter is not copyable); ranOnDevice(): which of the two forms the last
+    //! inPlaceFilter took; deviceWanted(knob): a device is present and the environment does not say <knob>=1.
+    struct DeviceBackedDataPointsFilter : DataPointsFilter {
+        pgslam_amd::LazyContext ctx;
+        bool onDevice = false;
+        DeviceBackedDataPointsFilter() {}
+        DeviceBackedDataPointsFilter(const DeviceBackedDataPointsFilter &) = delete;
+        DeviceBackedDataPointsFilter &operator=(const DeviceBackedDataPointsFilter &) = delete;
+        bool ranOnDevice() const { return onDevice; }
+        static bool deviceWanted(const char *knob)
+        {
+            static const bool have_device = pgicp_device_count() > 0;
+            const char *v = std::getenv(knob);
+            return have_device && !(v && std::strcmp(v, "1") == 0);
+        }
+        //! the output buffers are kept from call to call and only grow (a 1 M-point map: no fresh pages)
+        template <typename V> static void grow(V &v, size_t n) { if (v.size() < n) v.resize(n); }
+        static void need3D(const DataPoints &c, const char *filter)
+        {
+            if (c.features.rows() != 4) throw std::runtime_error(std::string(filter) + ": only 3-D clouds (4 feature rows) are supported");
+        }
+        static void needNormals(const DataPoints &c, const char *filter)
+        {
+            if (!c.descriptorExists("normals") || c.getDescriptorDimension("normals") != 3)
+                throw std::runtime_error(std::string(filter) + ": Error, cannot find normals in descriptors.");
+        }
+    };
     //! [EXT] MaxDistDataPointsFilter{maxDist, dim} / MinDistDataPointsFilter{minDist, dim} (DataPointsFilters/MaxDist.cpp, MinDist.cpp):
     //! dim = -1: keeps points whose distance to the origin -- features.col(i).head(3).norm() in T -- is below |maxDist| (above
     //! |minDist|), strictly; dim = 0..2: keeps features(dim, i) < maxDist (> minDist).  A NaN fails either comparison.
@@ -601,14 +641,10 @@ struct PointMatcher {
             f.type = PGICP_FILTER_RANDOM_SAMPLING; f.p[0] = (double)prob; f.p[1] = (double)seed;
             return true;
         }
-        static unsigned long long mix(unsigned long long z)
-        {
-            z += 0x9E3779B97F4A7C15ULL; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-            return z ^ (z >> 31);
-        }
+        static unsigned long long mix(unsigned long long z) { return mix64(z); }
         void inPlaceFilter(DataPoints &c) override
         {
-            compactColumns(c, [&](int j) { return (double)(mix(seed * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0 < (double)prob; });
+            compactColumns(c, [&](int j) { return seededDraw(seed, j) < (double)prob; });
         }
     };
     //! [EXT] MaxPointCountDataPointsFilter{maxCount, seed} (DataPointsFilters/MaxPointCount.cpp as of the libpointmatcher pgslam was
@@ -629,7 +665,7 @@ struct PointMatcher {
             const int n = (int)c.features.cols();
             if (!((double)n > (double)maxCount)) return;
             const double prob = (double)((T)maxCount / (T)n);
-            compactColumns(c, [&](int j) { return (double)(RandomSamplingDataPointsFilter::mix(seed * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0 < prob; });
+            compactColumns(c, [&](int j) { return seededDraw(seed, j) < prob; });
         }
     };
     //! [EXT] SurfaceNormalDataPointsFilter{knn, maxDist, epsilon, keepNormals, keepEigenValues}: normals (and,
@@ -693,18 +729,13 @@ struct PointMatcher {
     //! cannot be: nth_element's arrangement -> a sort on (coordinate, index); rand() -> the seeded draw; EigenSolver -> Jacobi).
     //! It runs once per keyframe / map, on the reference (Localizer.hpp:314-315), and per loop-closure candidate: on the device
     //! (pgicp_sampling_surface_normal_*, the same bits) when there is one, unless PGSLAM_HOST_SAMPLING_NORMALS=1 or the device
-    //! refuses the cloud (a NaN or infinite coordinate, an out-of-range knn); then the host recursion below.  ranOnDevice():
-    //! which of the two the last inPlaceFilter took.
-    struct SamplingSurfaceNormalDataPointsFilter : DataPointsFilter {
+    //! refuses the cloud (a NaN or infinite coordinate, an out-of-range knn); then the host recursion below.
+    struct SamplingSurfaceNormalDataPointsFilter : DeviceBackedDataPointsFilter {
+        using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         T ratio; int knn, samplingMethod; T maxBoxDim; bool averageExistingDescriptors, keepNormals; unsigned long long seed;
-        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
-        bool onDevice = false;
         SamplingSurfaceNormalDataPointsFilter(T r = T(0.5), int k = 7, int method = 0, T box = std::numeric_limits<T>::infinity(), bool avg = true,
                                               bool kn = true, unsigned long long sd = 1)
             : ratio(r), knn(k), samplingMethod(method), maxBoxDim(box), averageExistingDescriptors(avg), keepNormals(kn), seed(sd) {}
-        SamplingSurfaceNormalDataPointsFilter(const SamplingSurfaceNormalDataPointsFilter &) = delete;
-        SamplingSurfaceNormalDataPointsFilter &operator=(const SamplingSurfaceNormalDataPointsFilter &) = delete;
-        bool ranOnDevice() const { return onDevice; }
         //! the device form; false (the cloud untouched) when the device refuses the arguments
         bool deviceFilter(DataPoints &c)
         {
@@ -739,9 +770,7 @@ struct PointMatcher {
             onDevice = false;
             const int n = (int)c.features.cols();
             if (n == 0) return;
-            const char *knob = std::getenv("PGSLAM_HOST_SAMPLING_NORMALS");
-            static const bool have_device = pgicp_device_count() > 0;
-            if (have_device && !(knob && std::strcmp(knob, "1") == 0) && deviceFilter(c)) { onDevice = true; return; }
+            if (this->deviceWanted("PGSLAM_HOST_SAMPLING_NORMALS") && deviceFilter(c)) { onDevice = true; return; }
             const int drows = (int)c.descriptors.rows();
             std::vector<int> idx(n);
             for (int i = 0; i < n; i++) idx[i] = i;
@@ -799,7 +828,7 @@ struct PointMatcher {
                 if (samplingMethod == 0) {
                     for (int k = R.first; k < R.last; k++) {
                         const int i = idx[k];
-                        if (!((double)(RandomSamplingDataPointsFilter::mix(seed * 0x100000001B3ULL + (unsigned long long)i) >> 11) / 9007199254740992.0 < (double)ratio)) continue;
+                        if (!(seededDraw(seed, i) < (double)ratio)) continue;
                         keep[i] = 1;
                         nrm(0, i) = (T)V[0][l]; nrm(1, i) = (T)V[1][l]; nrm(2, i) = (T)V[2][l];
                     }
@@ -827,12 +856,11 @@ struct PointMatcher {
     //! (pgicp_voxel_grid_*).  3-D clouds only.  On the device (the same bits) when there is one, unless PGSLAM_HOST_VOXEL_GRID=1
     //! or the device refuses the cloud; then the host form below, which sorts (key, index) instead of allocating the dense
     //! grid.  No deviceSpec: a chain that holds it takes the per-filter path (it changes values, pgicp_filter_cloud only drops
-    //! points).  ranOnDevice(): which of the two the last inPlaceFilter took.  From YAML the three sizes come together or not at
-    //! all (upstream fills a missing one with 1 m; here one or two sizes alone are refused).
-    struct VoxelGridDataPointsFilter : DataPointsFilter {
+    //! points).  From YAML the three sizes come together or not at all (upstream fills a missing one with 1 m; here one or two
+    //! sizes alone are refused).
+    struct VoxelGridDataPointsFilter : DeviceBackedDataPointsFilter {
+        using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         T vSizeX, vSizeY, vSizeZ; bool useCentroid, averageExistingDescriptors;
-        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
-        bool onDevice = false;
         std::vector<T> oxBuf, odBuf;                 // the device form's outputs, kept from call to call (a 1 M-point map: no fresh pages)
         std::vector<int32_t> idxBuf;
         VoxelGridDataPointsFilter(T vx = T(1), T vy = T(1), T vz = T(1), bool cen = true, bool avg = true)
@@ -841,30 +869,13 @@ struct PointMatcher {
             for (T v : {vx, vy, vz})
                 if (!(v > T(0)) || !std::isfinite(v)) throw std::runtime_error("VoxelGridDataPointsFilter: vSizeX, vSizeY and vSizeZ must be finite and > 0");
         }
-        VoxelGridDataPointsFilter(const VoxelGridDataPointsFilter &) = delete;
-        VoxelGridDataPointsFilter &operator=(const VoxelGridDataPointsFilter &) = delete;
-        bool ranOnDevice() const { return onDevice; }
-        //! rows 0-2 from `ox` (3 a point), rows 3.. of the first point, descriptors from `od` (drows a point)
-        static void assemble(DataPoints &c, const T *ox, const T *od, const int32_t *idx, int kept)
-        {
-            const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            Matrix f(frows, kept), d(drows, kept);
-            for (int o = 0; o < kept; o++) {
-                const int i = idx[o];
-                for (int r = 0; r < 3; r++) f(r, o) = ox[3 * (size_t)o + r];
-                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
-                for (int r = 0; r < drows; r++) d(r, o) = od[(size_t)drows * o + r];
-            }
-            c.features = f;
-            if (drows > 0) c.descriptors = d;
-        }
         //! the device form; false (the cloud untouched) when the device refuses the arguments
         bool deviceFilter(DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            if (oxBuf.size() < 3 * (size_t)n) oxBuf.resize(3 * (size_t)n);
-            if (odBuf.size() < (size_t)drows * n) odBuf.resize((size_t)drows * n);
-            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            this->grow(oxBuf, 3 * (size_t)n);
+            this->grow(odBuf, (size_t)drows * n);
+            this->grow(idxBuf, (size_t)n);
             const double v[3] = {(double)vSizeX, (double)vSizeY, (double)vSizeZ};
             int kept = 0;
             const int st = pgslam_amd::Abi<T>::voxel_grid(ctx, c.features.data(), frows, n, v, useCentroid ? 1 : 0, drows > 0 ? c.descriptors.data() : nullptr,
@@ -949,11 +960,9 @@ struct PointMatcher {
         void inPlaceFilter(DataPoints &c) override
         {
             onDevice = false;
-            if (c.features.rows() != 4) throw std::runtime_error("VoxelGridDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            this->need3D(c, "VoxelGridDataPointsFilter");
             if (c.features.cols() == 0) return;
-            const char *knob = std::getenv("PGSLAM_HOST_VOXEL_GRID");
-            static const bool have_device = pgicp_device_count() > 0;
-            if (have_device && !(knob && std::strcmp(knob, "1") == 0) && deviceFilter(c)) { onDevice = true; return; }
+            if (this->deviceWanted("PGSLAM_HOST_VOXEL_GRID") && deviceFilter(c)) { onDevice = true; return; }
             hostFilter(c);
         }
     };
@@ -964,40 +973,17 @@ struct PointMatcher {
     //! PGSLAM_HOST_INPUT_STAGE=1; else the host form of the same statement (covsample_host.hpp): the same picks bit for bit given
     //! the same frame -- the host form sums its frame in index order, the device in a tree, so the two frames may differ in
     //! their last bits.  No deviceSpec: a chain that holds it takes the per-filter path (the picks come in pick order,
-    //! pgicp_filter_cloud only drops points).  ranOnDevice(): which of the two the last inPlaceFilter took; lastFrame: its frame.
-    struct CovarianceSamplingDataPointsFilter : DataPointsFilter {
+    //! pgicp_filter_cloud only drops points).  lastFrame: the last inPlaceFilter's frame.
+    struct CovarianceSamplingDataPointsFilter : DeviceBackedDataPointsFilter {
+        using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         enum TorqueNormMethod { L1 = 0, Lavg = 1, Lmax = 2 };
         std::size_t nbSample; TorqueNormMethod normalizationMethod;
-        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
-        bool onDevice = false;
         pgicp_cov_frame lastFrame{};
         std::vector<int32_t> idxBuf;
         explicit CovarianceSamplingDataPointsFilter(std::size_t nb = 5000, int torqueNorm = 1) : nbSample(nb), normalizationMethod((TorqueNormMethod)torqueNorm)
         {
             if (nb < 1 || nb > 2147483647u) throw std::runtime_error("CovarianceSamplingDataPointsFilter: nbSample must be in [1, INT_MAX]");
             if (torqueNorm < 0 || torqueNorm > 2) throw std::runtime_error("CovarianceSamplingDataPointsFilter: torqueNorm must be 0 (L = 1), 1 (Lavg) or 2 (Lmax)");
-        }
-        CovarianceSamplingDataPointsFilter(const CovarianceSamplingDataPointsFilter &) = delete;
-        CovarianceSamplingDataPointsFilter &operator=(const CovarianceSamplingDataPointsFilter &) = delete;
-        bool ranOnDevice() const { return onDevice; }
-        static bool deviceWanted()
-        {
-            const char *knob = std::getenv("PGSLAM_HOST_INPUT_STAGE");
-            static const bool have_device = pgicp_device_count() > 0;
-            return have_device && !(knob && std::strcmp(knob, "1") == 0);
-        }
-        //! the columns idx[0 .. kept), in that order (features and descriptors)
-        static void gatherColumns(DataPoints &c, const int32_t *idx, int kept)
-        {
-            const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            Matrix f(frows, kept), d(drows, kept);
-            for (int o = 0; o < kept; o++) {
-                const int i = idx[o];
-                for (int r = 0; r < frows; r++) f(r, o) = c.features(r, i);
-                for (int r = 0; r < drows; r++) d(r, o) = c.descriptors(r, i);
-            }
-            c.features = f;
-            c.descriptors = d;
         }
         //! the picks of the host form given a frame (nbSample < the cloud's size)
         void hostPicks(const DataPoints &c, const pgicp_cov_frame &frame, std::vector<int32_t> &picks) const
@@ -1021,7 +1007,7 @@ struct PointMatcher {
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
             const int rn = c.getDescriptorStartingRow("normals");
-            if (idxBuf.size() < nbSample) idxBuf.resize(nbSample);
+            this->grow(idxBuf, nbSample);
             int kept = 0;
             check(ctx, pgslam_amd::Abi<T>::covariance_sampling(ctx, c.features.data(), frows, c.descriptors.data() + rn, drows, n, (int)nbSample,
                                                                (int)normalizationMethod, idxBuf.data(), &kept, &lastFrame));
@@ -1030,11 +1016,10 @@ struct PointMatcher {
         void inPlaceFilter(DataPoints &c) override
         {
             onDevice = false;
-            if (!c.descriptorExists("normals") || c.getDescriptorDimension("normals") != 3)
-                throw std::runtime_error("CovarianceSamplingDataPointsFilter: Error, cannot find normals in descriptors.");
-            if (c.features.rows() != 4) throw std::runtime_error("CovarianceSamplingDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            this->needNormals(c, "CovarianceSamplingDataPointsFilter");
+            this->need3D(c, "CovarianceSamplingDataPointsFilter");
             if ((std::size_t)c.features.cols() <= nbSample) return;                 // the no-op: the cloud as it is
-            if (deviceWanted()) { deviceFilter(c); onDevice = true; return; }
+            if (this->deviceWanted("PGSLAM_HOST_INPUT_STAGE")) { deviceFilter(c); onDevice = true; return; }
             hostFilter(c);
         }
     };
@@ -1045,13 +1030,11 @@ struct PointMatcher {
     //! (pgicp_octree_grid_*, the same bits) when there is one, unless PGSLAM_HOST_INPUT_STAGE=1; else the host form of the same
     //! statement (octree_host.hpp).  No deviceSpec: a chain that holds it takes the per-filter path (it reorders points).
     //! `seed` (method 1) is a build-owned extra parameter, as RandomSampling's.  From YAML maxPointByNode or maxSizeByNode must be
-    //! given (neither: the defaults keep every distinct point, refused as an omission).  ranOnDevice(): which of the two the last
-    //! inPlaceFilter took.
-    struct OctreeGridDataPointsFilter : DataPointsFilter {
+    //! given (neither: the defaults keep every distinct point, refused as an omission).
+    struct OctreeGridDataPointsFilter : DeviceBackedDataPointsFilter {
+        using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         enum SamplingMethod { FIRST_PTS = 0, RAND_PTS = 1, CENTROID = 2, MEDOID = 3 };
         std::size_t maxPointByNode; T maxSizeByNode; SamplingMethod samplingMethod; bool buildParallel; unsigned long long seed;
-        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
-        bool onDevice = false;
         std::vector<T> oxBuf, odBuf;                 // the device form's outputs, kept from call to call
         std::vector<int32_t> idxBuf;
         explicit OctreeGridDataPointsFilter(std::size_t maxPts = 1, T maxSize = T(0), int method = 0, bool parallel = true, unsigned long long seed_ = 1)
@@ -1062,15 +1045,12 @@ struct PointMatcher {
             if (method < 0 || method > 3) throw std::runtime_error("OctreeGridDataPointsFilter: samplingMethod must be 0 (first), 1 (random), 2 (centroid) or 3 (medoid)");
             if (seed_ >= (1ULL << 53)) throw std::runtime_error("OctreeGridDataPointsFilter: seed must be in [0, 2^53)");
         }
-        OctreeGridDataPointsFilter(const OctreeGridDataPointsFilter &) = delete;
-        OctreeGridDataPointsFilter &operator=(const OctreeGridDataPointsFilter &) = delete;
-        bool ranOnDevice() const { return onDevice; }
         void deviceFilter(DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            if (oxBuf.size() < 3 * (size_t)n) oxBuf.resize(3 * (size_t)n);
-            if (odBuf.size() < (size_t)drows * n) odBuf.resize((size_t)drows * n);
-            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            this->grow(oxBuf, 3 * (size_t)n);
+            this->grow(odBuf, (size_t)drows * n);
+            this->grow(idxBuf, (size_t)n);
             int kept = 0;
             const int st = pgslam_amd::Abi<T>::octree_grid(ctx, c.features.data(), frows, n, (int)maxPointByNode, (double)maxSizeByNode, (int)samplingMethod, seed,
                                                            drows > 0 ? c.descriptors.data() : nullptr, drows, oxBuf.data(), drows > 0 ? odBuf.data() : nullptr,
@@ -1078,7 +1058,7 @@ struct PointMatcher {
             if (st == PGICP_ERR_ARG)
                 throw std::runtime_error("OctreeGridDataPointsFilter: a coordinate is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
             check(ctx, st);
-            VoxelGridDataPointsFilter::assemble(c, oxBuf.data(), odBuf.data(), idxBuf.data(), kept);
+            assemble(c, oxBuf.data(), odBuf.data(), idxBuf.data(), kept);
         }
         void hostFilter(DataPoints &c)
         {
@@ -1087,14 +1067,14 @@ struct PointMatcher {
             if (!pgslam_amd::octree::host_filter<T>(n, [&](int i, int a) { return c.features(a, i); }, drows, [&](int i, int r) { return c.descriptors(r, i); },
                                                     (int)maxPointByNode, maxSizeByNode, (int)samplingMethod, seed, res))
                 throw std::runtime_error("OctreeGridDataPointsFilter: a coordinate is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
-            VoxelGridDataPointsFilter::assemble(c, res.xyz.data(), res.desc.data(), res.kept.data(), (int)res.kept.size());
+            assemble(c, res.xyz.data(), res.desc.data(), res.kept.data(), (int)res.kept.size());
         }
         void inPlaceFilter(DataPoints &c) override
         {
             onDevice = false;
-            if (c.features.rows() != 4) throw std::runtime_error("OctreeGridDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            this->need3D(c, "OctreeGridDataPointsFilter");
             if (c.features.cols() == 0) return;
-            if (CovarianceSamplingDataPointsFilter::deviceWanted()) { deviceFilter(c); onDevice = true; return; }
+            if (this->deviceWanted("PGSLAM_HOST_INPUT_STAGE")) { deviceFilter(c); onDevice = true; return; }
             hostFilter(c);
         }
     };
@@ -1105,12 +1085,10 @@ struct PointMatcher {
     //! (pgicp_normal_space_sampling_*) when there is one, unless PGSLAM_HOST_INPUT_STAGE=1; else the host form of the same
     //! statement (normalspace_host.hpp): the same picks.  No deviceSpec: a chain that holds it takes the per-filter path (the
     //! picks come in pick order).  `seed` is a build-owned extra parameter, as RandomSampling's.  From YAML nbSample must be given
-    //! (upstream's default of 5000 bears no relation to the cloud's size).  ranOnDevice(): which of the two the last
-    //! inPlaceFilter took.
-    struct NormalSpaceDataPointsFilter : DataPointsFilter {
+    //! (upstream's default of 5000 bears no relation to the cloud's size).
+    struct NormalSpaceDataPointsFilter : DeviceBackedDataPointsFilter {
+        using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         std::size_t nbSample; double epsilon; unsigned long long seed;        // (epsilon: a double in both precisions, as the statement reads it)
-        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
-        bool onDevice = false;
         std::vector<int32_t> idxBuf;
         explicit NormalSpaceDataPointsFilter(std::size_t nb = 5000, double eps = 0.09, unsigned long long seed_ = 1) : nbSample(nb), epsilon(eps), seed(seed_)
         {
@@ -1120,38 +1098,34 @@ struct PointMatcher {
                 throw std::runtime_error("NormalSpaceDataPointsFilter: epsilon must be finite, > 0, <= pi and give at most 65536 buckets (about 1 degree or more)");
             if (seed_ >= (1ULL << 53)) throw std::runtime_error("NormalSpaceDataPointsFilter: seed must be in [0, 2^53)");
         }
-        NormalSpaceDataPointsFilter(const NormalSpaceDataPointsFilter &) = delete;
-        NormalSpaceDataPointsFilter &operator=(const NormalSpaceDataPointsFilter &) = delete;
-        bool ranOnDevice() const { return onDevice; }
         void hostFilter(DataPoints &c)
         {
             const int n = (int)c.features.cols(), rn = c.getDescriptorStartingRow("normals");
             std::vector<int32_t> picks, buckets;
             if (!pgslam_amd::normalspace::host_select<T>(n, [&](int i, int a) { return c.descriptors(rn + a, i); }, (int)nbSample, epsilon, seed, picks, buckets))
                 throw std::runtime_error("NormalSpaceDataPointsFilter: a normal component is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
-            CovarianceSamplingDataPointsFilter::gatherColumns(c, picks.data(), (int)picks.size());
+            gatherColumns(c, picks.data(), (int)picks.size());
         }
         void deviceFilter(DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
             const int rn = c.getDescriptorStartingRow("normals");
-            if (idxBuf.size() < nbSample) idxBuf.resize(nbSample);
+            this->grow(idxBuf, nbSample);
             int kept = 0;
             const int st = pgslam_amd::Abi<T>::normal_space(ctx, c.features.data(), frows, c.descriptors.data() + rn, drows, n, (int)nbSample, epsilon, seed,
                                                             idxBuf.data(), &kept);
             if (st == PGICP_ERR_ARG)
                 throw std::runtime_error("NormalSpaceDataPointsFilter: a normal component is NaN or infinite (put a RemoveNaNDataPointsFilter ahead of it)");
             check(ctx, st);
-            CovarianceSamplingDataPointsFilter::gatherColumns(c, idxBuf.data(), kept);
+            gatherColumns(c, idxBuf.data(), kept);
         }
         void inPlaceFilter(DataPoints &c) override
         {
             onDevice = false;
-            if (!c.descriptorExists("normals") || c.getDescriptorDimension("normals") != 3)
-                throw std::runtime_error("NormalSpaceDataPointsFilter: Error, cannot find normals in descriptors.");
-            if (c.features.rows() != 4) throw std::runtime_error("NormalSpaceDataPointsFilter: only 3-D clouds (4 feature rows) are supported");
+            this->needNormals(c, "NormalSpaceDataPointsFilter");
+            this->need3D(c, "NormalSpaceDataPointsFilter");
             if ((std::size_t)c.features.cols() <= nbSample) return;                 // the no-op: the cloud as it is
-            if (CovarianceSamplingDataPointsFilter::deviceWanted()) { deviceFilter(c); onDevice = true; return; }
+            if (this->deviceWanted("PGSLAM_HOST_INPUT_STAGE")) { deviceFilter(c); onDevice = true; return; }
             hostFilter(c);
         }
     };
@@ -1161,38 +1135,21 @@ struct PointMatcher {
     //! density, as upstream writes it.  The draw is the build's seeded one (not rand()-parity, see RandomSampling).  On the device
     //! (pgicp_max_density_*, the same bits) when there is one, unless PGSLAM_HOST_MAX_DENSITY=1 or the parameters are ones
     //! the device call refuses (maxDensity not > 0, a seed >= 2^53); then the host loop.  ranOnDevice(): which of the two the last inPlaceFilter (or fused pass) took.
-    struct MaxDensityDataPointsFilter : DataPointsFilter {
+    struct MaxDensityDataPointsFilter : DeviceBackedDataPointsFilter {
+        using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         T maxDensity; unsigned long long seed;
-        pgslam_amd::LazyContext ctx;                 // made when the filter first runs on the device, not when a YAML file is read
-        bool onDevice = false;
         std::vector<T> densBuf;                      // the device form's buffers, kept from call to call
         std::vector<int32_t> idxBuf;
         explicit MaxDensityDataPointsFilter(T d = T(10), unsigned long long s = 1) : maxDensity(d), seed(s) {}
-        MaxDensityDataPointsFilter(const MaxDensityDataPointsFilter &) = delete;
-        MaxDensityDataPointsFilter &operator=(const MaxDensityDataPointsFilter &) = delete;
-        bool ranOnDevice() const { return onDevice; }
-        //! a device is present and PGSLAM_HOST_MAX_DENSITY=1 does not force the host loop
         //! what pgicp_max_density_* refuses, checked here: every other refusal of the device call is an error and throws
         bool deviceTakesParameters() const { return maxDensity > T(0) && seed < (1ULL << 53); }
-        static bool deviceWanted()
-        {
-            const char *knob = std::getenv("PGSLAM_HOST_MAX_DENSITY");
-            static const bool have_device = pgicp_device_count() > 0;
-            return have_device && !(knob && std::strcmp(knob, "1") == 0);
-        }
-        //! keeps the columns idx[0 .. kept) (ascending), in order
-        static void keepColumns(DataPoints &c, const int32_t *idx, int kept)
-        {
-            int k = 0;
-            compactColumns(c, [&](int j) { if (k < kept && idx[k] == j) { k++; return true; } return false; });
-        }
         //! the device form (pgicp_max_density_*); false (the cloud untouched) for parameters the device call refuses
         bool deviceFilter(DataPoints &c)
         {
             if (!deviceTakesParameters()) return false;
             const int n = (int)c.features.cols(), rd = c.getDescriptorStartingRow("densities");
-            if (densBuf.size() < (size_t)n) densBuf.resize((size_t)n);
-            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            this->grow(densBuf, (size_t)n);
+            this->grow(idxBuf, (size_t)n);
             for (int i = 0; i < n; i++) densBuf[(size_t)i] = c.descriptors(rd, i);
             int kept = 0;
             check(ctx, pgslam_amd::Abi<T>::max_density(ctx, densBuf.data(), n, (double)maxDensity, (uint64_t)seed, idxBuf.data(), &kept));
@@ -1213,7 +1170,7 @@ struct PointMatcher {
                 if (!(density > maxDensity)) return true;
                 float accept = (float)(maxDensity / density);
                 if (density == last) accept = accept * (float)(1 - saturated / n);
-                return (double)(RandomSamplingDataPointsFilter::mix(seed * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0 < (double)accept;
+                return seededDraw(seed, j) < (double)accept;
             });
         }
         void inPlaceFilter(DataPoints &c) override
@@ -1222,7 +1179,7 @@ struct PointMatcher {
             if (!c.descriptorExists("densities")) throw std::runtime_error("MaxDensityDataPointsFilter: Error, no densities found in descriptors.");
             const int n = (int)c.features.cols();
             if (n == 0) return;
-            if (deviceWanted() && deviceFilter(c)) { onDevice = true; return; }
+            if (this->deviceWanted("PGSLAM_HOST_MAX_DENSITY") && deviceFilter(c)) { onDevice = true; return; }
             hostFilter(c);
         }
         //! SurfaceNormalDataPointsFilter{keepDensities} directly ahead of this filter (DataPointsFilters::apply): both as ONE device
@@ -1233,14 +1190,14 @@ struct PointMatcher {
         bool fusedWith(SurfaceNormalDataPointsFilter &sn, DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            if (n == 0 || frows < 3 || !sn.keepDensities || !deviceWanted() || !deviceTakesParameters() || sn.knn < 3 || sn.knn > 32) return false;
+            if (n == 0 || frows < 3 || !sn.keepDensities || !this->deviceWanted("PGSLAM_HOST_MAX_DENSITY") || !deviceTakesParameters() || sn.knn < 3 || sn.knn > 32) return false;
             for (const char *name : {"normals", "densities", "eigValues"}) if (c.descriptorExists(name)) return false;
             // (a coordinate that is not finite: the device refuses the cloud, and the unfused pair says so as it always did)
             for (int i = 0; i < n; i++)
                 if (!std::isfinite(c.features(0, i)) || !std::isfinite(c.features(1, i)) || !std::isfinite(c.features(2, i))) return false;
             const bool kn = sn.keepNormals, ke = sn.keepEigenValues;
             Matrix ox(frows, n), on(3, kn ? n : 0), oe(3, ke ? n : 0), od(1, n), oc(drows, drows > 0 ? n : 0);
-            if (idxBuf.size() < (size_t)n) idxBuf.resize((size_t)n);
+            this->grow(idxBuf, (size_t)n);
             const double md = std::isfinite((double)sn.maxDist) ? (double)sn.maxDist : 1e300;
             int kept = 0;
             const int st = pgslam_amd::Abi<T>::normals_max_density(sn.ctx, c.features.data(), frows, n, sn.knn, md, (double)maxDensity, (uint64_t)seed,
@@ -1313,69 +1270,68 @@ struct PointMatcher {
                    "SamplingSurfaceNormal, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, NormalSpace, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
                    "(seeded samplers, not rand()-parity))";
         }
+        //! refuses a module that carries a parameter outside `names` (only the filters that always refused one call it)
+        static void allowOnly(const pgslam_amd::yaml_lite::Module &m, std::initializer_list<const char *> names)
+        {
+            for (auto &kv : m.params)
+                if (std::none_of(names.begin(), names.end(), [&](const char *k) { return kv.first == k; }))
+                    throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+        }
         void load(const std::vector<pgslam_amd::yaml_lite::Module> &mods)
         {
             using pgslam_amd::yaml_lite::to_double;
             for (auto &m : mods) {
+                // parameter `k` as a number, `def` when the module does not give it
+                auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                 if (m.name == "IdentityDataPointsFilter") this->push_back(std::make_shared<IdentityDataPointsFilter>());
                 else if (m.name == "MaxDistDataPointsFilter" || m.name == "MinDistDataPointsFilter") {
-                    const int dim = m.params.count("dim") ? (int)to_double(m.params.at("dim"), m.name) : -1;
+                    const int dim = (int)get("dim", "-1");
                     if (dim < -1 || dim > 2) throw std::runtime_error(m.name + ": dim must be -1 (radius), 0, 1 or 2");
                     const T lim = (T)to_double(m.params.count("maxDist") ? m.params.at("maxDist") : m.params.count("minDist") ? m.params.at("minDist") : "1", m.name);
                     this->push_back(std::make_shared<DistLimitDataPointsFilter>(lim, m.name == "MaxDistDataPointsFilter", dim));
                 } else if (m.name == "SurfaceNormalDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return m.params.count(k) ? m.params.at(k) : std::string(def); };
                     // (epsilon > 0 allows an approximate neighbour search upstream; the exact search here meets every allowance)
-                    if (!(to_double(get("epsilon", "0"), m.name) >= 0.0)) throw std::runtime_error(m.name + ": epsilon must be >= 0");
+                    if (!(get("epsilon", "0") >= 0.0)) throw std::runtime_error(m.name + ": epsilon must be >= 0");
                     for (const char *k : {"keepEigenVectors", "keepMatchedIds", "keepMeanDist", "smoothNormals"})
-                        if (to_double(get(k, "0"), m.name) != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");
-                    const int knn = (int)to_double(get("knn", "5"), m.name);
+                        if (get(k, "0") != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");
+                    const int knn = (int)get("knn", "5");
                     if (knn < 3 || knn > 32) throw std::runtime_error(m.name + ": knn must be in [3, 32]");
-                    this->push_back(std::make_shared<SurfaceNormalDataPointsFilter>(knn, (T)to_double(get("maxDist", "inf"), m.name),
-                                                                                     to_double(get("keepNormals", "1"), m.name) != 0.0,
-                                                                                     to_double(get("keepEigenValues", "0"), m.name) != 0.0,
-                                                                                     to_double(get("keepDensities", "0"), m.name) != 0.0));
+                    this->push_back(std::make_shared<SurfaceNormalDataPointsFilter>(knn, (T)get("maxDist", "inf"),
+                                                                                     get("keepNormals", "1") != 0.0,
+                                                                                     get("keepEigenValues", "0") != 0.0,
+                                                                                     get("keepDensities", "0") != 0.0));
                 } else if (m.name == "SamplingSurfaceNormalDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return m.params.count(k) ? m.params.at(k) : std::string(def); };
                     for (const char *k : {"keepDensities", "keepEigenValues", "keepEigenVectors"})
-                        if (to_double(get(k, "0"), m.name) != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");
-                    const double ratio = to_double(get("ratio", "0.5"), m.name), seed = to_double(get("seed", "1"), m.name);
-                    const int knn = (int)to_double(get("knn", "7"), m.name), method = (int)to_double(get("samplingMethod", "0"), m.name);
+                        if (get(k, "0") != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");
+                    const double ratio = get("ratio", "0.5"), seed = get("seed", "1");
+                    const int knn = (int)get("knn", "7"), method = (int)get("samplingMethod", "0");
                     if (!(ratio > 0.0 && ratio < 1.0) || knn < 3 || (method != 0 && method != 1) || !(seed >= 0.0 && seed < 9007199254740992.0))
                         throw std::runtime_error(m.name + ": ratio must be in (0, 1), knn >= 3, samplingMethod 0 or 1, seed in [0, 2^53)");
-                    this->push_back(std::make_shared<SamplingSurfaceNormalDataPointsFilter>((T)ratio, knn, method, (T)to_double(get("maxBoxDim", "inf"), m.name),
-                                                                                             to_double(get("averageExistingDescriptors", "1"), m.name) != 0.0,
-                                                                                             to_double(get("keepNormals", "1"), m.name) != 0.0, (unsigned long long)seed));
+                    this->push_back(std::make_shared<SamplingSurfaceNormalDataPointsFilter>((T)ratio, knn, method, (T)get("maxBoxDim", "inf"),
+                                                                                             get("averageExistingDescriptors", "1") != 0.0,
+                                                                                             get("keepNormals", "1") != 0.0, (unsigned long long)seed));
                 } else if (m.name == "VoxelGridDataPointsFilter") {
-                    auto get = [&](const char *k) { return to_double(m.params.count(k) ? m.params.at(k) : std::string("1"), m.name); };
-                    for (auto &kv : m.params)
-                        if (kv.first != "vSizeX" && kv.first != "vSizeY" && kv.first != "vSizeZ" && kv.first != "useCentroid" && kv.first != "averageExistingDescriptors")
-                            throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    allowOnly(m, {"vSizeX", "vSizeY", "vSizeZ", "useCentroid", "averageExistingDescriptors"});
                     // the three sizes are given together or not at all (1 m each, upstream's defaults): one or two sizes alone would
                     // leave the others at 1 m -- a grid of 0.1 x 1 x 1 m from `vSizeX: 0.1`, which is a typo far more often than a
                     // choice -- so, as VarTrimmedDistOutlierFilter asks for every parameter, that is refused rather than guessed
                     const int given = (int)m.params.count("vSizeX") + (int)m.params.count("vSizeY") + (int)m.params.count("vSizeZ");
                     if (given != 0 && given != 3)
                         throw std::runtime_error(m.name + ": give vSizeX, vSizeY and vSizeZ together (or none of them: 1 m each)");
-                    const double vx = get("vSizeX"), vy = get("vSizeY"), vz = get("vSizeZ");
+                    const double vx = get("vSizeX", "1"), vy = get("vSizeY", "1"), vz = get("vSizeZ", "1");
                     for (double vs : {vx, vy, vz})
                         if (!(vs > 0.0) || !std::isfinite(vs) || !((T)vs > T(0)) || !std::isfinite((T)vs))
                             throw std::runtime_error(m.name + ": vSizeX, vSizeY and vSizeZ must be finite and > 0");
-                    this->push_back(std::make_shared<VoxelGridDataPointsFilter>((T)vx, (T)vy, (T)vz, get("useCentroid") != 0.0, get("averageExistingDescriptors") != 0.0));
+                    this->push_back(std::make_shared<VoxelGridDataPointsFilter>((T)vx, (T)vy, (T)vz, get("useCentroid", "1") != 0.0,
+                                                                                get("averageExistingDescriptors", "1") != 0.0));
                 } else if (m.name == "CovarianceSamplingDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
-                    for (auto &kv : m.params)
-                        if (kv.first != "nbSample" && kv.first != "torqueNorm") throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    allowOnly(m, {"nbSample", "torqueNorm"});
                     const double nb = get("nbSample", "5000"), tn = get("torqueNorm", "1");
                     if (!(nb >= 1.0 && nb <= 2147483647.0) || nb != std::floor(nb) || (tn != 0.0 && tn != 1.0 && tn != 2.0))
                         throw std::runtime_error(m.name + ": nbSample must be an integer in [1, INT_MAX], torqueNorm 0, 1 or 2");
                     this->push_back(std::make_shared<CovarianceSamplingDataPointsFilter>((std::size_t)nb, (int)tn));
                 } else if (m.name == "OctreeGridDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
-                    for (auto &kv : m.params)
-                        if (kv.first != "maxPointByNode" && kv.first != "maxSizeByNode" && kv.first != "samplingMethod" && kv.first != "buildParallel" &&
-                            kv.first != "seed")
-                            throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    allowOnly(m, {"maxPointByNode", "maxSizeByNode", "samplingMethod", "buildParallel", "seed"});
                     // with neither limit given the defaults hold (maxPointByNode 1, maxSizeByNode 0): one leaf a distinct point -- the
                     // cloud comes back whole, reordered, only coincident points merged.  As a list entry that is an omission far more
                     // often than a choice, so, as VoxelGrid refuses one or two sizes alone, that form is refused rather than run
@@ -1391,9 +1347,7 @@ struct PointMatcher {
                     this->push_back(std::make_shared<OctreeGridDataPointsFilter>((std::size_t)mp, (T)ms, (int)sm, get("buildParallel", "1") != 0.0,
                                                                                   (unsigned long long)seed));
                 } else if (m.name == "NormalSpaceDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
-                    for (auto &kv : m.params)
-                        if (kv.first != "nbSample" && kv.first != "epsilon" && kv.first != "seed") throw std::runtime_error(m.name + ": unknown parameter " + kv.first);
+                    allowOnly(m, {"nbSample", "epsilon", "seed"});
                     // upstream's default of 5000 bears no relation to the cloud's size: as a list entry without nbSample it is an
                     // omission far more often than a choice, so, as VoxelGrid and OctreeGrid refuse their bare forms, it is refused
                     if (!m.params.count("nbSample"))
@@ -1407,44 +1361,36 @@ struct PointMatcher {
                                                           "buckets (about 1 degree or more), seed in [0, 2^53)");
                     this->push_back(std::make_shared<NormalSpaceDataPointsFilter>((std::size_t)nb, eps, (unsigned long long)seed));
                 } else if (m.name == "MaxDensityDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double md = get("maxDensity", "10"), seed = get("seed", "1");
                     if (!(md > 0.0) || !(seed >= 0.0 && seed < 9007199254740992.0)) throw std::runtime_error(m.name + ": maxDensity must be positive, seed in [0, 2^53)");
                     this->push_back(std::make_shared<MaxDensityDataPointsFilter>((T)md, (unsigned long long)seed));
                 } else if (m.name == "SimpleSensorNoiseDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double st = get("sensorType", "0"), gain = get("gain", "1");
                     if (st != std::floor(st) || st < 0.0 || st > 4.0 || !(gain >= 1.0)) throw std::runtime_error(m.name + ": sensorType must be 0 ... 4, gain >= 1");
                     this->push_back(std::make_shared<SimpleSensorNoiseDataPointsFilter>((int)st, (T)gain));
                 } else if (m.name == "BoundingBoxDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return (T)to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
-                    const T lo[3] = {get("xMin", "-1"), get("yMin", "-1"), get("zMin", "-1")}, hi[3] = {get("xMax", "1"), get("yMax", "1"), get("zMax", "1")};
-                    this->push_back(std::make_shared<BoundingBoxDataPointsFilter>(lo, hi, get("removeInside", "1") != (T)0));
+                    const T lo[3] = {(T)get("xMin", "-1"), (T)get("yMin", "-1"), (T)get("zMin", "-1")}, hi[3] = {(T)get("xMax", "1"), (T)get("yMax", "1"), (T)get("zMax", "1")};
+                    this->push_back(std::make_shared<BoundingBoxDataPointsFilter>(lo, hi, (T)get("removeInside", "1") != (T)0));
                 } else if (m.name == "RemoveNaNDataPointsFilter") {
                     this->push_back(std::make_shared<RemoveNaNDataPointsFilter>());
                 } else if (m.name == "ObservationDirectionDataPointsFilter") {
-                    auto get = [&](const char *k) { return (T)to_double(m.params.count(k) ? m.params.at(k) : std::string("0"), m.name); };
-                    this->push_back(std::make_shared<ObservationDirectionDataPointsFilter>(get("x"), get("y"), get("z")));
+                    this->push_back(std::make_shared<ObservationDirectionDataPointsFilter>((T)get("x", "0"), (T)get("y", "0"), (T)get("z", "0")));
                 } else if (m.name == "OrientNormalsDataPointsFilter") {
-                    this->push_back(std::make_shared<OrientNormalsDataPointsFilter>(
-                        to_double(m.params.count("towardCenter") ? m.params.at("towardCenter") : std::string("1"), m.name) != 0.0));
+                    this->push_back(std::make_shared<OrientNormalsDataPointsFilter>(get("towardCenter", "1") != 0.0));
                 } else if (m.name == "ShadowDataPointsFilter") {
-                    const double e = to_double(m.params.count("eps") ? m.params.at("eps") : std::string("0.1"), m.name);
+                    const double e = get("eps", "0.1");
                     if (!(e >= 0.0 && e <= 3.14159265358979323846)) throw std::runtime_error(m.name + ": eps must be in [0, pi]");
                     this->push_back(std::make_shared<ShadowDataPointsFilter>((T)e));
                 } else if (m.name == "FixStepSamplingDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double start = get("startStep", "10"), end = get("endStep", "10"), mult = get("stepMult", "1");
                     if (!(start >= 1.0 && start <= 2147483647.0) || !(end >= 1.0 && end <= 2147483647.0) || !(mult > 0.0))
                         throw std::runtime_error(m.name + ": startStep and endStep must be in [1, INT_MAX], stepMult positive");
                     this->push_back(std::make_shared<FixStepSamplingDataPointsFilter>(start, m.params.count("endStep") ? end : start, mult));
                 } else if (m.name == "RandomSamplingDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double prob = get("prob", "0.75"), seed = get("seed", "1");
                     if (!(prob >= 0.0 && prob <= 1.0) || !(seed >= 0.0 && seed < 9007199254740992.0)) throw std::runtime_error(m.name + ": prob must be in [0, 1], seed in [0, 2^53)");
                     this->push_back(std::make_shared<RandomSamplingDataPointsFilter>((T)prob, (unsigned long long)seed));
                 } else if (m.name == "MaxPointCountDataPointsFilter") {
-                    auto get = [&](const char *k, const char *def) { return to_double(m.params.count(k) ? m.params.at(k) : std::string(def), m.name); };
                     const double mc = get("maxCount", "1000"), seed = get("seed", "1");
                     if (!(mc >= 1.0 && mc <= 2147483647.0) || !(seed >= 0.0 && seed < 9007199254740992.0)) throw std::runtime_error(m.name + ": maxCount must be in [1, INT_MAX], seed in [0, 2^53)");
                     this->push_back(std::make_shared<MaxPointCountDataPointsFilter>((unsigned)mc, (unsigned long long)seed));
@@ -1500,14 +1446,9 @@ struct PointMatcher {
                            ? cloud.getDescriptorStartingRow("observationDirections") : -1;
         int kept = 0;
         const T *d = nullptr;
-        const int rc = sizeof(T) == 4
-            ? pgicp_filter_cloud_f32(c, (int)specs.size(), specs.data(), (const float *)cloud.features.data(), (int)cloud.features.rows(),
-                                     drows ? (const float *)cloud.descriptors.data() : nullptr, drows, n, T16, r0, r1, (float *)cloud.features.data(),
-                                     drows ? (float *)cloud.descriptors.data() : nullptr, nullptr, &kept, (const float **)&d)
-            : pgicp_filter_cloud_f64(c, (int)specs.size(), specs.data(), (const double *)cloud.features.data(), (int)cloud.features.rows(),
-                                     drows ? (const double *)cloud.descriptors.data() : nullptr, drows, n, T16, r0, r1, (double *)cloud.features.data(),
-                                     drows ? (double *)cloud.descriptors.data() : nullptr, nullptr, &kept, (const double **)&d);
-        check(c, rc);
+        T *const desc = drows ? cloud.descriptors.data() : nullptr;
+        check(c, A::filter_cloud(c, (int)specs.size(), specs.data(), cloud.features.data(), (int)cloud.features.rows(), desc, drows, n, T16, r0, r1,
+                                 cloud.features.data(), desc, &kept, &d));
         for (auto &f : filters) f->afterDevicePass();               // (a FixStep filter's step moves on, as after inPlaceFilter)
         cloud.features.conservativeResize(cloud.features.rows(), kept);
         if (drows) cloud.descriptors.conservativeResize(drows, kept);
@@ -1549,12 +1490,8 @@ struct PointMatcher {
         for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) if (Tm(i, j) != (i == j ? T(1) : T(0))) return false;
         dropped.resize(4096);
         int nd = 0;
-        const int rc = sizeof(T) == 4
-            ? pgicp_filter_cloud_dev_f32(c, (int)specs.size(), specs.data(), (const float *)cloud.features.data(), (int)cloud.features.rows(), n, dropped.data(),
-                                         (int)dropped.size(), &nd, kept, (const float **)dev)
-            : pgicp_filter_cloud_dev_f64(c, (int)specs.size(), specs.data(), (const double *)cloud.features.data(), (int)cloud.features.rows(), n, dropped.data(),
-                                         (int)dropped.size(), &nd, kept, (const double **)dev);
-        check(c, rc);
+        check(c, A::filter_cloud_dev(c, (int)specs.size(), specs.data(), cloud.features.data(), (int)cloud.features.rows(), n, dropped.data(),
+                                     (int)dropped.size(), &nd, kept, dev));
         if (nd > (int)dropped.size()) { dropped.clear(); return false; }       // (the filters' state has not moved: afterDevicePass was not called)
         dropped.resize((size_t)nd);
         for (auto &f : filters) f->afterDevicePass();

@@ -252,6 +252,63 @@ def _bufs(xs, dtype=None):
     return out
 
 
+def _unempty(a, dtype):
+    """numpy gives an empty array zero strides; the C ABI wants the row stride of a real cloud"""
+    if not _is_torch(a) and np.shape(a)[0] == 0:
+        return np.zeros((1, 3), dtype=dtype or np.asarray(a).dtype)[:0]
+    return a
+
+
+def _host_ptr(t):
+    return None if t is None else C.c_void_p(t.ctypes.data)
+
+
+def _device_ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class _Staged:
+    """The inputs of one filter binding, staged for its C call: `x` (and `nb`) the _Buf views of the cloud (and its normals),
+    `d` / `drows` the descriptors made contiguous in the cloud's memory and dtype, `mk(shape, dtype=None)` an uninitialised
+    output in that memory (`dtype` a numpy dtype; None: the cloud's), `ptr(t)` its address (None for None), `rows(a, idx)` the
+    rows of an input that an int32 output names, `fn(lib, name)` the entry point of the cloud's precision.  Needs no Context
+    and, for numpy inputs, no library."""
+    __slots__ = ("x", "nb", "n", "mem", "dtype", "d", "drows", "mk", "ptr")
+
+    def __init__(self, xyz, normals=None, descriptors=None, dtype=None):
+        x = self.x = _Buf(_unempty(xyz, dtype), dtype)
+        n, dt = self.n, self.dtype = x.n, x.dtype
+        self.mem = x.mem
+        if x.mem == DEVICE:
+            import torch
+            like = x.keep
+            self.mk = lambda shape, dtype=None: torch.empty(shape, dtype=like.dtype if dtype is None else getattr(torch, np.dtype(dtype).name),
+                                                            device=like.device)
+            self.ptr = _device_ptr
+        else:
+            self.mk = lambda shape, dtype=None: np.empty(shape, dtype=dtype or dt)
+            self.ptr = _host_ptr
+        self.nb = None
+        if normals is not None:
+            nb = self.nb = _Buf(_unempty(normals, dt), dt if x.mem == HOST else None)
+            assert nb.n == n and nb.mem == x.mem and nb.dtype == dt
+        self.d, self.drows = None, 0
+        if descriptors is not None:
+            if x.mem == DEVICE:
+                d = descriptors.contiguous()
+                assert d.is_cuda and d.dtype == x.keep.dtype and d.shape[0] == n
+            else:
+                d = np.ascontiguousarray(descriptors, dtype=dt)
+                assert d.ndim == 2 and d.shape[0] == n
+            self.d, self.drows = d, int(d.shape[1])
+
+    def rows(self, a, idx):
+        return a[idx if self.mem == HOST else idx.long()]
+
+    def fn(self, lib, name):
+        return getattr(lib, "pgicp_" + name + ("_f32" if self.dtype == np.float32 else "_f64"))
+
+
 def _T16(T):
     T = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4))
     return (C.c_double * 16)(*T.ravel())
@@ -867,26 +924,16 @@ class Context:
     def surface_normals(self, xyz, knn=10, max_dist=float("inf"), dtype=None, want_eigen=False, want_ids=False):
         """SurfaceNormalDataPointsFilter on the device.  numpy in -> numpy out, torch CUDA in -> torch CUDA out.
         Returns normals (n,3) [, eigenvalues (n,3) ascending] [, ids (n,knn), d2 (n,knn)]."""
-        x = _Buf(xyz, dtype)
-        n = x.n
+        s = _Staged(xyz, dtype=dtype)
+        x, n, mk, ptr = s.x, s.n, s.mk, s.ptr
         md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
-            nrm = mk((n, 3), xyz.dtype)
-            eig = mk((n, 3), xyz.dtype) if want_eigen else None
-            ids = mk((n, knn), torch.int32) if want_ids else None
-            d2 = mk((n, knn), xyz.dtype) if want_ids else None
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            nrm = np.empty((n, 3), dtype=x.dtype)
-            eig = np.empty((n, 3), dtype=x.dtype) if want_eigen else None
-            ids = np.empty((n, knn), dtype=np.int32) if want_ids else None
-            d2 = np.empty((n, knn), dtype=x.dtype) if want_ids else None
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
-        fn = getattr(self.lib, "pgicp_surface_normals" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
-                       ptr(nrm), C.c_int(3), ptr(eig), ptr(ids), ptr(d2)))
+        nrm = mk((n, 3))
+        eig = mk((n, 3)) if want_eigen else None
+        ids = mk((n, knn), np.int32) if want_ids else None
+        d2 = mk((n, knn)) if want_ids else None
+        self._check(s.fn(self.lib, "surface_normals")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+            ptr(nrm), C.c_int(3), ptr(eig), ptr(ids), ptr(d2)))
         out = [nrm]
         if want_eigen:
             out.append(eig)
@@ -900,37 +947,17 @@ class Context:
         CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
         normals (k,3), kept_idx (k,) int32, descriptors (k,drows) or None, boxes: boxes fused) for the k kept points, in
         ascending input index."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-        x = _Buf(xyz, dtype)
-        n = x.n
-        d = None
-        drows = 0
-        if descriptors is not None:
-            if x.mem == DEVICE:
-                d = descriptors.contiguous()
-                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
-            else:
-                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
-                assert d.ndim == 2 and d.shape[0] == n
-            drows = int(d.shape[1])
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
-            ox, on, oi = mk((max(n, 1), 3), xyz.dtype), mk((max(n, 1), 3), xyz.dtype), mk((max(n, 1),), torch.int32)
-            od = mk((max(n, 1), drows), xyz.dtype) if d is not None else None
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            ox, on = np.empty((max(n, 1), 3), dtype=x.dtype), np.empty((max(n, 1), 3), dtype=x.dtype)
-            oi = np.empty(max(n, 1), dtype=np.int32)
-            od = np.empty((max(n, 1), drows), dtype=x.dtype) if d is not None else None
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
+        m = max(n, 1)
+        ox, on, oi = mk((m, 3)), mk((m, 3)), mk((m,), np.int32)
+        od = mk((m, drows)) if d is not None else None
         n_out, boxes = C.c_int(0), C.c_int(0)
-        fn = getattr(self.lib, "pgicp_sampling_surface_normal" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
-                       C.c_int(sampling_method), C.c_double(max_box_dim), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
-                       C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(on), C.c_int(3), ptr(od), ptr(oi),
-                       C.byref(n_out), C.byref(boxes)))
+        self._check(s.fn(self.lib, "sampling_surface_normal")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
+            C.c_int(sampling_method), C.c_double(max_box_dim), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
+            C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(on), C.c_int(3), ptr(od), ptr(oi),
+            C.byref(n_out), C.byref(boxes)))
         k = n_out.value
         return dict(xyz=ox[:k], normals=on[:k], kept_idx=oi[:k], descriptors=od[:k] if od is not None else None, boxes=boxes.value)
 
@@ -939,36 +966,16 @@ class Context:
         CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
         descriptors (k,drows) or None, kept_idx (k,) int32: each voxel's first point, count (k,) int32: its points) for the k
         non-empty voxels, in ascending first-point index."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-        x = _Buf(xyz, dtype)
-        n = x.n
-        d = None
-        drows = 0
-        if descriptors is not None:
-            if x.mem == DEVICE:
-                d = descriptors.contiguous()
-                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
-            else:
-                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
-                assert d.ndim == 2 and d.shape[0] == n
-            drows = int(d.shape[1])
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
-            ox, oi, oc = mk((max(n, 1), 3), xyz.dtype), mk((max(n, 1),), torch.int32), mk((max(n, 1),), torch.int32)
-            od = mk((max(n, 1), drows), xyz.dtype) if d is not None else None
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            ox = np.empty((max(n, 1), 3), dtype=x.dtype)
-            oi, oc = np.empty(max(n, 1), dtype=np.int32), np.empty(max(n, 1), dtype=np.int32)
-            od = np.empty((max(n, 1), drows), dtype=x.dtype) if d is not None else None
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
-        v = (C.c_double * 3)(*[float(s) for s in v_size])
+        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
+        m = max(n, 1)
+        ox, oi, oc = mk((m, 3)), mk((m,), np.int32), mk((m,), np.int32)
+        od = mk((m, drows)) if d is not None else None
+        v = (C.c_double * 3)(*[float(c) for c in v_size])
         n_out = C.c_int(0)
-        fn = getattr(self.lib, "pgicp_voxel_grid" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), v, C.c_int(int(bool(use_centroid))), ptr(d),
-                       C.c_int(drows), C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(od), ptr(oi), ptr(oc), C.byref(n_out)))
+        self._check(s.fn(self.lib, "voxel_grid")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), v, C.c_int(int(bool(use_centroid))), ptr(d),
+            C.c_int(drows), C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(od), ptr(oi), ptr(oc), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k], descriptors=od[:k] if od is not None else None, kept_idx=oi[:k], count=oc[:k])
 
@@ -977,29 +984,21 @@ class Context:
         """SurfaceNormalDataPointsFilter{keepDensities: 1} on the device (pgicp_surface_densities_*): one kernel, no neighbour
         table.  numpy in -> numpy out, torch CUDA in -> torch CUDA out.  Returns dict(normals (n,3) or None, eigen_values (n,3)
         ascending or None, densities (n,))."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-        x = _Buf(xyz, dtype)
-        n = x.n
+        s = _Staged(xyz, dtype=dtype)
+        x, n, mk, ptr = s.x, s.n, s.mk, s.ptr
         md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape: torch.empty(shape, dtype=xyz.dtype, device=xyz.device)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            mk = lambda shape: np.empty(shape, dtype=x.dtype)
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
         nrm = mk((n, 3)) if want_normals else None
         eig = mk((n, 3)) if want_eigen else None
         dens = mk((n,))
-        fn = getattr(self.lib, "pgicp_surface_densities" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
-                       ptr(nrm), C.c_int(3), ptr(eig), ptr(dens)))
+        self._check(s.fn(self.lib, "surface_densities")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+            ptr(nrm), C.c_int(3), ptr(eig), ptr(dens)))
         return dict(normals=nrm, eigen_values=eig, densities=dens)
 
     def max_density(self, densities, max_density=10.0, seed=1, dtype=None):
         """MaxDensityDataPointsFilter's stage on the device (pgicp_max_density_*): the ascending indices (int32) of the points it
-        keeps.  numpy in -> numpy out, torch CUDA in -> torch CUDA out."""
+        keeps.  numpy in -> numpy out, torch CUDA in -> torch CUDA out.  (Its input is one-dimensional, not a cloud, so it stages
+        its own two buffers.)"""
         if _is_torch(densities) and densities.is_cuda:
             import torch
             d = densities.contiguous()
@@ -1022,38 +1021,17 @@ class Context:
         torch CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
         normals (k,3), eigen_values (k,3), densities (k,), descriptors (k,drows) or None, kept_idx (k,) int32) for the k kept
         points, in ascending input index."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-        x = _Buf(xyz, dtype)
-        n = x.n
+        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
         md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
-        d = None
-        drows = 0
-        if descriptors is not None:
-            if x.mem == DEVICE:
-                d = descriptors.contiguous()
-                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
-            else:
-                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
-                assert d.ndim == 2 and d.shape[0] == n
-            drows = int(d.shape[1])
         m = max(n, 1)
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt=None: torch.empty(shape, dtype=dt or xyz.dtype, device=xyz.device)
-            oi = mk((m,), torch.int32)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            mk = lambda shape: np.empty(shape, dtype=x.dtype)
-            oi = np.empty(m, dtype=np.int32)
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
-        ox, on, oe, od = mk((m, x.stride)), mk((m, 3)), mk((m, 3)), mk((m,))
+        ox, on, oe, od, oi = mk((m, x.stride)), mk((m, 3)), mk((m, 3)), mk((m,)), mk((m,), np.int32)
         oc = mk((m, drows)) if d is not None else None
         n_out = C.c_int(0)
-        fn = getattr(self.lib, "pgicp_normals_max_density" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
-                       C.c_double(float(max_density)), C.c_uint64(int(seed)), ptr(d), C.c_int(drows), ptr(ox), ptr(on), C.c_int(3), ptr(oe),
-                       ptr(od), ptr(oc), ptr(oi), C.byref(n_out)))
+        self._check(s.fn(self.lib, "normals_max_density")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+            C.c_double(float(max_density)), C.c_uint64(int(seed)), ptr(d), C.c_int(drows), ptr(ox), ptr(on), C.c_int(3), ptr(oe),
+            ptr(od), ptr(oc), ptr(oi), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], eigen_values=oe[:k], densities=od[:k],
                     descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k])
@@ -1066,51 +1044,26 @@ class Context:
         the k = min(n, nb_sample) picks, in pick order; frame = dict(center (3,), L, eigenvalues (6,) ascending, basis (6,6):
         eigenvectors as columns).  `frame` given: the selection stage alone (pgicp_covariance_sampling_framed_*) -- kept_idx is
         the stage's, the rows are gathered from it here, the frame comes back as given."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-            normals = np.zeros((1, 3), dtype=xyz.dtype)[:0]
-        x = _Buf(xyz, dtype)
-        nb = _Buf(normals, x.dtype if x.mem == HOST else None)
-        n = x.n
-        assert nb.n == n and nb.mem == x.mem and nb.dtype == x.dtype
-        d = None
-        drows = 0
-        if descriptors is not None:
-            if x.mem == DEVICE:
-                d = descriptors.contiguous()
-                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
-            else:
-                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
-                assert d.ndim == 2 and d.shape[0] == n
-            drows = int(d.shape[1])
+        s = _Staged(xyz, normals, descriptors, dtype)
+        x, nb, n, d, drows, mk, ptr = s.x, s.nb, s.n, s.d, s.drows, s.mk, s.ptr
         m = max(min(n, int(nb_sample)), 1)
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt=None: torch.empty(shape, dtype=dt or xyz.dtype, device=xyz.device)
-            oi = mk((m,), torch.int32)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            mk = lambda shape: np.empty(shape, dtype=x.dtype)
-            oi = np.empty(m, dtype=np.int32)
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        oi = mk((m,), np.int32)
         n_out = C.c_int(0)
         if frame is not None:
             fr = CovFrame.from_dict(frame)
-            fn = getattr(self.lib, "pgicp_covariance_sampling_framed" + self._sfx(x.dtype))
-            self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
-                           C.c_int(int(nb_sample)), C.byref(fr), ptr(oi), C.byref(n_out)))
-            k = n_out.value
-            idx = oi[:k]
-            sel = idx.long() if x.mem == DEVICE else idx
-            return dict(xyz=x.keep[sel][:, :3], normals=nb.keep[sel][:, :3], descriptors=d[sel] if d is not None else None, kept_idx=idx,
-                        frame=fr.as_dict())
+            self._check(s.fn(self.lib, "covariance_sampling_framed")(
+                self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
+                C.c_int(int(nb_sample)), C.byref(fr), ptr(oi), C.byref(n_out)))
+            idx = oi[:n_out.value]
+            return dict(xyz=s.rows(x.keep, idx)[:, :3], normals=s.rows(nb.keep, idx)[:, :3],
+                        descriptors=s.rows(d, idx) if d is not None else None, kept_idx=idx, frame=fr.as_dict())
         ox, on = mk((m, x.stride)), mk((m, 3))
         oc = mk((m, drows)) if d is not None else None
         fr = CovFrame()
-        fn = getattr(self.lib, "pgicp_covariance_sampling" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
-                       C.c_int(int(nb_sample)), C.c_int(int(torque_norm)), ptr(d), C.c_int(drows), ptr(ox), ptr(on), C.c_int(3), ptr(oc), ptr(oi),
-                       C.byref(n_out), C.byref(fr)))
+        self._check(s.fn(self.lib, "covariance_sampling")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
+            C.c_int(int(nb_sample)), C.c_int(int(torque_norm)), ptr(d), C.c_int(drows), ptr(ox), ptr(on), C.c_int(3), ptr(oc), ptr(oi),
+            C.byref(n_out), C.byref(fr)))
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k], frame=fr.as_dict())
 
@@ -1121,37 +1074,16 @@ class Context:
         first point, 1 random (seeded), 2 centroid, 3 medoid.  Returns dict(xyz (k,3), descriptors (k,drows) or None, kept_idx (k,)
         int32: the leaf's first point for method 2, the kept point otherwise, count (k,) int32: the leaf's points, depth (k,)
         int32: the leaf's depth) for the k non-empty leaves, in depth-first leaf order."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-        x = _Buf(xyz, dtype)
-        n = x.n
-        d = None
-        drows = 0
-        if descriptors is not None:
-            if x.mem == DEVICE:
-                d = descriptors.contiguous()
-                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
-            else:
-                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
-                assert d.ndim == 2 and d.shape[0] == n
-            drows = int(d.shape[1])
+        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
         m = max(n, 1)
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=xyz.device)
-            ox, oi, oc, op = mk((m, 3), xyz.dtype), mk((m,), torch.int32), mk((m,), torch.int32), mk((m,), torch.int32)
-            od = mk((m, drows), xyz.dtype) if d is not None else None
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            ox = np.empty((m, 3), dtype=x.dtype)
-            oi, oc, op = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
-            od = np.empty((m, drows), dtype=x.dtype) if d is not None else None
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
+        ox, oi, oc, op = mk((m, 3)), mk((m,), np.int32), mk((m,), np.int32), mk((m,), np.int32)
+        od = mk((m, drows)) if d is not None else None
         n_out = C.c_int(0)
-        fn = getattr(self.lib, "pgicp_octree_grid" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(int(max_point_by_node)),
-                       C.c_double(float(max_size_by_node)), C.c_int(int(sampling_method)), C.c_ulonglong(int(seed)), ptr(d), C.c_int(drows), ptr(ox),
-                       C.c_int(3), ptr(od), ptr(oi), ptr(oc), ptr(op), C.byref(n_out)))
+        self._check(s.fn(self.lib, "octree_grid")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(int(max_point_by_node)),
+            C.c_double(float(max_size_by_node)), C.c_int(int(sampling_method)), C.c_uint64(int(seed)), ptr(d), C.c_int(drows), ptr(ox),
+            C.c_int(3), ptr(od), ptr(oi), ptr(oc), ptr(op), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k], descriptors=od[:k] if od is not None else None, kept_idx=oi[:k], count=oc[:k], depth=op[:k])
 
@@ -1161,40 +1093,16 @@ class Context:
         numpy in -> numpy out, torch CUDA in -> torch CUDA out.  `normals` (n, >= 3) and `descriptors` ((n, drows) or None) in the
         same memory as xyz.  Returns dict(xyz (k,3), normals (k,3), descriptors (k,drows) or None, kept_idx (k,) int32, bucket (k,)
         int32: the pick's bucket, -1 for the no-op) for the k = min(n, nb_sample) picks, in pick order."""
-        if not _is_torch(xyz) and np.shape(xyz)[0] == 0:           # (numpy gives an empty array zero strides)
-            xyz = np.zeros((1, 3), dtype=dtype or np.asarray(xyz).dtype)[:0]
-            normals = np.zeros((1, 3), dtype=xyz.dtype)[:0]
-        x = _Buf(xyz, dtype)
-        nb = _Buf(normals, x.dtype if x.mem == HOST else None)
-        n = x.n
-        assert nb.n == n and nb.mem == x.mem and nb.dtype == x.dtype
-        d = None
-        drows = 0
-        if descriptors is not None:
-            if x.mem == DEVICE:
-                d = descriptors.contiguous()
-                assert d.is_cuda and d.dtype == xyz.dtype and d.shape[0] == n
-            else:
-                d = np.ascontiguousarray(descriptors, dtype=x.dtype)
-                assert d.ndim == 2 and d.shape[0] == n
-            drows = int(d.shape[1])
+        s = _Staged(xyz, normals, descriptors, dtype)
+        x, nb, n, d, drows, mk, ptr = s.x, s.nb, s.n, s.d, s.drows, s.mk, s.ptr
         m = max(min(n, max(int(nb_sample), 0)), 1)
-        if x.mem == DEVICE:
-            import torch
-            mk = lambda shape, dt=None: torch.empty(shape, dtype=dt or xyz.dtype, device=xyz.device)
-            oi, ob = mk((m,), torch.int32), mk((m,), torch.int32)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            mk = lambda shape: np.empty(shape, dtype=x.dtype)
-            oi, ob = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
-            ptr = lambda t: C.c_void_p(t.ctypes.data) if t is not None else None
-        ox, on = mk((m, x.stride)), mk((m, 3))
+        ox, on, oi, ob = mk((m, x.stride)), mk((m, 3)), mk((m,), np.int32), mk((m,), np.int32)
         oc = mk((m, drows)) if d is not None else None
         n_out = C.c_int(0)
-        fn = getattr(self.lib, "pgicp_normal_space_sampling" + self._sfx(x.dtype))
-        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
-                       C.c_int(int(nb_sample)), C.c_double(float(epsilon)), C.c_ulonglong(int(seed)), ptr(d), C.c_int(drows), ptr(ox), ptr(on),
-                       C.c_int(3), ptr(oc), ptr(oi), ptr(ob), C.byref(n_out)))
+        self._check(s.fn(self.lib, "normal_space_sampling")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(n), C.c_int(x.mem),
+            C.c_int(int(nb_sample)), C.c_double(float(epsilon)), C.c_uint64(int(seed)), ptr(d), C.c_int(drows), ptr(ox), ptr(on),
+            C.c_int(3), ptr(oc), ptr(oi), ptr(ob), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k], bucket=ob[:k])
 

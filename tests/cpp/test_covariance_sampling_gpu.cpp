@@ -18,7 +18,7 @@ void run_forms(const char *name)
         cs.hostPicks(base, cs.lastFrame, picks);
         CHECK(picks.size() == 800);
         typename PM::DataPoints hst(base);
-        PM::CovarianceSamplingDataPointsFilter::gatherColumns(hst, picks.data(), 800);
+        PM::gatherColumns(hst, picks.data(), 800);
         CHECK(std::memcmp(dev.features.data(), hst.features.data(), sizeof(T) * 4 * 800) == 0);
         CHECK(std::memcmp(dev.descriptors.data(), hst.descriptors.data(), sizeof(T) * 3 * 800) == 0);
         // the knob: the host form from end to end; its frame sums in index order, so only the sizes are compared

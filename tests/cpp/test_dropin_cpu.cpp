@@ -4,6 +4,30 @@
 // "no CPU fallback" rule: constructing an ICP object without a GPU must throw.
 #include "common.hpp"
 #include <limits>
+#include <type_traits>
+
+// what the shared pieces promise for every device-backed input filter, in both precisions: each owns a device context, so
+// none is copyable, each is a DataPointsFilter, and Abi<T>'s forwarders take the cloud in T (voxel_grid stands for all)
+template <typename Base, typename F>
+constexpr bool sound()
+{
+    return !std::is_copy_constructible<F>::value && !std::is_copy_assignable<F>::value && std::is_base_of<Base, F>::value;
+}
+template <typename T>
+struct SharedPieces {
+    using PM = PointMatcher<T>;
+    static_assert(sound<typename PM::DataPointsFilter, typename PM::SamplingSurfaceNormalDataPointsFilter>(), "SamplingSurfaceNormalDataPointsFilter");
+    static_assert(sound<typename PM::DataPointsFilter, typename PM::VoxelGridDataPointsFilter>(), "VoxelGridDataPointsFilter");
+    static_assert(sound<typename PM::DataPointsFilter, typename PM::CovarianceSamplingDataPointsFilter>(), "CovarianceSamplingDataPointsFilter");
+    static_assert(sound<typename PM::DataPointsFilter, typename PM::OctreeGridDataPointsFilter>(), "OctreeGridDataPointsFilter");
+    static_assert(sound<typename PM::DataPointsFilter, typename PM::NormalSpaceDataPointsFilter>(), "NormalSpaceDataPointsFilter");
+    static_assert(sound<typename PM::DataPointsFilter, typename PM::MaxDensityDataPointsFilter>(), "MaxDensityDataPointsFilter");
+    static_assert(std::is_same<decltype(&pgslam_amd::Abi<T>::voxel_grid),
+                               int (*)(pgicp_ctx *, const T *, int, int, const double *, int, const T *, int, int, T *, T *, int32_t *, int *)>::value,
+                  "Abi<T>::voxel_grid takes the cloud, the descriptors and the outputs in T");
+};
+template struct SharedPieces<float>;
+template struct SharedPieces<double>;
 
 template <typename T>
 void type_spelling()
