@@ -1756,6 +1756,14 @@ static void FN(covariance_ko)(const real *p, int n, int K, const real *ref_xyz, 
         for (int r = c + 1; r < 6; r++) if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
         if (piv != c) for (int j = 0; j < 12; j++) { double t = M[c][j]; M[c][j] = M[piv][j]; M[piv][j] = t; }
         const double d = M[c][c];
+        if (d == 0.0) {
+            /* H is exactly singular (every pivot candidate of this column is 0: a plane with one constant normal in exact
+             * arithmetic): there is no inverse.  The library states "no information" as the largest double on the diagonal,
+             * zeros elsewhere (api_icp.inc, align_batch); dividing by the zero pivot here gave NaN in all 36 entries. */
+            for (int i = 0; i < 36; i++) cov[i] = 0.0;
+            for (int i = 0; i < 6; i++) cov[i * 6 + i] = DBL_MAX;
+            return;
+        }
         for (int j = 0; j < 12; j++) M[c][j] /= d;
         for (int r = 0; r < 6; r++) {
             if (r == c) continue;

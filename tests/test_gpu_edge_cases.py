@@ -153,10 +153,15 @@ def test_lazy_matcher_state_equals_oracle_every_iteration(ctx, oracle32):
     ctx.destroy_map(m)
 
 
-@pytest.mark.parametrize("n", [1, 2, 63, 2047, 2048, 2049, 4097, 30011])
+@pytest.mark.parametrize("n", [1, 2, 63, 2047, 2048, 2049, 4097, 30011, 32768, 32769, 43264])
 def test_outlier_selection_sizes_and_ratios(ctx, oracle32, n):
-    """The chip-wide trimmed-distance selection (histogram -> filter -> finish) at sizes around its 2048-point
-    tiles and with several ratios, in one ragged batch: threshold, kept and finite counts equal the oracle's."""
+    """The trimmed-distance selection at sizes around its 2048-point tiles and with several ratios, in one ragged batch:
+    threshold, kept and finite counts equal the oracle's.  Which kernel a size reaches at default knobs: up to 32 768
+    distances in the batch's largest problem (PGICP_SEL_SMALL_N) one block per problem selects (k_sel_small); 32 769 and
+    43 264 take the chip-wide selection (k_sel_hist -> k_sel_filter -> k_sel_final) in every selection of both iterations
+    -- with two problems the batch is below the four from which a guessed selection (k_sel_band) is used.  Under
+    PGICP_SEL_SMALL_N=0 (tests/test_gpu_knobs.py) every size takes the chip-wide one, under PGICP_SEL_BAND=1 with it the
+    guessed one from the second selection on."""
     t = synth.make_two_scans(max(n, 3000), rings=16)
     ref, nrm, T0 = t["ref_xyz"], t["ref_nrm"], t["T_init"]
     rd = t["reading_xyz"][:n].copy()

@@ -35,11 +35,19 @@ SETTINGS = [
 ]
 
 
+# The exact-arithmetic scenes whose expectations do not depend on the knobs: the selection without a guess (A) and the pair
+# sums (E).  B, C and D of that file assert which selection path ran (fallback counter, stage shape): default knobs only.
+EXACT_SCENES = ["tests/test_gpu_exact_scenes.py::" + t for t in (
+    "test_a_wide_selection_without_a_guess", "test_a_wide_selection_all_keys_distinct_f64", "test_e_error_stats_at_every_edge", "test_e_chain_batch_at_every_edge_both_orders",
+    "test_e_chain_batch_three_neighbours", "test_e_normal_filter_in_the_sums")]
+
+
 @pytest.mark.parametrize("setting", SETTINGS, ids=lambda s: ",".join(f"{k[6:]}={v}" for k, v in s.items()))
 def test_parity_holds_for_every_knob_setting(setting):
     env = dict(os.environ, **setting)
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_edge_cases.py", "tests/test_gpu_matcher_state.py", "tests/test_local_mapper.py", "tests/test_gpu_chain.py",
                         "tests/test_gpu_bit_exact.py", "tests/test_gpu_parity.py::test_seeded_partial_chain_equals_the_unseeded_one",
+                        *EXACT_SCENES,
                         "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
