@@ -605,6 +605,53 @@ int fetch_rows3(pgicp_ctx *c, T *out, int stride, const T *dev, int count, RowSp
     return d2h(c, late.jobs.back().tmp.data(), dev, sizeof(T) * vals);
 }
 
+// ---- the two ends VoxelGrid and OctreeGrid share ----
+// the order-preserving key of k_vox_bounds back to the value
+template <typename T>
+static T vox_unkey(unsigned long long k)
+{
+    if constexpr (sizeof(T) == 4) {
+        const uint32_t u = (uint32_t)k, b = (u & 0x80000000u) ? (u ^ 0x80000000u) : ~u;
+        float f; std::memcpy(&f, &b, 4); return f;
+    } else {
+        const uint64_t b = (k & 0x8000000000000000ULL) ? (k ^ 0x8000000000000000ULL) : ~k;
+        double d; std::memcpy(&d, &b, 8); return d;
+    }
+}
+// The bounds step: dpf_stat holds the call's VoxStat (*stat; launch_voxel_bounds zeroes its counters), one round trip brings each
+// axis's min and max back, in T.  A coordinate that is not finite fails the call of `who` (pgicp_<name>).
+template <typename T>
+int cloud_bounds(pgicp_ctx *c, const char *who, const T *d_xyz, int stride, int n, VoxStat **stat, T lo[3], T hi[3])
+{
+    HIPC(c, c->dpf_stat.ensure(sizeof(VoxStat)));
+    *stat = c->dpf_stat.as<VoxStat>();
+    VoxStat h;
+    launch_voxel_bounds<T>(c->stream, d_xyz, stride, n, *stat);
+    XFER(c, read_back(c, &h, *stat, sizeof h));
+    if (h.bad) return fail(c, PGICP_ERR_ARG, std::string(who) + ": a coordinate is NaN or infinite");
+    for (int a = 0; a < 3; a++) { lo[a] = vox_unkey<T>(h.lo[a]); hi[a] = vox_unkey<T>(h.hi[a]); }
+    return PGICP_OK;
+}
+// The tail: the kept count back, then -- host memory -- the packed device outputs into the caller's arrays: the coordinates, `dr`
+// descriptor rows, and each (host, device) pair of int32_t arrays whose host side is not null
+template <typename T>
+int fetch_kept(pgicp_ctx *c, int mem, const VoxStat *stat, T *out_xyz, int out_stride, const T *d_ox, T *out_desc, const T *d_od, int dr,
+               std::initializer_list<std::pair<int32_t *, const int32_t *>> ints, int *n_out)
+{
+    int kept = 0;
+    XFER(c, read_back(c, &kept, &stat->kept, sizeof kept));
+    if (mem == PGICP_HOST && kept > 0) {
+        RowSpread<T> late;
+        XFER(c, fetch_rows3<T>(c, out_xyz, out_stride, d_ox, kept, late));
+        if (dr) XFER(c, d2h(c, out_desc, d_od, sizeof(T) * (size_t)dr * kept));
+        for (const auto &io : ints)
+            if (io.first) XFER(c, d2h(c, io.first, io.second, sizeof(int32_t) * (size_t)kept));
+        XFER(c, late.land(c));
+    }
+    *n_out = kept;
+    return PGICP_OK;
+}
+
 static int pinned_ensure(pgicp_ctx *c, char **buf, size_t *cap, size_t bytes)
 {
     if (bytes <= *cap) return PGICP_OK;

@@ -100,7 +100,7 @@ int covariance_sampling(pgicp_ctx *c, const char *who, const T *xyz, int stride,
         d_picks = w.picks;
         if (frame_out) *frame_out = frame;
     }
-    launch_cov_gather<T>(c->stream, d_picks, m, n, in.xyz, stride, d_nrm, nstride, in.desc, dr, d_ox, stride, d_on, ons, d_od, d_oi);
+    launch_gather_rows<T>(c->stream, d_picks, nullptr, nullptr, m, n, in.xyz, stride, d_nrm, nstride, in.desc, dr, d_ox, stride, d_on, ons, d_od, d_oi, nullptr);
     if (mem == PGICP_HOST) {
         RowSpread<T> late;
         XFER(c, fetch_rows3<T>(c, out_xyz, stride, d_ox, m, late, stride));

@@ -67,9 +67,9 @@ int normal_space_sampling(pgicp_ctx *c, const T *xyz, int stride, const T *nrm, 
         nsp::draw(counts.data(), grid.nbBucket, m, seed, pb, pr);
         for (int j = 0; j < m; j++) pr[(size_t)j] += start[(size_t)pb[(size_t)j]];            // the position in the sorted order
         XFER(c, h2d(c, w.pos, pr.data(), sizeof(int32_t) * (size_t)m));
-        d_pos = w.pos; d_skey = w.key[cur]; d_sidx = w.idx[cur];
+        d_pos = w.pos; d_skey = w.sort.key[cur]; d_sidx = w.sort.idx[cur];
     }
-    launch_ns_gather<T>(c->stream, d_pos, d_skey, d_sidx, m, n, in.xyz, stride, d_nrm, nstride, in.desc, dr, d_ox, stride, d_on, ons, d_od, d_oi, d_ob);
+    launch_gather_rows<T>(c->stream, d_pos, d_skey, d_sidx, m, n, in.xyz, stride, d_nrm, nstride, in.desc, dr, d_ox, stride, d_on, ons, d_od, d_oi, d_ob);
     if (mem == PGICP_HOST) {
         RowSpread<T> late;
         XFER(c, fetch_rows3<T>(c, out_xyz, stride, d_ox, m, late, stride));

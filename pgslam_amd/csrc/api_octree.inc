@@ -21,7 +21,6 @@ int octree_grid(pgicp_ctx *c, const T *xyz, int stride, int n, int mem, int max_
     const int dr = desc ? drows : 0;
     OctScratch w;
     XFER(c, carve_buf(c, c->dpf_work, [&](Carve &cv) { w = oct_scratch(cv, n); }));
-    HIPC(c, c->dpf_stat.ensure(sizeof(VoxStat)));
     CloudIn<T> in;
     T *d_ox = out_xyz, *d_od = out_desc;
     int32_t *d_oi = kept_idx, *d_oc = out_count, *d_odp = out_depth;
@@ -39,35 +38,15 @@ int octree_grid(pgicp_ctx *c, const T *xyz, int stride, int n, int mem, int max_
         os = 3;
     }
     XFER(c, upload_cloud<T>(c, mem, xyz, stride, n, desc, dr, in));
-    VoxStat *stat = c->dpf_stat.as<VoxStat>();
-    VoxStat h;
-    launch_voxel_bounds<T>(c->stream, in.xyz, stride, n, stat);
-    XFER(c, read_back(c, &h, stat, sizeof h));
-    if (h.bad) return fail(c, PGICP_ERR_ARG, "pgicp_octree_grid: a coordinate is NaN or infinite");
+    VoxStat *stat;
     T lo[3], hi[3];
-    for (int a = 0; a < 3; a++) { lo[a] = vox_unkey<T>(h.lo[a]); hi[a] = vox_unkey<T>(h.hi[a]); }
-    const pgslam_amd::octree::Root<T> Rh = pgslam_amd::octree::make_root<T>(lo, hi, ms);
-    OctRoot<T> R;
-    for (int a = 0; a < 3; a++) R.c[a] = Rh.c[a];
-    R.r = Rh.r;
-    R.levels = Rh.levels;
+    XFER(c, cloud_bounds<T>(c, "pgicp_octree_grid", in.xyz, stride, n, &stat, lo, hi));
+    const OctRoot<T> R = pgslam_amd::octree::make_root<T>(lo, hi, ms);
     {
         ProfScope ps(c, PGICP_PROF_NORMALS, n);
         launch_octree_grid<T>(c->stream, in.xyz, stride, n, R, max_pts, method, seed, in.desc, dr, w, d_ox, os, d_od, d_oi, d_oc, d_odp, stat);
     }
-    int kept = 0;
-    XFER(c, read_back(c, &kept, &stat->kept, sizeof kept));
-    if (mem == PGICP_HOST && kept > 0) {
-        RowSpread<T> late;
-        XFER(c, fetch_rows3<T>(c, out_xyz, out_stride, d_ox, kept, late));
-        if (desc) XFER(c, d2h(c, out_desc, d_od, sizeof(T) * (size_t)dr * kept));
-        if (kept_idx) XFER(c, d2h(c, kept_idx, d_oi, sizeof(int32_t) * (size_t)kept));
-        if (out_count) XFER(c, d2h(c, out_count, d_oc, sizeof(int32_t) * (size_t)kept));
-        if (out_depth) XFER(c, d2h(c, out_depth, d_odp, sizeof(int32_t) * (size_t)kept));
-        XFER(c, late.land(c));
-    }
-    *n_out = kept;
-    return PGICP_OK;
+    return fetch_kept<T>(c, mem, stat, out_xyz, out_stride, d_ox, out_desc, d_od, dr, {{kept_idx, d_oi}, {out_count, d_oc}, {out_depth, d_odp}}, n_out);
 }
 
 }  // namespace

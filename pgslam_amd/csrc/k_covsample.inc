@@ -15,7 +15,7 @@
 //           key and rank = how many of its ties belong to the list.  k_cov_flag marks the ties, ONE scan ranks them (any number:
 //           a planar cloud makes a whole list equal), k_cov_emit writes each list's entries through a cursor -- in no order: the
 //           host sorts them by (value, index), a total order.
-//   pass 5  k_cov_gather: the picks' coordinates, normals and descriptor rows.
+//   pass 5  k_gather_rows: the picks' coordinates, normals and descriptor rows (NormalSpace's gather too, through its sort).
 
 template <int MODE> struct CovMode;
 // nv values a row of partials, the first nsum of them sums (the rest maxima), the first ndd of those carried as (sum, error):
@@ -302,21 +302,29 @@ __global__ __launch_bounds__(256) void k_cov_emit(const T *__restrict__ v, int n
     }
 }
 
+// out[j] = in[i]: i = pos[j], or -- through a pair sort's result -- i = sidx[pos[j]] with the bucket skey[pos[j]] >> 24
 template <typename T>
-__global__ __launch_bounds__(256) void k_cov_gather(const int *__restrict__ picks, int m, int n, const T *__restrict__ X, int xs,
-                                                    const T *__restrict__ N, int ns, const T *__restrict__ desc, int drows,
-                                                    T *__restrict__ out_xyz, int os, T *__restrict__ out_nrm, int ons,
-                                                    T *__restrict__ out_desc, int *__restrict__ kept_idx)
+__global__ __launch_bounds__(256) void k_gather_rows(const int *__restrict__ pos, const unsigned long long *__restrict__ skey, const int *__restrict__ sidx,
+                                                     int m, int n, const T *__restrict__ X, int xs, const T *__restrict__ N, int ns,
+                                                     const T *__restrict__ desc, int drows, T *__restrict__ out_xyz, int os, T *__restrict__ out_nrm,
+                                                     int ons, T *__restrict__ out_desc, int *__restrict__ kept_idx, int *__restrict__ bucket_out)
 {
     const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
-    const long long i = picks ? picks[j] : j;
+    long long i = pos ? pos[j] : j;
+    int b = -1;
+    if (pos && sidx) {
+        if (i < 0 || i >= n) return;
+        b = (int)(skey[i] >> 24);
+        i = sidx[i];
+    }
     if (i < 0 || i >= n) return;
     if (out_xyz) { const T *x = X + i * xs; T *o = out_xyz + j * os; o[0] = x[0]; o[1] = x[1]; o[2] = x[2]; }
     if (out_nrm) { const T *x = N + i * ns; T *o = out_nrm + j * ons; o[0] = x[0]; o[1] = x[1]; o[2] = x[2]; }
     if (out_desc)
         for (int r = 0; r < drows; r++) out_desc[j * drows + r] = desc[i * drows + r];
     if (kept_idx) kept_idx[j] = (int)i;
+    if (bucket_out) bucket_out[j] = b;
 }
 
 // ---- launchers ----
@@ -362,19 +370,19 @@ void launch_cov_select(hipStream_t st, const T *X, int xs, const T *N, int ns, i
 }
 
 template <typename T>
-void launch_cov_gather(hipStream_t st, const int *picks, int m, int n, const T *X, int xs, const T *N, int ns, const T *desc, int drows, T *out_xyz,
-                       int os, T *out_nrm, int ons, T *out_desc, int *kept_idx)
+void launch_gather_rows(hipStream_t st, const int *pos, const unsigned long long *skey, const int *sidx, int m, int n, const T *X, int xs, const T *N,
+                        int ns, const T *desc, int drows, T *out_xyz, int os, T *out_nrm, int ons, T *out_desc, int *kept_idx, int *bucket_out)
 {
-    hipLaunchKernelGGL(k_cov_gather<T>, dim3(cdiv(m, 256)), dim3(256), 0, st, picks, m, n, X, xs, N, ns, desc, drows, out_xyz, os, out_nrm, ons,
-                       desc ? out_desc : (T *)nullptr, kept_idx);
+    hipLaunchKernelGGL(k_gather_rows<T>, dim3(cdiv(m, 256)), dim3(256), 0, st, pos, skey, sidx, m, n, X, xs, N, ns, desc, drows, out_xyz, os, out_nrm, ons,
+                       desc ? out_desc : (T *)nullptr, kept_idx, bucket_out);
 }
 
 #define INSTANTIATE_COVSAMPLE(T)                                                                                                       \
     template void launch_cov_frame<T>(hipStream_t, const T *, int, const T *, int, int, int, const CovScratch &, CovStat *);          \
     template void launch_cov_select<T>(hipStream_t, const T *, int, const T *, int, int, const CovFrameDev<T> &, int, const CovScratch &, \
                                        CovStat *);                                                                                   \
-    template void launch_cov_gather<T>(hipStream_t, const int *, int, int, const T *, int, const T *, int, const T *, int, T *, int, T *, int, \
-                                       T *, int *);
+    template void launch_gather_rows<T>(hipStream_t, const int *, const unsigned long long *, const int *, int, int, const T *, int, const T *, \
+                                        int, const T *, int, T *, int, T *, int, T *, int *, int *);
 INSTANTIATE_COVSAMPLE(float)
 INSTANTIATE_COVSAMPLE(double)
 #undef INSTANTIATE_COVSAMPLE

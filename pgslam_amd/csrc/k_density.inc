@@ -8,7 +8,7 @@
 //      sign of a zero maximum does not matter.  An order-preserving bit key, a block reduction and one atomicMax a block, as
 //      k_gd_max does it; whether dens[0] is a NaN is noted apart;
 //   2. k_md_count: saturated = #{dens[i] == last}: ballot, popcount, one integer add a block;
-//   3. k_md_keep: the keep flag of every point, the draw being k_filter.inc's splitmix on the point's index;
+//   3. k_md_keep: the keep flag of every point, the draw being k_filter.inc's seeded_mix on the point's index;
 //   4. the three scan kernels of k_build.inc rank the flags, k_filter_compact moves the coordinates, the carried descriptor rows
 //      and the kept indices, k_density_compact the rows the normals kernel made (normals, eigenvalues, densities).
 // DensStat (kernels.hpp): key = the largest order-preserving key of a non-NaN density (0: none seen); saturated; first_nan.
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_md_keep(const T *__restrict__ dens, int
     if (d > max_density) {
         float accept = (float)(max_density / d);
         if (d == md_last<T>(*stat)) accept = accept * (float)(1 - stat->saturated / n);       // INTEGER division, as upstream writes it
-        k = (double)(splitmix(seed * 0x100000001B3ULL + (unsigned long long)i) >> 11) / 9007199254740992.0 < (double)accept ? 1 : 0;
+        k = (double)(seeded_mix(seed, i) >> 11) / 9007199254740992.0 < (double)accept ? 1 : 0;
     }
     keep[i] = k;
 }

@@ -66,6 +66,8 @@ __device__ __forceinline__ unsigned long long splitmix(unsigned long long z)
     z += 0x9E3779B97F4A7C15ULL; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
     return z ^ (z >> 31);
 }
+// the hash behind every seeded draw: element i of seed's stream.  The caller takes its bits (>> 11 for a double in [0, 1), ...)
+__device__ __forceinline__ unsigned long long seeded_mix(unsigned long long seed, unsigned long long i) { return splitmix(seed * 0x100000001B3ULL + i); }
 
 // one index-dependent filter: `rank` = the point's index in the cloud this filter is handed (exclusive scan of the flags)
 __global__ __launch_bounds__(256) void k_filter_index(int n, FilterDev f, const int *__restrict__ rank, int *__restrict__ keep)
@@ -76,13 +78,13 @@ __global__ __launch_bounds__(256) void k_filter_index(int n, FilterDev f, const 
     bool ok = true;
     if (f.type == PGICP_F_FIX_STEP) ok = j % (int)f.p[0] == 0;
     else if (f.type == PGICP_F_RANDOM_SAMPLING)
-        ok = (double)(splitmix((unsigned long long)f.p[1] * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0 < f.p[0];
+        ok = (double)(seeded_mix((unsigned long long)f.p[1], j) >> 11) / 9007199254740992.0 < f.p[0];
     else if (f.type == PGICP_F_MAX_POINT_COUNT) {
         // [EXT] MaxPointCount.cpp (the vintage pgslam was written against): only when maxCount < N, a random sample with
         // prob = T(maxCount) / T(N); N = the points this filter is handed = rank[n]; prob_bits: that quotient, made by the host in T
         const int total = rank[n];
         if ((double)total > f.p[0])
-            ok = (double)(splitmix((unsigned long long)f.p[1] * 0x100000001B3ULL + (unsigned long long)j) >> 11) / 9007199254740992.0 <
+            ok = (double)(seeded_mix((unsigned long long)f.p[1], j) >> 11) / 9007199254740992.0 <
                  (f.p[2] != 0.0 ? (double)((float)f.p[0] / (float)total) : f.p[0] / (double)total);
     }
     if (!ok) keep[i] = 0;

@@ -6,7 +6,7 @@
 //      and derives the root and the levels of a code, min(21, d_size), in T (octree_host.hpp, shared with the host form);
 //   2. k_oct_paths: compare and halve per level, the centre carried in T as the statement writes it; the level-l digit sits
 //      above the level-(l+1) digit, so ascending codes are the depth-first order with children 0 .. 7;
-//   3. the stable LSD radix sort of (code, index) over the code's bits only: k_vox_hist / k_vox_scatter, unchanged;
+//   3. the stable LSD radix sort of (code, index) over the code's bits only: launch_pair_sort (k_pairsort.inc);
 //   4. k_oct_depth: per sorted position the leaf depth -- the count of codes sharing a d-prefix is non-increasing in d, so the
 //      smallest d meeting the count rule is a binary search over d, each probe a lower bound in the sorted codes and one look
 //      maxPointByNode positions ahead -- and the leaf-head flag (the depth-prefix differs from the left neighbour's);
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_oct_emit(const T *__restrict__ X, int x
     if (out_depth) out_depth[g] = ldepth[g];
     if (method >= 2 && c > kOctHeavy) { heavy[atomicAdd(&st->nheavy, 1)] = g; return; }
     int keep = first;
-    if (method == 1) keep = p[(int)((splitmix(seed * 0x100000001B3ULL + (unsigned long long)first) >> 11) % (unsigned long long)c)];
+    if (method == 1) keep = p[(int)((seeded_mix(seed, first) >> 11) % (unsigned long long)c)];
     T cen[3] = {(T)0, (T)0, (T)0};
     if (method >= 2) {
         const T cnt = (T)c;
@@ -236,29 +236,16 @@ void launch_octree_grid(hipStream_t st, const T *X, int xs, int n, const OctRoot
 {
     if (n <= 0) return;
     const dim3 b256(256);
-    const int nb = cdiv(n, 256), nt = cdiv(n, kVoxTile);
-    int cur = 0;
-    auto sort = [&](int bits) {                                          // the stable LSD radix sort of VoxelGrid, its kernels unchanged
-        for (int shift = 0; shift < bits; shift += 8) {
-            hipLaunchKernelGGL(k_vox_hist, dim3(nt), b256, 0, st, (const unsigned long long *)w.key[cur], n, shift, nt, w.hist);
-            launch_exclusive_scan(st, w.hist, 256 * nt, w.hoff, w.bsum);
-            hipLaunchKernelGGL(k_vox_scatter, dim3(nt), b256, 0, st, (const unsigned long long *)w.key[cur], (const int *)w.idx[cur], n, shift, nt,
-                               (const int *)w.hoff, w.key[cur ^ 1], w.idx[cur ^ 1]);
-            cur ^= 1;
-        }
-    };
-    hipLaunchKernelGGL(k_oct_paths<T>, dim3(nb), b256, 0, st, X, xs, n, R, w.key[0], w.idx[0]);
-    sort(3 * R.levels);
-    hipLaunchKernelGGL(k_oct_depth, dim3(nb), b256, 0, st, (const unsigned long long *)w.key[cur], n, R.levels, max_pts, w.depth, w.head);
-    launch_exclusive_scan(st, w.head, n, w.hs, w.bsum);
+    const int nb = cdiv(n, 256);
+    hipLaunchKernelGGL(k_oct_paths<T>, dim3(nb), b256, 0, st, X, xs, n, R, w.sort.key[0], w.sort.idx[0]);
+    int cur = launch_pair_sort(st, w.sort, n, 3 * R.levels, 0);
+    hipLaunchKernelGGL(k_oct_depth, dim3(nb), b256, 0, st, (const unsigned long long *)w.sort.key[cur], n, R.levels, max_pts, w.depth, w.head);
+    launch_exclusive_scan(st, w.head, n, w.hs, w.sort.bsum);
     const bool resort = max_pts > 1;
-    hipLaunchKernelGGL(k_oct_leaves, dim3(nb), b256, 0, st, (const int *)w.idx[cur], n, (const int *)w.depth, (const int *)w.head, (const int *)w.hs,
-                       w.start, w.ldepth, resort ? w.key[cur ^ 1] : (unsigned long long *)nullptr, resort ? w.idx[cur ^ 1] : (int *)nullptr);
-    if (resort) {
-        cur ^= 1;
-        sort(n > 1 ? 32 - __builtin_clz((unsigned)(n - 1)) : 0);
-    }
-    const int *sidx = w.idx[cur];
+    hipLaunchKernelGGL(k_oct_leaves, dim3(nb), b256, 0, st, (const int *)w.sort.idx[cur], n, (const int *)w.depth, (const int *)w.head, (const int *)w.hs,
+                       w.start, w.ldepth, resort ? w.sort.key[cur ^ 1] : (unsigned long long *)nullptr, resort ? w.sort.idx[cur ^ 1] : (int *)nullptr);
+    if (resort) cur = launch_pair_sort(st, w.sort, n, n > 1 ? 32 - __builtin_clz((unsigned)(n - 1)) : 0, cur ^ 1);
+    const int *sidx = w.sort.idx[cur];
     hipLaunchKernelGGL(k_oct_emit<T>, dim3(nb), b256, 0, st, X, xs, n, sidx, (const int *)w.start, (const int *)w.ldepth, (const int *)(w.hs + n), method,
                        seed, desc, drows, out_xyz, os, out_desc, kept_idx, out_count, out_depth, w.heavy, stat);
     if (method >= 2)

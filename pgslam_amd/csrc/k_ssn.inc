@@ -206,7 +206,7 @@ __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int x
     if (method == 0) {
         for (int k = 0; k < B.count; k++) {
             const int i = member(k);
-            const double u = (double)(splitmix(seed * 0x100000001B3ULL + (unsigned long long)i) >> 11) / 9007199254740992.0;
+            const double u = (double)(seeded_mix(seed, i) >> 11) / 9007199254740992.0;
             if (!(u < (double)ratio)) continue;
             keep[i] = 1; box_of[i] = b;
         }

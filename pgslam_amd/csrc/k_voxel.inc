@@ -4,10 +4,8 @@
 //   1. k_vox_bounds: min / max of each axis (atomics on order-preserving keys: exact, any order) and the not-finite flag;
 //      the host reads them back and derives minB, numDiv and the key's bit count in T, as the statement writes them;
 //   2. k_vox_keys: the 64-bit voxel key of every point, paired with its index;
-//   3. an LSD radix sort of the (key, index) pairs, 8 bits a pass, over the key's bits only: per tile a digit histogram
-//      (k_vox_hist), one scan of the [digit][tile] counts, and a stable scatter (k_vox_scatter: the rank of a pair among the
-//      equal digits of its wave from 8 ballots, waves and rounds in input order).  The input is in index order, so a voxel's
-//      pairs end in ascending index: its first pair is its first point;
+//   3. the stable LSD radix sort of the (key, index) pairs over the key's bits only (launch_pair_sort, k_pairsort.inc).  The
+//      input is in index order, so a voxel's pairs end in ascending index: its first pair is its first point;
 //   4. k_vox_heads marks the segment heads, one scan numbers them; k_vox_first flags each voxel's first point (by point
 //      index), and one scan of those flags gives every voxel its output slot: ascending first index;
 //   5. k_vox_emit, one thread per first point, writes the index, count, centre or first-point values and -- for a voxel of at
@@ -72,59 +70,6 @@ __global__ __launch_bounds__(256) void k_vox_keys(const T *__restrict__ X, int x
     }
     key[i] = c[0] + c[1] * g.nd[0] + c[2] * (g.nd[0] * g.nd[1]);
     idx[i] = i;
-}
-
-// per tile: the count of each digit; hist[d * nb + tile]
-__global__ __launch_bounds__(256) void k_vox_hist(const unsigned long long *__restrict__ key, int n, int shift, int nb, int *__restrict__ hist)
-{
-    __shared__ int cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * kVoxTile;
-    for (int r = 0; r < kVoxTile / 256; r++) {
-        const long long e = base + r * 256 + threadIdx.x;
-        if (e < n) atomicAdd(&cnt[(int)((key[e] >> shift) & 255)], 1);
-    }
-    __syncthreads();
-    hist[(long long)threadIdx.x * nb + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// stable scatter of one pass: off = the exclusive scan of hist
-__global__ __launch_bounds__(256) void k_vox_scatter(const unsigned long long *__restrict__ key, const int *__restrict__ idx, int n, int shift, int nb,
-                                                     const int *__restrict__ off, unsigned long long *__restrict__ key_out, int *__restrict__ idx_out)
-{
-    __shared__ int cnt[4][256];
-    __shared__ int run[256];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    run[threadIdx.x] = off[(long long)threadIdx.x * nb + blockIdx.x];
-    const unsigned long long below = (1ULL << lane) - 1ULL;
-    const long long base = (long long)blockIdx.x * kVoxTile;
-    for (int r = 0; r < kVoxTile / 256; r++) {
-        const long long e = base + r * 256 + threadIdx.x;
-        const bool valid = e < n;
-        unsigned long long k = 0;
-        int id = 0, d = 0;
-        if (valid) { k = key[e]; id = idx[e]; d = (int)((k >> shift) & 255); }
-        // the lanes of this wave with the same digit
-        unsigned long long same = __ballot(valid);
-        for (int b = 0; b < 8; b++) {
-            const unsigned long long m = __ballot((d >> b) & 1);
-            same &= ((d >> b) & 1) ? m : ~m;
-        }
-        const int rank = __popcll(same & below), wcnt = __popcll(same);
-        for (int q = 0; q < 4; q++) cnt[q][threadIdx.x] = 0;
-        __syncthreads();
-        if (valid && rank == wcnt - 1) cnt[w][d] = wcnt;
-        __syncthreads();
-        {   // thread t owns digit t: the waves' offsets in order
-            int acc = run[threadIdx.x];
-            for (int q = 0; q < 4; q++) { const int c = cnt[q][threadIdx.x]; cnt[q][threadIdx.x] = acc; acc += c; }
-            run[threadIdx.x] = acc;
-        }
-        __syncthreads();
-        if (valid) { const int dst = cnt[w][d] + rank; key_out[dst] = k; idx_out[dst] = id; }
-        __syncthreads();
-    }
 }
 
 // head[s] = 1 where a voxel starts in the sorted order
@@ -294,19 +239,11 @@ void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<
 {
     if (n <= 0) return;
     const dim3 b256(256);
-    auto scan = [&](const int *in, int len, int *out) { launch_exclusive_scan(st, in, len, out, w.bsum); };
-    hipLaunchKernelGGL(k_vox_keys<T>, dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, g, w.key[0], w.idx[0]);
-    int cur = 0;
-    const int nt = cdiv(n, kVoxTile);
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(k_vox_hist, dim3(nt), b256, 0, st, (const unsigned long long *)w.key[cur], n, shift, nt, w.hist);
-        scan(w.hist, 256 * nt, w.hoff);
-        hipLaunchKernelGGL(k_vox_scatter, dim3(nt), b256, 0, st, (const unsigned long long *)w.key[cur], (const int *)w.idx[cur], n, shift, nt,
-                           (const int *)w.hoff, w.key[cur ^ 1], w.idx[cur ^ 1]);
-        cur ^= 1;
-    }
-    const unsigned long long *skey = w.key[cur];
-    const int *sidx = w.idx[cur];
+    auto scan = [&](const int *in, int len, int *out) { launch_exclusive_scan(st, in, len, out, w.sort.bsum); };
+    hipLaunchKernelGGL(k_vox_keys<T>, dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, g, w.sort.key[0], w.sort.idx[0]);
+    const int cur = launch_pair_sort(st, w.sort, n, bits, 0);
+    const unsigned long long *skey = w.sort.key[cur];
+    const int *sidx = w.sort.idx[cur];
     hipLaunchKernelGGL(k_vox_heads, dim3(cdiv(n, 256)), b256, 0, st, skey, n, w.head);
     scan(w.head, n, w.hs);
     (void)hipMemsetAsync(w.first, 0, sizeof(int) * (size_t)n, st);

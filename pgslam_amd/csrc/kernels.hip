@@ -189,6 +189,7 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_launch.inc"
 #include "k_ssn.inc"
 #include "k_vartrim.inc"
+#include "k_pairsort.inc"
 #include "k_voxel.inc"
 #include "k_noise.inc"
 #include "k_density.inc"

@@ -1,6 +1,7 @@
 // kernels.hpp -- launch entry points of kernels.hip (host callable).
 #pragma once
 #include "device_types.hpp"
+#include "pgslam_amd/octree_host.hpp"
 
 namespace pgicp {
 
@@ -173,6 +174,28 @@ int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, 
                             const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
                             T *out_desc, int *kept_idx, int *counters);
 
+// The stable LSD radix sort of (64-bit key, index) pairs (k_pairsort.inc), 8 bits a pass, that VoxelGrid, OctreeGrid and NormalSpace
+// share: the two ping-pong buffers, the [digit][tile] counts and their scan, and the scan's block sums.  `other_scan`: the longest
+// scan the caller itself runs through bsum (0: none) -- bsum is sized for the longer of that and the sort's own
+constexpr int kPairTile = 4096;      // pairs per block of the radix passes: 256 threads x 16 rounds
+struct PairSort {
+    unsigned long long *key[2];
+    int *idx[2], *hist, *hoff, *bsum;
+};
+inline PairSort pair_sort_scratch(Carve &cv, int n, size_t other_scan)
+{
+    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kPairTile - 1) / kPairTile + 1, hist = 256 * tiles + 1;
+    PairSort w;
+    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
+    for (auto &i : w.idx) i = cv.take<int>(n1);
+    w.hist = cv.take<int>(hist);
+    w.hoff = cv.take<int>(hist);
+    w.bsum = cv.take<int>(scan_scratch_ints(hist > other_scan ? hist : other_scan));
+    return w;
+}
+// sorts the pairs in key[cur] / idx[cur] over the low `bits` bits of the key; returns which of key[] / idx[] holds the result
+int launch_pair_sort(hipStream_t st, const PairSort &w, int n, int bits, int cur);
+
 // pgicp_voxel_grid_*: the bounds and counters of a call (device), the grid the host derives from the bounds, and the scratch
 struct VoxStat {
     unsigned long long lo[3], hi[3];    // order-preserving keys of each axis's min / max (-0.0 as +0.0)
@@ -183,21 +206,16 @@ struct VoxGrid {
     T v[3], minB[3];
     unsigned long long nd[3];           // numDiv of each axis (< 2^31)
 };
-constexpr int kVoxTile = 4096;       // pairs per block of the radix passes: 256 threads x 16 rounds
 struct VoxScratch {
-    unsigned long long *key[2];
-    int *idx[2], *hist, *hoff, *bsum, *head, *hs, *start, *first, *vox_of, *pos;
+    PairSort sort;
+    int *head, *hs, *start, *first, *vox_of, *pos;
     int2 *heavy;
 };
 inline VoxScratch vox_scratch(Carve &cv, int n)
 {
-    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kVoxTile - 1) / kVoxTile + 1, hist = 256 * tiles + 1;
+    const size_t n1 = (size_t)n + 1;
     VoxScratch w;
-    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
-    for (auto &i : w.idx) i = cv.take<int>(n1);
-    w.hist = cv.take<int>(hist);
-    w.hoff = cv.take<int>(hist);
-    w.bsum = cv.take<int>(scan_scratch_ints(hist > n1 ? hist : n1));
+    w.sort = pair_sort_scratch(cv, n, n1);           // bsum also serves the scans of head and first: n + 1 elements
     w.head = cv.take<int>(n1);
     w.hs = cv.take<int>(n1);
     w.start = cv.take<int>(n1 + 1);
@@ -214,23 +232,20 @@ void launch_voxel_grid(hipStream_t st, const T *X, int xs, int n, const VoxGrid<
                        const VoxScratch &w, T *out_xyz, int os, T *out_desc, int *kept_idx, int *out_count, VoxStat *stat);
 
 // include/pgicp_octree.h (k_octree.inc): OctreeGridDataPointsFilter.  The root the host derives from the bounds (VoxStat, from
-// launch_voxel_bounds) and the levels of a path code; the scratch of a call: the sort's buffers as VoxelGrid's, then per sorted
-// position the leaf depth, the head flag and its scan, per leaf the start and depth, and the heavy leaves' list
+// launch_voxel_bounds) and the levels of a path code: octree_host.hpp's Root<T>, as make_root returns it; the scratch of a call: the
+// pair sort's, then per sorted position the leaf depth, the head flag and its scan, per leaf the start and depth, and the heavy
+// leaves' list
 template <typename T>
-struct OctRoot { T c[3], r; int levels; };
+using OctRoot = pgslam_amd::octree::Root<T>;
 struct OctScratch {
-    unsigned long long *key[2];
-    int *idx[2], *hist, *hoff, *bsum, *depth, *head, *hs, *start, *ldepth, *heavy;
+    PairSort sort;
+    int *depth, *head, *hs, *start, *ldepth, *heavy;
 };
 inline OctScratch oct_scratch(Carve &cv, int n)
 {
-    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kVoxTile - 1) / kVoxTile + 1, hist = 256 * tiles + 1;
+    const size_t n1 = (size_t)n + 1;
     OctScratch w;
-    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
-    for (auto &i : w.idx) i = cv.take<int>(n1);
-    w.hist = cv.take<int>(hist);
-    w.hoff = cv.take<int>(hist);
-    w.bsum = cv.take<int>(scan_scratch_ints(hist > n1 ? hist : n1));
+    w.sort = pair_sort_scratch(cv, n, n1);           // bsum also serves the scan of head: n + 1 elements
     w.depth = cv.take<int>(n1);
     w.head = cv.take<int>(n1);
     w.hs = cv.take<int>(n1);
@@ -323,29 +338,25 @@ void launch_cov_frame(hipStream_t st, const T *X, int xs, const T *N, int ns, in
 // pass 4: the values, each list's first m entries (unordered) into cand_idx / cand_v
 template <typename T>
 void launch_cov_select(hipStream_t st, const T *X, int xs, const T *N, int ns, int n, const CovFrameDev<T> &F, int m, const CovScratch &w, CovStat *stat);
-// pass 5: out[j] = in[picks[j]] (picks == null: the identity); any output may be null
+// the gather of CovarianceSampling (pass 5) and NormalSpace: out[j] = in[i] with i = pos[j], or -- sidx and skey set, both or
+// neither -- i = sidx[pos[j]] and bucket_out[j] = skey[pos[j]] >> 24; pos == null: the identity, bucket -1.  Any output may be null
 template <typename T>
-void launch_cov_gather(hipStream_t st, const int *picks, int m, int n, const T *X, int xs, const T *N, int ns, const T *desc, int drows, T *out_xyz,
-                       int os, T *out_nrm, int ons, T *out_desc, int *kept_idx);
+void launch_gather_rows(hipStream_t st, const int *pos, const unsigned long long *skey, const int *sidx, int m, int n, const T *X, int xs, const T *N,
+                        int ns, const T *desc, int drows, T *out_xyz, int os, T *out_nrm, int ons, T *out_desc, int *kept_idx, int *bucket_out);
 
-// include/pgicp_normalspace.h (k_normalspace.inc): NormalSpaceDataPointsFilter.  The scratch of a call: the sort's buffers as
-// VoxelGrid's, the buckets' counts with the not-finite flag behind them (counts[nb_bucket]), and the picks' sorted positions
+// include/pgicp_normalspace.h (k_normalspace.inc): NormalSpaceDataPointsFilter.  The scratch of a call: the pair sort's, the
+// buckets' counts with the not-finite flag behind them (counts[nb_bucket]), and the picks' sorted positions
 constexpr int kNsLdsBuckets = 8192;     // a grid of at most this many buckets is counted in LDS, block by block
 struct NsGrid { double epsilon; int n_phi, n_theta, nb_bucket; };
 struct NsScratch {
-    unsigned long long *key[2];
-    int *idx[2], *hist, *hoff, *bsum, *counts, *pos;
+    PairSort sort;
+    int *counts, *pos;
 };
 // n points, m = min(n, nbSample) picks
 inline NsScratch ns_scratch(Carve &cv, int n, int m, int nb_bucket)
 {
-    const size_t n1 = (size_t)n + 1, tiles = ((size_t)n + kVoxTile - 1) / kVoxTile + 1, hist = 256 * tiles + 1;
     NsScratch w;
-    for (auto &k : w.key) k = cv.take<unsigned long long>(n1);
-    for (auto &i : w.idx) i = cv.take<int>(n1);
-    w.hist = cv.take<int>(hist);
-    w.hoff = cv.take<int>(hist);
-    w.bsum = cv.take<int>(scan_scratch_ints(hist));
+    w.sort = pair_sort_scratch(cv, n, 0);            // nothing of length n is scanned: bsum serves the sort alone
     w.counts = cv.take<int>((size_t)nb_bucket + 1);
     w.pos = cv.take<int>((size_t)m);
     return w;
@@ -353,9 +364,5 @@ inline NsScratch ns_scratch(Carve &cv, int n, int m, int nb_bucket)
 // the keys, the counts (zeroed here) and the stable sort of (key, index); returns which of key[] / idx[] holds the sorted order
 template <typename T>
 int launch_ns_sort(hipStream_t st, const T *N, int ns, int n, const NsGrid &g, unsigned long long seed, const NsScratch &w);
-// out[j] = in[sidx[pos[j]]], bucket_out[j] = skey[pos[j]] >> 24 (pos == null: the identity, bucket -1); any output may be null
-template <typename T>
-void launch_ns_gather(hipStream_t st, const int *pos, const unsigned long long *skey, const int *sidx, int m, int n, const T *X, int xs, const T *N,
-                      int ns, const T *desc, int drows, T *out_xyz, int os, T *out_nrm, int ons, T *out_desc, int *kept_idx, int *bucket_out);
 
 }  // namespace pgicp

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
 #include <thread>
 #include <limits>
 #include <numeric>

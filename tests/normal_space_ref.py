@@ -215,6 +215,7 @@ CASES = [
     ("n255", 1, 0.09, 3, 0), ("n255", 254, 0.5, 4, 3), ("n255", 64, PI, 3, 0),
     ("n256", 64, 0.09, 4, 7), ("n256", 255, 0.0175, 3, 0), ("n256", 256, 0.09, 3, 3), ("n256", 257, 0.09, 3, 0),
     ("n257", 256, PI, 3, 3), ("n257", 64, 0.0175, 3, 0), ("n257", 1, 0.5, 4, 7),
+    ("n300", 1, 0.09, 3, 3), ("n300", 256, 0.09, 4, 3), ("n300", 257, 0.09, 3, 3), ("n300", 300, 0.09, 4, 3),   # the gather's block edge
     ("n4097", 1024, 0.09, 3, 0), ("n4097", 4096, 0.5, 4, 3), ("n4097", 1, 0.0175, 3, 7), ("n4097", 1024, PI, 3, 0),
     ("n4097", 4097, 0.09, 3, 0), ("n4097", 4098, 0.09, 4, 3),
     ("n20001", 5000, 0.09, 3, 3), ("n20001", 20000, 0.09, 4, 0), ("n20001", 5000, 0.0175, 3, 0), ("n20001", 1, 0.5, 3, 0),

@@ -82,6 +82,21 @@ def test_full_call(ctx, kind, T, use_torch):
 
 
 @pytest.mark.parametrize("T", DTYPES)
+def test_gather_at_its_block_edge(ctx, T):
+    """one pick, a full block of 256, one pick into the second block, and the identity path (nbSample = n), 3 descriptor rows"""
+    x, nr = ref.cloud("room", 300, T)
+    desc = np.random.default_rng(5).normal(size=(300, 3)).astype(T)
+    for nb in (1, 256, 257, 300):
+        g = ctx.covariance_sampling(x, nr, nb_sample=nb, descriptors=desc)
+        picks = ref.select(x, nr, nb, g["frame"], T) if nb < 300 else np.arange(300)
+        assert len(g["kept_idx"]) == nb
+        np.testing.assert_array_equal(g["kept_idx"], picks, err_msg=f"nb {nb}")
+        np.testing.assert_array_equal(g["xyz"], x[picks])
+        np.testing.assert_array_equal(g["normals"], nr[picks])
+        np.testing.assert_array_equal(g["descriptors"], desc[picks])
+
+
+@pytest.mark.parametrize("T", DTYPES)
 def test_noop_when_nb_sample_reaches_n(ctx, T):
     x, nr = ref.cloud("room", 300, T)
     for nb in (300, 301, 5000):

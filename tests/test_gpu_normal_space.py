@@ -1,7 +1,7 @@
 """NormalSpaceDataPointsFilter on the device (pgicp_normal_space_sampling_*, k_normalspace.inc) through the C ABI from Python,
 against the plain statement of tests/normal_space_ref.py: kept indices, buckets, coordinates, normals and descriptor rows bit for
 bit, in both precisions, host memory and device memory alike.  The cases are the reference module's: n = 0, 1, 2, the sort's tile
-and round boundaries, nbSample 1, n - 1, n, n + 1 and about n / 4, epsilon 0.09, 0.5, pi (two buckets) and 0.0175 (64 800 buckets:
+and round boundaries, nbSample 1, n - 1, n, n + 1 and about n / 4, the gather's block edge (256 and 257 picks of 300), epsilon 0.09, 0.5, pi (two buckets) and 0.0175 (64 800 buckets:
 the histogram on the global array), strides 3 and 4, descriptor rows 0, 3 and 7, one bucket with ties of r_i, one point per
 bucket, a small bucket that empties mid-draw, and the hand-written pole and seam cloud.  No input lies in the statement's band of
 freedom (the reference module asserts it), so nothing here has a tolerance."""

@@ -11,7 +11,7 @@ import pytest
 
 from pgslam_amd import icp
 from test_voxel_grid_host import apply_dropin, build_exe
-from voxel_grid_ref import voxel_grid
+from voxel_grid_ref import grid, voxel_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CPP = os.path.join(ROOT, "tests", "cpp")
@@ -86,6 +86,38 @@ def test_edges(ctx, T):
         for cen in (True, False):
             for avg in (True, False):
                 check(ctx, x, T, (0.4, 0.4, 0.4), cen, d, avg, label=f"drows={drows} cen={cen} avg={avg}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+def test_every_pass_count_of_the_sort(ctx, T):
+    """4097 points -- two tiles of the sort, the second holding one pair -- at voxel sizes whose keys take 1 .. 8 passes of 8 bits:
+    which buffer the sort's result lies in (odd and even pass counts) and the shift of every pass"""
+    x = np.random.default_rng(11).uniform(-10, 10, size=(4097, 3))
+    passes = []
+    for k in (0, 3, 6, 8, 11, 14, 17, 19):
+        v = (20 / 2 ** k,) * 3
+        nd = [int(a) for a in grid(x, v, T)[2]]                   # the statement's numDiv in T
+        passes.append(-(-(nd[0] + nd[1] * nd[0] + nd[2] * nd[0] * nd[1]).bit_length() // 8))
+        for cen in (True, False):
+            check(ctx, x, T, v, cen, label=f"k={k} passes={passes[-1]} cen={cen}")
+    assert passes == [1, 2, 3, 4, 5, 6, 7, 8]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+def test_heavy_voxel_two_row_passes(ctx, T):
+    """one voxel of c points -- one point into the second chunk of 512, one into the third, a ragged tail -- summed by a block over
+    10 rows (3 coordinates, 7 descriptor rows): two row passes, of 8 and of 2; 50 more points lie in voxels of their own"""
+    rng = np.random.default_rng(12)
+    for c in (513, 1025, 1100):
+        x = np.concatenate([rng.uniform(0, 5, size=(c, 3)), rng.uniform(60, 2000, size=(50, 3))])[rng.permutation(c + 50)]
+        d = rng.normal(size=(c + 50, 7)).astype(T)
+        for stride in (3, 4):
+            h = np.ones((c + 50, stride), dtype=T)
+            h[:, :3] = x
+            g, _ = check(ctx, h, T, (50.0,) * 3, True, d, True, label=f"c={c} stride={stride}")
+            assert g["count"].max() == c and np.sort(g["count"])[-2] <= 64
 
 
 @pytest.mark.gpu

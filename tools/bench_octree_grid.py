@@ -1,5 +1,6 @@
 # OctreeGridDataPointsFilter timing (GPU box), written to profiles/r12_octree_grid.json: for f32 and f64, a 100 k-point scan and
-# a 1 M-point cloud, methods 0 and 2, at maxPointByNode 1 and at maxSizeByNode 0.2 with a large count -- wall time of the ABI call
+# a 1 M-point cloud, methods 0 and 2, at maxPointByNode 1, at maxSizeByNode 0.2 with a large count and (the 100 k scan only) at
+# maxPointByNode 1000, whose leaves are summed by a block each -- wall time of the ABI call
 # host in / host out and device in / device out, and of the drop-in's host form (tests/cpp/test_octree_grid_cpu time: the filter
 # alone, PGSLAM_HOST_INPUT_STAGE=1), the yardstick.
 #   python tools/bench_octree_grid.py [--reps 10]
@@ -28,7 +29,8 @@ def room(n):
 
 dev = torch.device('cuda', 0)
 ctx = icp.Context(0)
-SETTINGS = (("count1", dict(max_point_by_node=1, max_size_by_node=0.0)), ("size0.2", dict(max_point_by_node=1_000_000_000, max_size_by_node=0.2)))
+SETTINGS = (("count1", dict(max_point_by_node=1, max_size_by_node=0.0)), ("size0.2", dict(max_point_by_node=1_000_000_000, max_size_by_node=0.2)),
+            ("count1000", dict(max_point_by_node=1000, max_size_by_node=0.0)))      # leaves above 64 points: method 2 goes through k_oct_heavy
 if args.once:
     tx = torch.from_numpy(room(1_000_000).astype(np.float32)).to(dev)
     for _ in range(2):
@@ -43,6 +45,8 @@ for name, n in (("scan_100k", 100_000), ("cloud_1M", 1_000_000)):
         x = np.ascontiguousarray(cloud, dtype=T)
         tx = torch.from_numpy(x).to(dev)
         for tag, kw in SETTINGS:
+            if tag == "count1000" and n != 100_000:
+                continue
             for method in (0, 2):
                 k = dict(kw, sampling_method=method)
                 leaves = len(ctx.octree_grid(x, **k)["kept_idx"])         # scratch allocated, code loaded
