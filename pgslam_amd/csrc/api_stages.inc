@@ -41,6 +41,7 @@ int run_partial(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, i
                       S.d2.template as<T>(), ch, 1, n, 0, c->small.as<int>() + 16, c->slow_list.as<int2>(), c->slow_lb.as<T>(),
                       c->slow_ring.as<int>(), L.rings_unseeded, c->active.as<int>(), S.none_r.template as<T>(), 1, c->queue.p, 1, L.table_kinds);
         c->seg_clean = 0;
+        c->counters_clean = 0;                 // (pgicp_debug_counters: this pass's queue counters, not the copy batch_begin cleared)
         // public matcher output / partial chain: resolve every queued query exactly
         if (c->prm.matcher == PGICP_MATCHER_GRID)
             launch_knn_slow<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(),

@@ -202,6 +202,7 @@ __device__ __forceinline__ void item_rounds_d(const double4 *__restrict__ pts, c
 // d_f - E(d_f) > fb + E(fb) cannot reach it.  The test used is weaker (d_f - 2.5 E(d_f) <= fb, E increasing, d_f >= fb), as one
 // threshold per item: a superset survives, typically one or two records per owner and round.  Items longer than eight records (a pool that
 // overflowed its slots: rare) take item_rounds_d.
+// (What holds the threshold: tests/test_gpu_tie_scenes.py::test_double_pairs_against_the_float_prefilter -- pairs that float32 orders wrongly half the time, on both branches.)
 __device__ __forceinline__ void item_rounds_dp(const double4 *__restrict__ pts, const float4 *__restrict__ ptsf, const int2 *items, int total,
                                                const double *sq, unsigned long long *skey, int *sidx, int *sslot, unsigned *fb, const float *su,
                                                int lane, int chunk)

@@ -40,6 +40,11 @@ SETTINGS = [
 EXACT_SCENES = ["tests/test_gpu_exact_scenes.py::" + t for t in (
     "test_a_wide_selection_without_a_guess", "test_a_wide_selection_all_keys_distinct_f64", "test_e_error_stats_at_every_edge", "test_e_chain_batch_at_every_edge_both_orders",
     "test_e_chain_batch_three_neighbours", "test_e_normal_filter_in_the_sums")]
+# The tie scenes (tests/tie_scenes.py): every knob moves the same ties between the matcher's paths.  The function that asserts which
+# path a layer reached runs at default knobs only.
+TIE_SCENES = ["tests/test_gpu_tie_scenes.py::" + t for t in (
+    "test_exact_plane", "test_exact_cube", "test_exact_knn_lists", "test_rounded_lattice", "test_double_pairs_against_the_float_prefilter",
+    "test_two_maps_of_one_batch", "test_seeded_passes_on_the_tied_plane", "test_a_seed_that_is_tied_but_not_the_lowest_index")]
 
 
 @pytest.mark.parametrize("setting", SETTINGS, ids=lambda s: ",".join(f"{k[6:]}={v}" for k, v in s.items()))
@@ -47,7 +52,7 @@ def test_parity_holds_for_every_knob_setting(setting):
     env = dict(os.environ, **setting)
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_edge_cases.py", "tests/test_gpu_matcher_state.py", "tests/test_local_mapper.py", "tests/test_gpu_chain.py",
                         "tests/test_gpu_bit_exact.py", "tests/test_gpu_parity.py::test_seeded_partial_chain_equals_the_unseeded_one",
-                        *EXACT_SCENES,
+                        *EXACT_SCENES, *TIE_SCENES,
                         "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
