@@ -37,6 +37,7 @@
 #include "octree_host.hpp"
 #include "../pgicp_normalspace.h"
 #include "normalspace_host.hpp"
+#include "../pgicp_normals_ext.h"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -165,6 +166,9 @@ template <typename T> struct Abi {
     static int normals(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, T *out, int os, T *eig) { return pick<T>(pgicp_surface_normals_f32, pgicp_surface_normals_f64)(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, nullptr, nullptr); }
     static int normals_ids(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, T *out, int os, T *eig, int32_t *ids) { return pick<T>(pgicp_surface_normals_f32, pgicp_surface_normals_f64)(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, ids, nullptr); }
     static int densities(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, T *out, int os, T *eig, T *dens) { return pick<T>(pgicp_surface_densities_f32, pgicp_surface_densities_f64)(c, x, xs, n, PGICP_HOST, knn, md, out, os, eig, dens); }
+    static int normals_ext(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, int smooth, T *out, int os, T *eig, T *vec, T *mdist, T *mids, T *dens)
+    { return pick<T>(pgicp_surface_normals_ext_f32, pgicp_surface_normals_ext_f64)(c, x, xs, n, PGICP_HOST, knn, md, smooth, out, os, eig, vec, mdist, mids, nullptr, nullptr, dens); }
+    static int smooth_normals(pgicp_ctx *c, const T *nr, int ns, const int32_t *ids, int knn, int n, T *out, int os) { return pick<T>(pgicp_smooth_normals_f32, pgicp_smooth_normals_f64)(c, nr, ns, ids, knn, n, PGICP_HOST, out, os); }
     static int max_density(pgicp_ctx *c, const T *dens, int n, double md, uint64_t sd, int32_t *idx, int *n_out) { return pick<T>(pgicp_max_density_f32, pgicp_max_density_f64)(c, dens, n, PGICP_HOST, md, sd, idx, n_out); }
     static int normals_max_density(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, double dmax, uint64_t sd, const T *d, int dr, T *ox, T *on,
                                    T *oe, T *odn, T *od, int32_t *idx, int *n_out)
@@ -670,19 +674,45 @@ struct PointMatcher {
     };
     //! [EXT] SurfaceNormalDataPointsFilter{knn, maxDist, epsilon, keepNormals, keepEigenValues}: normals (and,
     //! on request, eigenvalues) of every point from its knn neighbours, computed on the device by
-    //! pgicp_surface_normals_*; the descriptors are appended as libpointmatcher appends them.
+    //! pgicp_surface_normals_*; the descriptors are appended as libpointmatcher appends them.  keepEigenVectors (`eigVectors`, 9
+    //! rows: three columns in ascending-eigenvalue order), keepMatchedIds (`matchedIds`, knn rows, -1 = none), keepMeanDist
+    //! (`meanDists`) and smoothNormals go through pgicp_surface_normals_ext_*; their statement, with its marked deviations from
+    //! upstream, is in include/pgicp_normals_ext.h.
     struct SurfaceNormalDataPointsFilter : DataPointsFilter {
         int knn = 5; T maxDist = std::numeric_limits<T>::infinity(); bool keepNormals = true, keepEigenValues = false, keepDensities = false;
+        bool keepEigenVectors = false, keepMatchedIds = false, keepMeanDist = false, smoothNormals = false;
         pgslam_amd::LazyContext ctx;                 // made when the filter first runs, not when a YAML file is read
-        SurfaceNormalDataPointsFilter(int k, T md, bool kn, bool ke, bool kd = false) : knn(k), maxDist(md), keepNormals(kn), keepEigenValues(ke), keepDensities(kd) {}
+        SurfaceNormalDataPointsFilter(int k, T md, bool kn, bool ke, bool kd = false, bool kev = false, bool kmi = false, bool kmd = false, bool sm = false)
+            : knn(k), maxDist(md), keepNormals(kn), keepEigenValues(ke), keepDensities(kd), keepEigenVectors(kev), keepMatchedIds(kmi), keepMeanDist(kmd), smoothNormals(sm)
+        {
+            if (sm && !kn) throw std::runtime_error("SurfaceNormalDataPointsFilter: smoothNormals needs keepNormals (there is nothing to smooth into)");
+        }
+        //! an output only pgicp_surface_normals_ext_* makes
+        bool wantsExt() const { return keepEigenVectors || keepMatchedIds || keepMeanDist || smoothNormals; }
         SurfaceNormalDataPointsFilter(const SurfaceNormalDataPointsFilter &) = delete;
         SurfaceNormalDataPointsFilter &operator=(const SurfaceNormalDataPointsFilter &) = delete;
         void inPlaceFilter(DataPoints &c) override
         {
             const int n = (int)c.features.cols();
-            if (n == 0 || (!keepNormals && !keepEigenValues && !keepDensities)) return;
+            if (n == 0 || (!keepNormals && !keepEigenValues && !keepDensities && !wantsExt())) return;
             Matrix nrm(3, n), eig(3, n);
             const double md = std::isfinite((double)maxDist) ? (double)maxDist : 1e300;
+            if (wantsExt()) {
+                // upstream's order: normals, densities, eigValues, eigVectors, matchedIds, meanDists
+                if (knn < (keepDensities ? 3 : 1) || knn > 32) throw std::runtime_error("SurfaceNormalDataPointsFilter: knn must be in [1, 32], in [3, 32] with keepDensities");
+                Matrix dens(1, keepDensities ? n : 0), vec(9, keepEigenVectors ? n : 0), ids(knn, keepMatchedIds ? n : 0), dist(1, keepMeanDist ? n : 0);
+                check(ctx, pgslam_amd::Abi<T>::normals_ext(ctx, c.features.data(), (int)c.features.rows(), n, knn, md, smoothNormals ? 1 : 0,
+                                                           keepNormals ? nrm.data() : nullptr, 3, keepEigenValues ? eig.data() : nullptr,
+                                                           keepEigenVectors ? vec.data() : nullptr, keepMeanDist ? dist.data() : nullptr,
+                                                           keepMatchedIds ? ids.data() : nullptr, keepDensities ? dens.data() : nullptr));
+                if (keepNormals) c.setDescriptor("normals", nrm);
+                if (keepDensities) c.setDescriptor("densities", dens);
+                if (keepEigenValues) c.setDescriptor("eigValues", eig);
+                if (keepEigenVectors) c.setDescriptor("eigVectors", vec);
+                if (keepMatchedIds) c.setDescriptor("matchedIds", ids);
+                if (keepMeanDist) c.setDescriptor("meanDists", dist);
+                return;
+            }
             if (keepDensities) {
                 // [EXT] computeDensity: neighbours found / volume of the sphere that holds them around their MEAN, in T (the oracle's
                 // orc_densities) -- an epilogue of the device's normals kernel (pgicp_surface_densities_*): no id table comes back
@@ -1190,7 +1220,7 @@ struct PointMatcher {
         bool fusedWith(SurfaceNormalDataPointsFilter &sn, DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            if (n == 0 || frows < 3 || !sn.keepDensities || !this->deviceWanted("PGSLAM_HOST_MAX_DENSITY") || !deviceTakesParameters() || sn.knn < 3 || sn.knn > 32) return false;
+            if (n == 0 || frows < 3 || !sn.keepDensities || sn.wantsExt() || !this->deviceWanted("PGSLAM_HOST_MAX_DENSITY") || !deviceTakesParameters() || sn.knn < 3 || sn.knn > 32) return false;
             for (const char *name : {"normals", "densities", "eigValues"}) if (c.descriptorExists(name)) return false;
             // (a coordinate that is not finite: the device refuses the cloud, and the unfused pair says so as it always did)
             for (int i = 0; i < n; i++)
@@ -1292,14 +1322,18 @@ struct PointMatcher {
                 } else if (m.name == "SurfaceNormalDataPointsFilter") {
                     // (epsilon > 0 allows an approximate neighbour search upstream; the exact search here meets every allowance)
                     if (!(get("epsilon", "0") >= 0.0)) throw std::runtime_error(m.name + ": epsilon must be >= 0");
-                    for (const char *k : {"keepEigenVectors", "keepMatchedIds", "keepMeanDist", "smoothNormals"})
-                        if (get(k, "0") != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");
                     const int knn = (int)get("knn", "5");
                     if (knn < 3 || knn > 32) throw std::runtime_error(m.name + ": knn must be in [3, 32]");
+                    if (get("smoothNormals", "0") != 0.0 && get("keepNormals", "1") == 0.0)
+                        throw std::runtime_error(m.name + ": smoothNormals needs keepNormals (there is nothing to smooth into)");
                     this->push_back(std::make_shared<SurfaceNormalDataPointsFilter>(knn, (T)get("maxDist", "inf"),
                                                                                      get("keepNormals", "1") != 0.0,
                                                                                      get("keepEigenValues", "0") != 0.0,
-                                                                                     get("keepDensities", "0") != 0.0));
+                                                                                     get("keepDensities", "0") != 0.0,
+                                                                                     get("keepEigenVectors", "0") != 0.0,
+                                                                                     get("keepMatchedIds", "0") != 0.0,
+                                                                                     get("keepMeanDist", "0") != 0.0,
+                                                                                     get("smoothNormals", "0") != 0.0));
                 } else if (m.name == "SamplingSurfaceNormalDataPointsFilter") {
                     for (const char *k : {"keepDensities", "keepEigenValues", "keepEigenVectors"})
                         if (get(k, "0") != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");

@@ -288,6 +288,27 @@ int launch_surface_normals(hipStream_t st, const MapDev<T> *maps, int map, int m
     return 0;
 }
 
+// pgicp_normals_ext.h: the instantiation with both epilogues (any output may be null; x's rows as NormalsExtOut says)
+template <typename T>
+int launch_surface_normals_ext(hipStream_t st, const MapDev<T> *maps, int map, int m, int knn, T max_dist, T eps_rank, T *out_nrm,
+                               int out_stride, T *out_eig, int *out_ids, T *out_d2, T *out_dens, const NormalsExtOut<T> &x)
+{
+    const dim3 grid(cdiv(m, 128)), block(128);
+    if (knn <= 8) hipLaunchKernelGGL((k_surface_normals<T, 8, true, true>), grid, block, 0, st, maps, map, knn, max_dist, eps_rank, out_nrm, out_stride, out_eig, out_ids, out_d2, out_dens, x);
+    else if (knn <= 16) hipLaunchKernelGGL((k_surface_normals<T, 16, true, true>), grid, block, 0, st, maps, map, knn, max_dist, eps_rank, out_nrm, out_stride, out_eig, out_ids, out_d2, out_dens, x);
+    else if (knn <= 32) hipLaunchKernelGGL((k_surface_normals<T, 32, true, true>), grid, block, 0, st, maps, map, knn, max_dist, eps_rank, out_nrm, out_stride, out_eig, out_ids, out_d2, out_dens, x);
+    else return -1;
+    return 0;
+}
+
+template <typename T>
+void launch_smooth_normals(hipStream_t st, const T *nrm, int ns, const int *nb, long long rs, long long cs, int knn, int n, const int *out_of,
+                           T *out, int os, int *bad)
+{
+    if (bad) (void)hipMemsetAsync(bad, 0, sizeof(int), st);
+    hipLaunchKernelGGL(k_smooth_normals<T>, dim3(cdiv(n, 128)), dim3(128), 0, st, nrm, ns, nb, rs, cs, knn, n, out_of, out, os, bad);
+}
+
 int reduce_blocks(int max_n) { return round8(cdiv(max_n, kReduceSpan)); }
 
 // (max_n: the largest number of PAIRS of a problem = points x knn; rd_nrm: the sorted reading normals when a
@@ -491,6 +512,8 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     template void launch_borrow_order<T>(hipStream_t, const ProblemDev *, const SrcDesc *, const int *, const int *, const typename Vec4<T>::type *, int, const SeedSegs &, \
                                          const int *, int, T *, int *, int *);                                            \
     template int launch_surface_normals<T>(hipStream_t, const MapDev<T> *, int, int, int, T, T, T *, int, T *, int *, T *); \
+    template int launch_surface_normals_ext<T>(hipStream_t, const MapDev<T> *, int, int, int, T, T, T *, int, T *, int *, T *, T *, const NormalsExtOut<T> &); \
+    template void launch_smooth_normals<T>(hipStream_t, const T *, int, const int *, long long, long long, int, int, const int *, T *, int, int *); \
     template void launch_unpermute<T>(hipStream_t, const MapDev<T> *, int, const int *, const int *, const T *, int, int, \
                                       int *, T *);
 

@@ -125,11 +125,18 @@ __device__ __forceinline__ void jacobi3(double a[3][3], double v[3][3])
 // DENS (pgicp_density.h): the `densities` row as an epilogue -- the neighbours, their count and their mean are at hand, so the
 // largest squared distance to the mean rides in the scatter loop and no id table leaves the kernel; out_nrm may then be null.
 // The statement is the oracle's orc_densities, in T.  DENS = false is the kernel as it was.
-template <typename T, int K, bool DENS = false>
+// EXT (pgicp_normals_ext.h): the rows the kernel used to drop, as a second epilogue -- the three eigenvector columns in
+// ascending-eigenvalue order, the point's distance to its neighbours' mean, the neighbour ids as values of T -- and, for the
+// smoothing pass (k_smooth_normals), the raw normal, the point's index and its neighbours' SLOTS, all in slot order, the table
+// transposed ([neighbour][slot]) so that the wave writes and later reads it coalesced.  EXT = false takes no argument for it
+// (an empty structure) and is the kernel as it was.
+struct NormalsNoExt {};
+template <typename T, int K, bool DENS = false, bool EXT = false>
 __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__restrict__ maps, int map, int knn, T max_dist,
                                                           T eps_rank, T *__restrict__ out_nrm, int out_stride,
                                                           T *__restrict__ out_eig, int *__restrict__ out_ids,
-                                                          T *__restrict__ out_d2, T *__restrict__ out_dens = nullptr)
+                                                          T *__restrict__ out_d2, T *__restrict__ out_dens = nullptr,
+                                                          typename std::conditional<EXT, NormalsExtOut<T>, NormalsNoExt>::type x = {})
 {
     const MapDev<T> M = maps[map];
     const int s0 = blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,8 +165,13 @@ __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__rest
         }
     T c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
     T r2 = 0;                                                        // DENS: the largest squared distance to the mean, by strict >
+    T mean_dist = 0;                                                 // EXT: |point - mean|
     if (cnt > 0) {
         const T mx = sx / (T)cnt, my = sy / (T)cnt, mz = sz / (T)cnt;
+        if constexpr (EXT) {
+            const T dx = qx - mx, dy = qy - my, dz = qz - mz;
+            mean_dist = sqrt_rn_t((dx * dx + dy * dy) + dz * dz);
+        }
 #pragma unroll
         for (int j = 0; j < K; j++)
             if (j >= K - knn && L.slot[j] >= 0) {
@@ -210,6 +222,70 @@ __global__ __launch_bounds__(128) void k_surface_normals(const MapDev<T> *__rest
                 if (out_d2) out_d2[(long long)self * knn + jj] = ok ? L.d[j] : Bits<T>::inf();
             }
     }
+    if constexpr (EXT) {
+        if (x.eigvec) {
+            // columns lo, mid, hi of V; a rank < 2 scatter: libpointmatcher's defaults (eigenvalues (1,0,0), eigenvectors I) in the
+            // same ascending, first-minimum order.  The first column is the normal written above, bit for bit
+            T *o = x.eigvec + 9LL * self;
+            T m0 = 0, m1 = 0, m2 = 1, h0 = 1, h1 = 0, h2 = 0;
+            if (!degenerate) {
+                m0 = (T)(mid == 0 ? V[0][0] : (mid == 1 ? V[0][1] : V[0][2]));
+                m1 = (T)(mid == 0 ? V[1][0] : (mid == 1 ? V[1][1] : V[1][2]));
+                m2 = (T)(mid == 0 ? V[2][0] : (mid == 1 ? V[2][1] : V[2][2]));
+                h0 = (T)(hi == 0 ? V[0][0] : (hi == 1 ? V[0][1] : V[0][2]));
+                h1 = (T)(hi == 0 ? V[1][0] : (hi == 1 ? V[1][1] : V[1][2]));
+                h2 = (T)(hi == 0 ? V[2][0] : (hi == 1 ? V[2][1] : V[2][2]));
+            }
+            o[0] = nx; o[1] = ny; o[2] = nz; o[3] = m0; o[4] = m1; o[5] = m2; o[6] = h0; o[7] = h1; o[8] = h2;
+        }
+        if (x.mean_dist) x.mean_dist[self] = mean_dist;
+        if (x.raw) {
+            x.raw[3LL * s0] = nx; x.raw[3LL * s0 + 1] = ny; x.raw[3LL * s0 + 2] = nz;
+            x.self[s0] = self;
+        }
+        if (x.matched || x.raw) {
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                if (j >= K - knn) {
+                    const int jj = j - (K - knn);
+                    const bool ok = L.slot[j] >= 0;
+                    if (x.matched) x.matched[(long long)self * knn + jj] = ok ? (T)L.idx[j] : (T)-1;
+                    if (x.raw) x.nb[(long long)jj * M.m + s0] = ok ? L.slot[j] - M.first : -1;
+                }
+        }
+    }
+}
+
+// smoothNormals (pgicp_normals_ext.h): one lane per row of the table.  Row i names its neighbours by position in `nrm` (entry j at
+// nb[i * rs + j * cs], -1 = none); the result goes to row out_of[i] of `out` (out_of null: row i).  After k_surface_normals<..,
+// EXT> the rows are slots: a wave's 64 points are neighbours in space, so their lists name mostly one another and the gather stays
+// in cache.  The arithmetic is the statement's: list order, sums in T, no contraction, a correctly rounded root and division.  An
+// id outside [-1, n) is never followed; it raises *bad (bad null: the table is the kernel's own).
+template <typename T>
+__global__ __launch_bounds__(128) void k_smooth_normals(const T *__restrict__ nrm, int ns, const int *__restrict__ nb, long long rs,
+                                                         long long cs, int knn, int n, const int *__restrict__ out_of,
+                                                         T *__restrict__ out, int os, int *__restrict__ bad)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const T *r = nrm + (long long)i * ns;
+    const T rx = r[0], ry = r[1], rz = r[2];
+    T ax = 0, ay = 0, az = 0;
+    bool wrong = false;
+    for (int j = 0; j < knn; j++) {
+        const int id = nb[(long long)i * rs + (long long)j * cs];
+        if (id < 0 || id >= n) { wrong = wrong || id != -1; continue; }
+        const T *p = nrm + (long long)id * ns;
+        const T px = p[0], py = p[1], pz = p[2];
+        const T d = (rx * px + ry * py) + rz * pz;
+        if (d > (T)0) { ax += px; ay += py; az += pz; }
+        else { ax -= px; ay -= py; az -= pz; }
+    }
+    if (wrong && bad) atomicOr(bad, 1);
+    const T len = sqrt_rn_t((ax * ax + ay * ay) + az * az);
+    const bool ok = len > (T)0 && len < Bits<T>::inf();
+    T *o = out + (long long)(out_of ? out_of[i] : i) * os;
+    o[0] = ok ? ax / len : rx; o[1] = ok ? ay / len : ry; o[2] = ok ? az / len : rz;
 }
 
 // KDTreeMatcher.knn > 1 (SURVEY.md A.3): the knn nearest map points of every reading point, in (distance, index) order,

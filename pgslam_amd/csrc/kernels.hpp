@@ -285,6 +285,21 @@ DensWork<T> dens_scratch(Carve &cv, int n, bool rows)
 template <typename T>
 int launch_surface_densities(hipStream_t st, const MapDev<T> *maps, int map, int m, int knn, T max_dist, T eps_rank, T *out_nrm,
                              int out_stride, T *out_eig, T *out_dens);
+
+// include/pgicp_normals_ext.h (k_normals.inc): what k_surface_normals<.., EXT> writes besides; every pointer may be null.  eigvec
+// (9 a point), mean_dist (1) and matched (knn, the ids as values of T) go to the point's original index.  raw, self and nb are
+// for the smoothing pass and travel together (raw null: none of them): in SLOT order the raw normal (3), the original index, and
+// the neighbours' slots relative to the map's first, transposed -- entry j of slot s at nb[j * m + s], -1 = none
+template <typename T>
+struct NormalsExtOut { T *eigvec, *mean_dist, *matched, *raw; int *self, *nb; };
+template <typename T>
+int launch_surface_normals_ext(hipStream_t st, const MapDev<T> *maps, int map, int m, int knn, T max_dist, T eps_rank, T *out_nrm,
+                               int out_stride, T *out_eig, int *out_ids, T *out_d2, T *out_dens, const NormalsExtOut<T> &x);
+// out[out_of ? out_of[i] : i] = the smoothed normal of row i; entry j of row i at nb[i * rs + j * cs]; *bad (zeroed here; may be
+// null) is raised by an id outside [-1, n)
+template <typename T>
+void launch_smooth_normals(hipStream_t st, const T *nrm, int ns, const int *nb, long long rs, long long cs, int knn, int n, const int *out_of,
+                           T *out, int os, int *bad);
 template <typename T>
 void launch_max_density(hipStream_t st, const T *dens, int n, T max_density, unsigned long long seed, DensStat *stat, int *keep, int *pos,
                         int *block_sums);

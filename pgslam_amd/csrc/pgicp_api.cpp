@@ -13,6 +13,7 @@
 #include "pgslam_amd/octree_host.hpp"
 #include "pgicp_normalspace.h"
 #include "pgslam_amd/normalspace_host.hpp"
+#include "pgicp_normals_ext.h"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -48,6 +49,7 @@ using namespace pgicp;
 #include "api_covsample.inc"          // pgicp_covariance_sampling_*, pgicp_covariance_sampling_framed_* (pgicp_covsample.h)
 #include "api_octree.inc"             // pgicp_octree_grid_* (pgicp_octree.h)
 #include "api_normalspace.inc"        // pgicp_normal_space_sampling_* (pgicp_normalspace.h)
+#include "api_normals_ext.inc"        // pgicp_surface_normals_ext_*, pgicp_smooth_normals_* (pgicp_normals_ext.h)
 
 extern "C" {
 

@@ -76,6 +76,10 @@ COVSAMPLE_SYMBOLS = (
 OCTREE_SYMBOLS = ("pgicp_octree_grid_f32", "pgicp_octree_grid_f64")
 # every symbol the companion header include/pgicp_normalspace.h declares (checked by tests/test_cpp_normal_space.py)
 NORMALSPACE_SYMBOLS = ("pgicp_normal_space_sampling_f32", "pgicp_normal_space_sampling_f64")
+# every symbol the companion header include/pgicp_normals_ext.h declares (checked by tests/test_cpp_surface_normals_ext.py)
+NORMALS_EXT_SYMBOLS = (
+    "pgicp_surface_normals_ext_f32", "pgicp_surface_normals_ext_f64", "pgicp_smooth_normals_f32", "pgicp_smooth_normals_f64",
+)
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -1105,6 +1109,50 @@ class Context:
             C.c_int(3), ptr(oc), ptr(oi), ptr(ob), C.byref(n_out)))
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k], bucket=ob[:k])
+
+    # ---- the rest of SurfaceNormal's outputs (include/pgicp_normals_ext.h) ------------------------
+    def surface_normals_ext(self, xyz, knn=10, max_dist=float("inf"), smooth=False, want_normals=True, want_eigen=False,
+                            want_eigen_vectors=False, want_mean_dist=False, want_matched_ids=False, want_ids=False, want_densities=False,
+                            dtype=None):
+        """SurfaceNormalDataPointsFilter with every output it can keep (pgicp_surface_normals_ext_*, statement in
+        include/pgicp_normals_ext.h).  numpy in -> numpy out, torch CUDA in -> torch CUDA out.  Returns dict(normals (n,3) --
+        smoothed when `smooth` --, eigen_values (n,3) ascending, eigen_vectors (n,9): three columns in that order, mean_dists (n,),
+        matched_ids (n,knn) in the cloud's dtype, ids (n,knn) int32, d2 (n,knn), densities (n,)); what was not asked for is None."""
+        s = _Staged(xyz, dtype=dtype)
+        x, n, mk, ptr = s.x, s.n, s.mk, s.ptr
+        md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
+        knn = int(knn)
+        k = max(knn, 0)
+        nrm = mk((n, 3)) if want_normals else None
+        eig = mk((n, 3)) if want_eigen else None
+        vec = mk((n, 9)) if want_eigen_vectors else None
+        dist = mk((n,)) if want_mean_dist else None
+        mid = mk((n, k)) if want_matched_ids else None
+        ids = mk((n, k), np.int32) if want_ids else None
+        d2 = mk((n, k)) if want_ids else None
+        dens = mk((n,)) if want_densities else None
+        self._check(s.fn(self.lib, "surface_normals_ext")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md), C.c_int(int(bool(smooth))),
+            ptr(nrm), C.c_int(3), ptr(eig), ptr(vec), ptr(dist), ptr(mid), ptr(ids), ptr(d2), ptr(dens)))
+        return dict(normals=nrm, eigen_values=eig, eigen_vectors=vec, mean_dists=dist, matched_ids=mid, ids=ids, d2=d2, densities=dens)
+
+    def smooth_normals(self, normals, ids, dtype=None):
+        """The smoothing step of SurfaceNormalDataPointsFilter{smoothNormals: 1} alone (pgicp_smooth_normals_*): `normals` (n, >= 3),
+        `ids` (n, knn) integers in the same memory, row i the neighbours of point i, -1 = none.  numpy in -> numpy out, torch CUDA
+        in -> torch CUDA out.  Returns the smoothed normals (n,3); an id outside [-1, n) raises."""
+        s = _Staged(normals, dtype=dtype)
+        x, n, mk, ptr = s.x, s.n, s.mk, s.ptr
+        if s.mem == DEVICE:
+            import torch
+            t = ids.to(torch.int32).contiguous()
+            assert t.is_cuda and t.dim() == 2 and t.shape[0] == n
+        else:
+            t = np.ascontiguousarray(ids, dtype=np.int32)
+            assert t.ndim == 2 and t.shape[0] == n
+        out = mk((n, 3))
+        self._check(s.fn(self.lib, "smooth_normals")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), ptr(t), C.c_int(int(t.shape[1])), C.c_int(n), C.c_int(x.mem), ptr(out), C.c_int(3)))
+        return out
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
