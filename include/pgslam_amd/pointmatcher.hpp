@@ -38,6 +38,8 @@
 #include "../pgicp_normalspace.h"
 #include "normalspace_host.hpp"
 #include "../pgicp_normals_ext.h"
+#include "../pgicp_quantile.h"
+#include "axis_quantile_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
 
@@ -519,6 +521,33 @@ struct PointMatcher {
                 const T r = std::sqrt((x * x + y * y) + z * z);          // Eigen's .norm() of the three coordinates, in T
                 return keepInside ? r < al : r > al;
             });
+        }
+    };
+    //! [EXT] MaxQuantileOnAxisDataPointsFilter{dim, ratio} (DataPointsFilters/MaxQuantileOnAxis.cpp, restated as recalled in
+    //! pgicp_quantile.h): keeps the points whose coordinate `dim` lies strictly below the k-th smallest one, k = (int)(T(n) * ratio)
+    //! in T.  The host form is axis_quantile_host.hpp's statement (a lone host cloud is not worth an upload); as an entry of a
+    //! device list (deviceSpec) the same cut is an exact radix select on the device.
+    struct MaxQuantileOnAxisDataPointsFilter : DataPointsFilter {
+        int dim; T ratio;
+        explicit MaxQuantileOnAxisDataPointsFilter(int d = 0, T r = (T)0.5) : dim(d), ratio(r)
+        {
+            if (!pgslam_amd::axis_quantile::dim_ok(d)) throw std::runtime_error("MaxQuantileOnAxisDataPointsFilter: dim must be 0, 1 or 2");
+            if (!pgslam_amd::axis_quantile::ratio_ok((double)r) || !(r > (T)0 && r < (T)1))
+                throw std::runtime_error("MaxQuantileOnAxisDataPointsFilter: ratio must be in [1e-7, 0.9999999]");
+        }
+        bool deviceSpec(pgicp_filter &f) const override
+        {
+            std::memset(&f, 0, sizeof f);
+            f.type = PGICP_FILTER_MAX_QUANTILE_ON_AXIS; f.p[0] = (double)dim; f.p[1] = (double)ratio;
+            return true;
+        }
+        void inPlaceFilter(DataPoints &c) override
+        {
+            const int n = (int)c.features.cols();
+            if (n == 0) return;
+            if (c.features.rows() <= dim) throw std::runtime_error("MaxQuantileOnAxisDataPointsFilter: the cloud has no coordinate `dim`");
+            const auto r = pgslam_amd::axis_quantile::select<T>(c.features.data() + dim, (long long)c.features.rows(), n, ratio);
+            compactColumns(c, [&](int j) { return c.features(dim, j) < r.limit; });
         }
     };
     //! [EXT] BoundingBoxDataPointsFilter{xMin..zMax, removeInside}: a point is inside when every coordinate lies
@@ -1296,7 +1325,7 @@ struct PointMatcher {
         }
         static std::string supportedNames()
         {
-            return " (supported: Identity, MinDist, MaxDist, BoundingBox, RemoveNaN, SurfaceNormal, "
+            return " (supported: Identity, MinDist, MaxDist, DistanceLimit, MaxQuantileOnAxis, BoundingBox, RemoveNaN, SurfaceNormal, "
                    "SamplingSurfaceNormal, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, NormalSpace, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
                    "(seeded samplers, not rand()-parity))";
         }
@@ -1319,6 +1348,26 @@ struct PointMatcher {
                     if (dim < -1 || dim > 2) throw std::runtime_error(m.name + ": dim must be -1 (radius), 0, 1 or 2");
                     const T lim = (T)to_double(m.params.count("maxDist") ? m.params.at("maxDist") : m.params.count("minDist") ? m.params.at("minDist") : "1", m.name);
                     this->push_back(std::make_shared<DistLimitDataPointsFilter>(lim, m.name == "MaxDistDataPointsFilter", dim));
+                } else if (m.name == "DistanceLimitDataPointsFilter") {
+                    // upstream's newer spelling of Min/MaxDist: removeInside = 1 keeps what MinDist keeps, 0 what MaxDist keeps
+                    allowOnly(m, {"dim", "dist", "removeInside"});
+                    const int dim = (int)get("dim", "-1");
+                    if (dim < -1 || dim > 2) throw std::runtime_error(m.name + ": dim must be -1 (radius), 0, 1 or 2");
+                    const double ri = get("removeInside", "1");
+                    if (ri != 0.0 && ri != 1.0) throw std::runtime_error(m.name + ": removeInside must be 0 or 1");
+                    this->push_back(std::make_shared<DistLimitDataPointsFilter>((T)get("dist", "1"), /*keepInside=*/ri == 0.0, dim));
+                } else if (m.name == "MaxQuantileOnAxisDataPointsFilter") {
+                    allowOnly(m, {"dim", "ratio"});
+                    // upstream's default ratio of 0.5 drops half of every scan: as a bare list entry that is an omission far more
+                    // often than a choice, so, as VoxelGrid, OctreeGrid and NormalSpace refuse their bare forms, it is refused
+                    if (!m.params.count("ratio"))
+                        throw std::runtime_error("DataPointsFilters: unsupported filter '" + m.name + "' without ratio: the default (0.5) drops half of "
+                                                 "every scan, give ratio (in [1e-7, 0.9999999])" + supportedNames());
+                    const double dim = get("dim", "0"), ratio = get("ratio", "0.5");
+                    if (dim != 0.0 && dim != 1.0 && dim != 2.0) throw std::runtime_error(m.name + ": dim must be 0, 1 or 2");
+                    if (!pgslam_amd::axis_quantile::ratio_ok(ratio) || !((T)ratio > (T)0 && (T)ratio < (T)1))
+                        throw std::runtime_error(m.name + ": ratio must be in [1e-7, 0.9999999]");
+                    this->push_back(std::make_shared<MaxQuantileOnAxisDataPointsFilter>((int)dim, (T)ratio));
                 } else if (m.name == "SurfaceNormalDataPointsFilter") {
                     // (epsilon > 0 allows an approximate neighbour search upstream; the exact search here meets every allowance)
                     if (!(get("epsilon", "0") >= 0.0)) throw std::runtime_error(m.name + ": epsilon must be >= 0");

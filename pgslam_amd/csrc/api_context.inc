@@ -120,7 +120,7 @@ struct pgicp_ctx {
     // pgicp_filter_cloud: four sets of device buffers used in turn (the filtered features of a call stay valid, as a device
     // reading, for the next three calls: a localizer that pre-processes scan k + 1 while scan k aligns, and now and then a
     // scan that was not pre-processed ahead, has three calls between making a reading and aligning it)
-    struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop; } fset[4];
+    struct FilterSet { DevBuf in_f, in_d, keep, pos, bsum, out_f, out_d, idx, drop, qsel; } fset[4];     // (qsel: a MaxQuantileOnAxis entry's scratch)
     // pgicp_sampling_surface_normal_*, pgicp_voxel_grid_* and include/pgicp_density.h share three buffers: the scratch of the call
     // running, the device copies of its host inputs / outputs, its counters.  The calls of a context are serialised on its stream
     // and none hands a pointer into these back, so every call carves them anew and they hold the largest call's need.

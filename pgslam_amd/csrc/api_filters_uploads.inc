@@ -1,10 +1,25 @@
 // api_filters_uploads.inc -- part of pgicp_api.cpp (one translation unit): input filters on the device, the batched map ABI, diagnostics of the last call, map transfer, uploads.
 // the filter list of pgicp_filter_cloud*, checked, as the launcher takes it
+// MaxQuantileOnAxis (pgicp_quantile.h): dim in {0, 1, 2}; ratio finite and, as T, in (0, 1)
 template <typename T>
-int filter_specs(pgicp_ctx *c, int nf, const pgicp_filter *f, int *types, double *params)
+bool axis_quantile_args_ok(double dim, double ratio)
 {
+    const T r = (T)ratio;
+    return (dim == 0.0 || dim == 1.0 || dim == 2.0) && std::isfinite(ratio) && r > (T)0 && r < (T)1;
+}
+
+// (*n_quantile: the list's MaxQuantileOnAxis entries -- the launcher wants their scratch)
+template <typename T>
+int filter_specs(pgicp_ctx *c, int nf, const pgicp_filter *f, int *types, double *params, int *n_quantile)
+{
+    *n_quantile = 0;
     for (int k = 0; k < nf; k++) {
-        if (f[k].type < PGICP_FILTER_IDENTITY || f[k].type > PGICP_FILTER_MAX_POINT_COUNT) return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: unknown filter type");
+        if (f[k].type < PGICP_FILTER_IDENTITY || f[k].type > PGICP_FILTER_MAX_QUANTILE_ON_AXIS) return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: unknown filter type");
+        if (f[k].type == PGICP_FILTER_MAX_QUANTILE_ON_AXIS) {
+            if (!axis_quantile_args_ok<T>(f[k].p[0], f[k].p[1]))
+                return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: MaxQuantileOnAxis needs dim in {0, 1, 2} and a finite ratio in (0, 1)");
+            ++*n_quantile;
+        }
         if (f[k].type == PGICP_FILTER_FIX_STEP && !(f[k].p[0] >= 1.0 && f[k].p[0] <= 2147483647.0))
             return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: FixStep needs 1 <= step <= INT_MAX");
         if ((f[k].type == PGICP_FILTER_MAX_DIST || f[k].type == PGICP_FILTER_MIN_DIST) &&
@@ -20,6 +35,7 @@ int filter_specs(pgicp_ctx *c, int nf, const pgicp_filter *f, int *types, double
         types[k] = f[k].type;
         std::memcpy(params + 8 * k, f[k].p, sizeof f[k].p);
         if (f[k].type == PGICP_FILTER_MAX_POINT_COUNT) params[8 * k + 2] = sizeof(T) == 4 ? 1.0 : 0.0;   // prob = T(maxCount) / T(N)
+        if (f[k].type == PGICP_FILTER_MAX_QUANTILE_ON_AXIS) params[8 * k + 1] = (double)(T)f[k].p[1];      // (ratio is held as T)
     }
     return PGICP_OK;
 }
@@ -34,7 +50,8 @@ int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat, int
     if (T16 && !is_rigid(T16)) return fail(c, PGICP_ERR_NOT_RIGID, "pgicp_filter_cloud: transformation is not rigid");
     int types[PGICP_MAX_FILTERS];
     double params[8 * PGICP_MAX_FILTERS];
-    { const int st = filter_specs<T>(c, nf, f, types, params); if (st) return st; }
+    int n_quantile = 0;
+    { const int st = filter_specs<T>(c, nf, f, types, params, &n_quantile); if (st) return st; }
     HIPC(c, hipSetDevice(c->device));
     pgicp_ctx::FilterSet &S = c->fset[c->fset_next];
     c->fset_next = (c->fset_next + 1) & 3;
@@ -52,6 +69,8 @@ int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat, int
     if (dev_desc) { HIPC(c, S.in_d.ensure(bd)); HIPC(c, S.out_d.ensure(bd)); }
     HIPC(c, S.keep.ensure(sizeof(int) * ((size_t)n + 1))); HIPC(c, S.pos.ensure(sizeof(int) * ((size_t)n + 1)));
     HIPC(c, S.bsum.ensure(sizeof(int) * scan_scratch_ints(n)));
+    AqScratch aq{};
+    if (n_quantile) { HIPC(c, S.qsel.ensure(axis_quantile_scratch_bytes(n, sizeof(T)))); aq = axis_quantile_scratch(S.qsel.p, n, sizeof(T)); }
     const bool want_idx = kept_idx || ident;
     if (want_idx) HIPC(c, S.idx.ensure(sizeof(int) * (size_t)n));
     XFER(c, h2d(c, S.in_f.p, feat, bf));
@@ -65,7 +84,7 @@ int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat, int
     launch_filter_cloud<T>(c->stream, S.in_f.as<T>(), frows, frows, dev_desc ? S.in_d.as<T>() : nullptr, drows, n, nf, types, params,
                            ident ? nullptr : T16, rot0, rot1, S.keep.as<int>(), S.pos.as<int>(), S.bsum.as<int>(), S.out_f.as<T>(),
                            dev_desc ? S.out_d.as<T>() : nullptr, want_idx ? S.idx.as<int>() : nullptr, want_drop ? S.drop.as<int>() : nullptr,
-                           want_drop ? std::min(kDropCap, n) : 0);
+                           want_drop ? std::min(kDropCap, n) : 0, n_quantile ? &aq : nullptr);
     int kept = 0;
     int drop_list[kDropCap];
     XFER(c, d2h(c, &kept, S.pos.as<int>() + n, sizeof(int)));
@@ -131,7 +150,8 @@ int filter_cloud_dev(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat,
         return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud_dev: bad argument");
     int types[PGICP_MAX_FILTERS];
     double params[8 * PGICP_MAX_FILTERS];
-    { const int st = filter_specs<T>(c, nf, f, types, params); if (st) return st; }
+    int n_quantile = 0;
+    { const int st = filter_specs<T>(c, nf, f, types, params, &n_quantile); if (st) return st; }
     HIPC(c, hipSetDevice(c->device));
     pgicp_ctx::FilterSet &S = c->fset[c->fset_next];
     c->fset_next = (c->fset_next + 1) & 3;
@@ -140,10 +160,12 @@ int filter_cloud_dev(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat,
     HIPC(c, S.in_f.ensure(bf)); HIPC(c, S.out_f.ensure(bf));
     HIPC(c, S.keep.ensure(sizeof(int) * ((size_t)n + 1))); HIPC(c, S.pos.ensure(sizeof(int) * ((size_t)n + 1)));
     HIPC(c, S.bsum.ensure(sizeof(int) * scan_scratch_ints(n)));
+    AqScratch aq{};
+    if (n_quantile) { HIPC(c, S.qsel.ensure(axis_quantile_scratch_bytes(n, sizeof(T)))); aq = axis_quantile_scratch(S.qsel.p, n, sizeof(T)); }
     HIPC(c, S.drop.ensure(sizeof(int) * (size_t)std::max(cap, 1)));
     XFER(c, h2d(c, S.in_f.p, feat, bf));
     launch_filter_cloud<T>(c->stream, S.in_f.as<T>(), frows, frows, nullptr, 0, n, nf, types, params, nullptr, -1, -1, S.keep.as<int>(), S.pos.as<int>(),
-                           S.bsum.as<int>(), S.out_f.as<T>(), nullptr, nullptr, cap ? S.drop.as<int>() : nullptr, cap);
+                           S.bsum.as<int>(), S.out_f.as<T>(), nullptr, nullptr, cap ? S.drop.as<int>() : nullptr, cap, n_quantile ? &aq : nullptr);
     // the kept count and the head of the dropped list in ONE round trip (a second one only when more than that were dropped)
     int kept = 0;
     const int head = std::min(cap, 256);

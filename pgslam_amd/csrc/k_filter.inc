@@ -21,6 +21,7 @@ struct FilterDev { int type; int pad_; double p[8]; };
 #define PGICP_F_FIX_STEP 5
 #define PGICP_F_RANDOM_SAMPLING 6
 #define PGICP_F_MAX_POINT_COUNT 7
+#define PGICP_F_MAX_QUANTILE_ON_AXIS 8       // (include/pgicp_quantile.h; its kernels: k_axisquantile.inc)
 
 __device__ __forceinline__ float sqrt_rn(float v) { return __builtin_sqrtf(v); }      // (correctly rounded; __fsqrt_rn is the native 1-ulp one)
 __device__ __forceinline__ double sqrt_rn(double v) { return __builtin_sqrt(v); }

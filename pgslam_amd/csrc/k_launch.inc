@@ -443,12 +443,50 @@ void launch_unpermute(hipStream_t st, const MapDev<T> *maps, int map, const int 
     hipLaunchKernelGGL(k_unpermute<T>, dim3(cdiv((long long)n * knn, 256)), dim3(256), 0, st, maps, map, order, slot, d2, n, knn, ids_out, d2_out);
 }
 
+// MaxQuantileOnAxis (k_axisquantile.inc): the scratch of one selection, and the selection -- the table's memset and three launches
+constexpr int kAqTableInts = kSelBins + 8;     // k_aq_hist's bins, then the candidate list's cursor
+template <typename T>
+static AqScratch aq_scratch(Carve &cv, int n)
+{
+    AqScratch w;
+    w.table = cv.take<int>(kAqTableInts);
+    w.result = cv.take<AqResult>(1);
+    w.keys = cv.take<typename Bits<T>::U>((size_t)std::max(n, 1));      // worst case: every point in the rank's bin
+    return w;
+}
+size_t axis_quantile_scratch_bytes(int n, size_t elem)
+{
+    Carve cv;
+    if (elem == 4) (void)aq_scratch<float>(cv, n); else (void)aq_scratch<double>(cv, n);
+    return cv.used;
+}
+AqScratch axis_quantile_scratch(void *base, int n, size_t elem)
+{
+    Carve cv(base);
+    return elem == 4 ? aq_scratch<float>(cv, n) : aq_scratch<double>(cv, n);
+}
+
+template <typename T>
+void launch_axis_quantile(hipStream_t st, const T *feat, int stride, int dim, int n, const int *keep, T ratio, const AqScratch &w)
+{
+    using U = typename Bits<T>::U;
+    (void)hipMemsetAsync(w.table, 0, sizeof(int) * kAqTableInts, st);
+    // about 2048 blocks at the most: every block costs one table merge
+    const int tiles = cdiv(n, kSelTile);
+    const int blocks = std::min(tiles, 2048);
+    const int span = cdiv(tiles, blocks) * kSelTile;
+    const dim3 wide(cdiv(n, span));
+    hipLaunchKernelGGL(k_aq_hist<T>, wide, dim3(256), 0, st, feat, stride, dim, n, keep, w.table, span);
+    hipLaunchKernelGGL(k_aq_filter<T>, wide, dim3(256), 0, st, feat, stride, dim, n, keep, ratio, w.table, (U *)w.keys, span);
+    hipLaunchKernelGGL(k_aq_final<T>, dim3(1), dim3(kSelectBlock), 0, st, ratio, (const int *)w.table, (const U *)w.keys, w.result);
+}
+
 // The localizer's input filters + sensor transform on the device (k_filter.inc).  `filters`: n entries of (type, p[8]) as
 // pgicp.h's pgicp_filter.  keep / pos: n + 1 ints each; block_sums: scan scratch.  pos[n] ends up holding the number kept.
 template <typename T>
 void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, const T *desc, int drows, int n, int n_filters,
                          const int *types, const double *params, const double *T16, int rot0, int rot1, int *keep, int *pos,
-                         int *block_sums, T *out_feat, T *out_desc, int *kept_idx, int *dropped, int dropped_cap)
+                         int *block_sums, T *out_feat, T *out_desc, int *kept_idx, int *dropped, int dropped_cap, const AqScratch *aq)
 {
     FilterList fl;
     std::memset(&fl, 0, sizeof fl);
@@ -459,9 +497,17 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     int k = 0;
     while (k < fl.n) {
         int e = k;
-        while (e < fl.n && fl.f[e].type != PGICP_F_FIX_STEP && fl.f[e].type != PGICP_F_RANDOM_SAMPLING && fl.f[e].type != PGICP_F_MAX_POINT_COUNT) ++e;
+        while (e < fl.n && fl.f[e].type != PGICP_F_FIX_STEP && fl.f[e].type != PGICP_F_RANDOM_SAMPLING && fl.f[e].type != PGICP_F_MAX_POINT_COUNT &&
+               fl.f[e].type != PGICP_F_MAX_QUANTILE_ON_AXIS) ++e;
         if (e > k) hipLaunchKernelGGL(k_filter_points<T>, grid, block, 0, st, feat, fstride, frows, n, fl, k, e, keep);
-        if (e < fl.n) {
+        if (e < fl.n && fl.f[e].type == PGICP_F_MAX_QUANTILE_ON_AXIS) {
+            // the third kind of entry: it looks at all the survivors before it decides -- the selection over the flags as they
+            // stand, then the cut; the limit stays on the device (aq: the caller's scratch, required with such an entry)
+            const int dim = (int)fl.f[e].p[0];
+            launch_axis_quantile<T>(st, feat, fstride, dim, n, keep, (T)fl.f[e].p[1], *aq);
+            hipLaunchKernelGGL(k_aq_apply<T>, grid, block, 0, st, feat, fstride, dim, n, (const AqResult *)aq->result, keep);
+            ++e;
+        } else if (e < fl.n) {
             launch_exclusive_scan(st, keep, n, pos, block_sums);
             hipLaunchKernelGGL(k_filter_index, grid, block, 0, st, n, fl.f[e], (const int *)pos, keep);
             ++e;
@@ -505,7 +551,8 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     template void launch_error_stats<T>(hipStream_t, const MapDev<T> *, int, const int *, const T *, int, const int *,    \
                                         const T *, int, int, const T[3], double *, double *, int);                        \
     template void launch_filter_cloud<T>(hipStream_t, const T *, int, int, const T *, int, int, int, const int *, const double *,   \
-                                         const double *, int, int, int *, int *, int *, T *, T *, int *, int *, int);       \
+                                         const double *, int, int, int *, int *, int *, T *, T *, int *, int *, int, const AqScratch *); \
+    template void launch_axis_quantile<T>(hipStream_t, const T *, int, int, int, const int *, T, const AqScratch &);         \
     template void launch_slot_of<T>(hipStream_t, const typename Vec4<T>::type *, int, int, int *);                       \
     template void launch_gd_max<T>(hipStream_t, ProblemDev *, const MapDev<T> *, const int *, int, int, const int *);     \
     template void launch_map_values<T>(hipStream_t, const typename Vec4<T>::type *, int, int, const T *, int, T *, int *); \

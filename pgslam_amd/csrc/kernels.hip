@@ -186,6 +186,7 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_select.inc"
 #include "k_minimise.inc"
 #include "k_filter.inc"
+#include "k_axisquantile.inc"
 #include "k_launch.inc"
 #include "k_ssn.inc"
 #include "k_vartrim.inc"

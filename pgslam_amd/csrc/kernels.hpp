@@ -99,10 +99,20 @@ void launch_var_trim(hipStream_t st, ProblemDev *probs, const T *d2, const int *
                      double min_ratio, double max_ratio, double lambda);
 template <typename T>
 void launch_trim_raw(hipStream_t st, const T *d2, int n, T ratio, T scale, T *limit_nf, T *w);
+// MaxQuantileOnAxis (k_axisquantile.inc): what a selection leaves on the device (limit: T's bits; count: the points it ranked), and
+// its scratch -- the bin table with the candidate list's cursor, the result, one key (T's width) per point
+struct AqResult { unsigned long long limit_bits; int k, below, count, pad_; };
+struct AqScratch { int *table; AqResult *result; void *keys; };
+size_t axis_quantile_scratch_bytes(int n, size_t elem);
+AqScratch axis_quantile_scratch(void *base, int n, size_t elem);
+// the selection over the points of [0, n) with keep[i] != 0 (keep == null: all of them); n >= 1; no host step inside
+template <typename T>
+void launch_axis_quantile(hipStream_t st, const T *feat, int stride, int dim, int n, const int *keep, T ratio, const AqScratch &w);
 template <typename T>
 void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, const T *desc, int drows, int n, int n_filters,
                          const int *types, const double *params, const double *T16, int rot0, int rot1, int *keep, int *pos,
-                         int *block_sums, T *out_feat, T *out_desc, int *kept_idx, int *dropped = nullptr, int dropped_cap = 0);
+                         int *block_sums, T *out_feat, T *out_desc, int *kept_idx, int *dropped = nullptr, int dropped_cap = 0,
+                         const AqScratch *aq = nullptr);
 template <typename T>
 void launch_slot_of(hipStream_t st, const typename Vec4<T>::type *pts, int first, int m, int *slot_of);
 template <typename T>

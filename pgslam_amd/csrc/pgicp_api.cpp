@@ -14,6 +14,7 @@
 #include "pgicp_normalspace.h"
 #include "pgslam_amd/normalspace_host.hpp"
 #include "pgicp_normals_ext.h"
+#include "pgicp_quantile.h"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -50,6 +51,7 @@ using namespace pgicp;
 #include "api_octree.inc"             // pgicp_octree_grid_* (pgicp_octree.h)
 #include "api_normalspace.inc"        // pgicp_normal_space_sampling_* (pgicp_normalspace.h)
 #include "api_normals_ext.inc"        // pgicp_surface_normals_ext_*, pgicp_smooth_normals_* (pgicp_normals_ext.h)
+#include "api_quantile.inc"           // pgicp_axis_quantile_* (pgicp_quantile.h); the list entry runs in launch_filter_cloud
 
 extern "C" {
 
@@ -201,7 +203,7 @@ void pgicp_ctx_destroy(pgicp_ctx *c)
     if (std::getenv("PGICP_GRAPH_DEBUG"))
         std::fprintf(stderr, "pgicp context %p: %lld iteration graphs captured, %lld replayed, %d failures\n", (void *)c, c->graph_captures, c->graph_launches, c->graph_failures);
     for (auto &fs : c->fset)
-        for (DevBuf *b : {&fs.in_f, &fs.in_d, &fs.keep, &fs.pos, &fs.bsum, &fs.out_f, &fs.out_d, &fs.idx}) b->release();
+        for (DevBuf *b : {&fs.in_f, &fs.in_d, &fs.keep, &fs.pos, &fs.bsum, &fs.out_f, &fs.out_d, &fs.idx, &fs.qsel}) b->release();
     for (auto &g : c->iter_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (c->stamp_dev) (void)t_free(c->stamp_dev);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -80,6 +80,8 @@ NORMALSPACE_SYMBOLS = ("pgicp_normal_space_sampling_f32", "pgicp_normal_space_sa
 NORMALS_EXT_SYMBOLS = (
     "pgicp_surface_normals_ext_f32", "pgicp_surface_normals_ext_f64", "pgicp_smooth_normals_f32", "pgicp_smooth_normals_f64",
 )
+# every symbol the companion header include/pgicp_quantile.h declares (checked by tests/test_axis_quantile_host.py)
+QUANTILE_SYMBOLS = ("pgicp_axis_quantile_f32", "pgicp_axis_quantile_f64")
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -116,6 +118,7 @@ class Filter(C.Structure):
 
 FILTER_IDENTITY, FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_REMOVE_NAN, FILTER_FIX_STEP, FILTER_RANDOM_SAMPLING, \
     FILTER_MAX_POINT_COUNT = range(8)
+FILTER_MAX_QUANTILE_ON_AXIS = 8         # (include/pgicp_quantile.h) p[0] = dim, p[1] = ratio
 
 
 class CovFrame(C.Structure):
@@ -1153,6 +1156,20 @@ class Context:
         self._check(s.fn(self.lib, "smooth_normals")(
             self.h, C.c_void_p(x.ptr), C.c_int(x.stride), ptr(t), C.c_int(int(t.shape[1])), C.c_int(n), C.c_int(x.mem), ptr(out), C.c_int(3)))
         return out
+
+    # ---- MaxQuantileOnAxis (include/pgicp_quantile.h) ------------------------
+    def axis_quantile(self, features, dim, ratio, dtype=None):
+        """The selection of MaxQuantileOnAxisDataPointsFilter{dim, ratio} over a whole cloud (pgicp_axis_quantile_*, statement in
+        include/pgicp_quantile.h): `features` (n, >= 3) a host array, a torch CUDA tensor or a DevPtr -- from device memory only
+        the three scalars come down.  Returns (limit as a scalar of the cloud's dtype, k, the number of values below limit)."""
+        x = _Buf(features if isinstance(features, DevPtr) else _unempty(features, dtype), dtype)
+        assert x.dtype in (np.float32, np.float64)
+        limit = (C.c_float if x.dtype == np.float32 else C.c_double)(0)
+        k, below = C.c_int(0), C.c_int(0)
+        fn = getattr(self.lib, "pgicp_axis_quantile" + self._sfx(x.dtype))
+        self._check(fn(self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(x.n), C.c_int(x.mem), C.c_int(int(dim)), C.c_double(float(ratio)),
+                       C.byref(limit), C.byref(k), C.byref(below)))
+        return x.dtype.type(limit.value), k.value, below.value
 
     def adopt_map(self, other: "Context", map_id: int) -> int:
         """Take over a map built by another context of the same device (pgicp_map_transfer)."""
