@@ -39,6 +39,7 @@
 #include "normalspace_host.hpp"
 #include "../pgicp_normals_ext.h"
 #include "../pgicp_quantile.h"
+#include "../pgicp_ssn_ext.h"
 #include "axis_quantile_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
@@ -178,6 +179,9 @@ template <typename T> struct Abi {
     static int sampling_normals(pgicp_ctx *c, const T *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const T *d, int dr, int avg,
                                 T *ox, T *on, T *od, int32_t *idx, int *n_out)
     { return pick<T>(pgicp_sampling_surface_normal_f32, pgicp_sampling_surface_normal_f64)(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr); }
+    static int sampling_normals_ext(pgicp_ctx *c, const T *x, int xs, int n, int knn, double r, int m, double box, uint64_t sd, const T *d, int dr, int avg,
+                                    T *ox, T *on, T *od, int32_t *idx, int *n_out, T *eig, T *vec, T *dens)
+    { return pick<T>(pgicp_sampling_surface_normal_ext_f32, pgicp_sampling_surface_normal_ext_f64)(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr, eig, vec, dens); }
     static int covariance_sampling(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pick<T>(pgicp_covariance_sampling_f32, pgicp_covariance_sampling_f64)(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
     static int normal_space(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
@@ -789,23 +793,46 @@ struct PointMatcher {
     //! It runs once per keyframe / map, on the reference (Localizer.hpp:314-315), and per loop-closure candidate: on the device
     //! (pgicp_sampling_surface_normal_*, the same bits) when there is one, unless PGSLAM_HOST_SAMPLING_NORMALS=1 or the device
     //! refuses the cloud (a NaN or infinite coordinate, an out-of-range knn); then the host recursion below.
+    //! keepDensities (`densities`, 1 row), keepEigenValues (`eigValues`, 3 rows, ascending) and keepEigenVectors (`eigVectors`, 9 rows:
+    //! three columns in that order) append the kept point's BOX's values after `normals`, in upstream's order; they go through
+    //! pgicp_sampling_surface_normal_ext_*, and the host recursion computes them by the same statement (include/pgicp_ssn_ext.h,
+    //! with its marked deviations from upstream), so the two forms agree bit for bit.  From YAML keepEigenValues and
+    //! keepEigenVectors load; `keepDensities: 1` is still refused there (a constructed filter carries densities).
     struct SamplingSurfaceNormalDataPointsFilter : DeviceBackedDataPointsFilter {
         using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
         T ratio; int knn, samplingMethod; T maxBoxDim; bool averageExistingDescriptors, keepNormals; unsigned long long seed;
+        bool keepDensities, keepEigenValues, keepEigenVectors;
         SamplingSurfaceNormalDataPointsFilter(T r = T(0.5), int k = 7, int method = 0, T box = std::numeric_limits<T>::infinity(), bool avg = true,
-                                              bool kn = true, unsigned long long sd = 1)
-            : ratio(r), knn(k), samplingMethod(method), maxBoxDim(box), averageExistingDescriptors(avg), keepNormals(kn), seed(sd) {}
+                                              bool kn = true, unsigned long long sd = 1, bool kd = false, bool ke = false, bool kev = false)
+            : ratio(r), knn(k), samplingMethod(method), maxBoxDim(box), averageExistingDescriptors(avg), keepNormals(kn), seed(sd),
+              keepDensities(kd), keepEigenValues(ke), keepEigenVectors(kev) {}
+        //! an output only pgicp_sampling_surface_normal_ext_* makes
+        bool wantsExt() const { return keepDensities || keepEigenValues || keepEigenVectors; }
+        //! upstream's order after `normals`: densities, eigValues, eigVectors (each overwritten when it exists)
+        void setExtDescriptors(DataPoints &c, const Matrix &dens, const Matrix &eig, const Matrix &vec) const
+        {
+            if (keepDensities) c.setDescriptor("densities", dens);
+            if (keepEigenValues) c.setDescriptor("eigValues", eig);
+            if (keepEigenVectors) c.setDescriptor("eigVectors", vec);
+        }
         //! the device form; false (the cloud untouched) when the device refuses the arguments
         bool deviceFilter(DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
             Matrix ox(3, n), on(3, n), od(drows > 0 ? drows : 1, n);
+            Matrix dens(1, keepDensities ? n : 0), eig(3, keepEigenValues ? n : 0), vec(9, keepEigenVectors ? n : 0);
             std::vector<int32_t> idx((size_t)n);
             int kept = 0;
-            const int st = pgslam_amd::Abi<T>::sampling_normals(ctx, c.features.data(), frows, n, knn, (double)ratio, samplingMethod, (double)maxBoxDim,
+            const int st = !wantsExt()
+                ? pgslam_amd::Abi<T>::sampling_normals(ctx, c.features.data(), frows, n, knn, (double)ratio, samplingMethod, (double)maxBoxDim,
                                                                 (uint64_t)seed, drows > 0 ? c.descriptors.data() : nullptr, drows,
                                                                 averageExistingDescriptors ? 1 : 0, ox.data(), on.data(), drows > 0 ? od.data() : nullptr,
-                                                                idx.data(), &kept);
+                                                                idx.data(), &kept)
+                : pgslam_amd::Abi<T>::sampling_normals_ext(ctx, c.features.data(), frows, n, knn, (double)ratio, samplingMethod, (double)maxBoxDim,
+                                                           (uint64_t)seed, drows > 0 ? c.descriptors.data() : nullptr, drows,
+                                                           averageExistingDescriptors ? 1 : 0, ox.data(), on.data(), drows > 0 ? od.data() : nullptr,
+                                                           idx.data(), &kept, keepEigenValues ? eig.data() : nullptr,
+                                                           keepEigenVectors ? vec.data() : nullptr, keepDensities ? dens.data() : nullptr);
             if (st == PGICP_ERR_ARG) return false;
             check(ctx, st);
             // what the host recursion leaves: the kept columns in input order, rows 0-2 from the device (the box mean with
@@ -822,6 +849,15 @@ struct PointMatcher {
             c.features = f;
             if (drows > 0) c.descriptors = d;
             if (keepNormals) c.setDescriptor("normals", nrm);
+            if (wantsExt()) {
+                // (the rows came packed: the first `kept` columns are the kept points')
+                auto head = [&](const Matrix &m, bool want) {
+                    Matrix h(m.rows(), want ? kept : 0);
+                    for (int o = 0; o < (int)h.cols(); o++) for (int r = 0; r < (int)m.rows(); r++) h(r, o) = m(r, o);
+                    return h;
+                };
+                setExtDescriptors(c, head(dens, keepDensities), head(eig, keepEigenValues), head(vec, keepEigenVectors));
+            }
             return true;
         }
         void inPlaceFilter(DataPoints &c) override
@@ -835,6 +871,8 @@ struct PointMatcher {
             for (int i = 0; i < n; i++) idx[i] = i;
             std::vector<char> keep(n, 0);
             Matrix nrm(3, n);
+            const bool ext = wantsExt();
+            Matrix dens(1, keepDensities ? n : 0), eig(3, keepEigenValues ? n : 0), vec(9, keepEigenVectors ? n : 0);
             struct Range { int first, last; T lo[3], hi[3]; };
             std::vector<Range> stack;
             Range all{0, n, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}};
@@ -884,17 +922,41 @@ struct PointMatcher {
                 for (int k = 1; k < 3; k++) { if (ev[k] < ev[l]) l = k; if (ev[k] > ev[h]) h = k; }
                 const int mid = 3 - l - h;
                 if (l == h || !(ev[h] > 0.0) || !(ev[mid] > 3.0 * (double)std::numeric_limits<T>::epsilon() * ev[h])) continue;   // rank < 2
+                // include/pgicp_ssn_ext.h: the box's density (pgicp_density.h's statement over the members, around the box's mean)
+                T boxDens = 0;
+                if (keepDensities) {
+                    T r2 = 0;
+                    for (int k = R.first; k < R.last; k++) {
+                        const int i = idx[k];
+                        const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
+                        const T q = (dx * dx + dy * dy) + dz * dz;
+                        if (q > r2) r2 = q;
+                    }
+                    const T r = std::sqrt(r2);
+                    boxDens = (T)count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
+                }
+                // ... and its eigenvalues and eigenvectors, ascending (first minimum, first maximum), to a kept point
+                auto extRows = [&](int i) {
+                    const int col[3] = {l, mid, h};
+                    if (keepDensities) dens(0, i) = boxDens;
+                    for (int cc = 0; cc < 3; cc++) {
+                        if (keepEigenValues) eig(cc, i) = (T)ev[col[cc]];
+                        if (keepEigenVectors) for (int r = 0; r < 3; r++) vec(3 * cc + r, i) = (T)V[r][col[cc]];
+                    }
+                };
                 if (samplingMethod == 0) {
                     for (int k = R.first; k < R.last; k++) {
                         const int i = idx[k];
                         if (!(seededDraw(seed, i) < (double)ratio)) continue;
                         keep[i] = 1;
                         nrm(0, i) = (T)V[0][l]; nrm(1, i) = (T)V[1][l]; nrm(2, i) = (T)V[2][l];
+                        if (ext) extRows(i);
                     }
                 } else {
                     const int i = idx[R.first];
                     keep[i] = 1;
                     nrm(0, i) = (T)V[0][l]; nrm(1, i) = (T)V[1][l]; nrm(2, i) = (T)V[2][l];
+                    if (ext) extRows(i);
                     if (drows > 0 && averageExistingDescriptors) {
                         for (int r = 0; r < drows; r++) merged(r, 0) = 0;
                         for (int k = R.first; k < R.last; k++) for (int r = 0; r < drows; r++) merged(r, 0) += c.descriptors(r, idx[k]);
@@ -905,6 +967,7 @@ struct PointMatcher {
                 }
             }
             if (keepNormals) c.setDescriptor("normals", nrm);
+            if (ext) setExtDescriptors(c, dens, eig, vec);
             compactColumns(c, [&](int j) { return keep[j] != 0; });
         }
     };
@@ -1384,15 +1447,17 @@ struct PointMatcher {
                                                                                      get("keepMeanDist", "0") != 0.0,
                                                                                      get("smoothNormals", "0") != 0.0));
                 } else if (m.name == "SamplingSurfaceNormalDataPointsFilter") {
-                    for (const char *k : {"keepDensities", "keepEigenValues", "keepEigenVectors"})
-                        if (get(k, "0") != 0.0) throw std::runtime_error(m.name + ": " + k + " is not supported");
+                    // (a constructed filter carries densities; from YAML the key stays refused)
+                    if (get("keepDensities", "0") != 0.0) throw std::runtime_error(m.name + ": keepDensities is not supported");
                     const double ratio = get("ratio", "0.5"), seed = get("seed", "1");
                     const int knn = (int)get("knn", "7"), method = (int)get("samplingMethod", "0");
                     if (!(ratio > 0.0 && ratio < 1.0) || knn < 3 || (method != 0 && method != 1) || !(seed >= 0.0 && seed < 9007199254740992.0))
                         throw std::runtime_error(m.name + ": ratio must be in (0, 1), knn >= 3, samplingMethod 0 or 1, seed in [0, 2^53)");
                     this->push_back(std::make_shared<SamplingSurfaceNormalDataPointsFilter>((T)ratio, knn, method, (T)get("maxBoxDim", "inf"),
                                                                                              get("averageExistingDescriptors", "1") != 0.0,
-                                                                                             get("keepNormals", "1") != 0.0, (unsigned long long)seed));
+                                                                                             get("keepNormals", "1") != 0.0, (unsigned long long)seed,
+                                                                                             false, get("keepEigenValues", "0") != 0.0,
+                                                                                             get("keepEigenVectors", "0") != 0.0));
                 } else if (m.name == "VoxelGridDataPointsFilter") {
                     allowOnly(m, {"vSizeX", "vSizeY", "vSizeZ", "useCentroid", "averageExistingDescriptors"});
                     // the three sizes are given together or not at all (1 m each, upstream's defaults): one or two sizes alone would

@@ -155,11 +155,17 @@ __global__ __launch_bounds__(256) void k_ssn_part(int n, const int *__restrict__
 
 // one thread per box: extent, mean and scatter sequentially in box order in T, jacobi3 in double, the rank test; the kept
 // points (method 0: each with probability ratio; method 1: the box's first) flagged with their box
-template <typename T>
+// EXT (pgicp_ssn_ext.h): the rows the kernel used to drop, per fused box -- the three eigenvalues and the three eigenvector
+// columns in ascending order (l, mid, h), and the density of the box around its mean, which takes one more walk over the
+// members (pgicp_density.h's statement: the largest squared distance by strict >, from 0).  EXT = false takes no argument for
+// it (an empty structure) and is the kernel as it was.
+struct SsnNoExt {};
+template <typename T, bool EXT = false>
 __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int xs, int n, const int *__restrict__ lst, const SsnBox *__restrict__ boxes,
                                                   int nbox, int method, T ratio, T max_box, unsigned long long seed, T eps,
                                                   int *__restrict__ keep, int *__restrict__ box_of, T *__restrict__ bnrm, T *__restrict__ bmean,
-                                                  const int *__restrict__ box_count, int *__restrict__ fused)
+                                                  const int *__restrict__ box_count, int *__restrict__ fused,
+                                                  typename std::conditional<EXT, SsnExtBox<T>, SsnNoExt>::type x = {})
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nbox || b >= *box_count) return;
@@ -203,6 +209,23 @@ __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int x
     atomicAdd(fused, 1);
     bnrm[3LL * b] = (T)V[0][l]; bnrm[3LL * b + 1] = (T)V[1][l]; bnrm[3LL * b + 2] = (T)V[2][l];
     bmean[3LL * b] = mx; bmean[3LL * b + 1] = my; bmean[3LL * b + 2] = mz;
+    if constexpr (EXT) {
+        const int col[3] = {l, mid, h};
+        T *be = x.beig + 3LL * b, *bv = x.bvec + 9LL * b;
+        for (int c = 0; c < 3; c++) {
+            be[c] = (T)ev[col[c]];
+            for (int r = 0; r < 3; r++) bv[3 * c + r] = (T)V[r][col[c]];
+        }
+        T r2 = 0;
+        for (int k = 0; k < B.count; k++) {
+            const T *p = X + (long long)member(k) * xs;
+            const T dx = p[0] - mx, dy = p[1] - my, dz = p[2] - mz;
+            const T q = (dx * dx + dy * dy) + dz * dz;
+            if (q > r2) r2 = q;
+        }
+        const T r = sqrt_rn_t(r2);
+        x.bdens[b] = (T)B.count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
+    }
     if (method == 0) {
         for (int k = 0; k < B.count; k++) {
             const int i = member(k);
@@ -218,13 +241,15 @@ __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int x
 
 // the kept points in index order: coordinates (method 1: the box mean), the box's normal, the index, the descriptors
 // (method 1 with averaging: the box's mean of each row, summed in box order in T)
-template <typename T>
+// EXT: besides, the box's eigenvalues, eigenvectors and density to each kept point (each output may be null)
+template <typename T, bool EXT = false>
 __global__ __launch_bounds__(256) void k_ssn_compact(const T *__restrict__ X, int xs, int n, const int *__restrict__ lst,
                                                      const SsnBox *__restrict__ boxes, const int *__restrict__ keep, const int *__restrict__ pos,
                                                      const int *__restrict__ box_of, const T *__restrict__ bnrm, const T *__restrict__ bmean,
                                                      int method, const T *__restrict__ desc, int drows, int average,
                                                      T *__restrict__ out_xyz, int os, T *__restrict__ out_nrm, int ns, T *__restrict__ out_desc,
-                                                     int *__restrict__ kept_idx)
+                                                     int *__restrict__ kept_idx,
+                                                     typename std::conditional<EXT, SsnExtOut<T>, SsnNoExt>::type x = {})
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !keep[i]) return;
@@ -235,6 +260,11 @@ __global__ __launch_bounds__(256) void k_ssn_compact(const T *__restrict__ X, in
     else { const T *p = X + (long long)i * xs; ox[0] = p[0]; ox[1] = p[1]; ox[2] = p[2]; }
     if (out_nrm) { T *on = out_nrm + o * ns; on[0] = bnrm[3LL * b]; on[1] = bnrm[3LL * b + 1]; on[2] = bnrm[3LL * b + 2]; }
     if (kept_idx) kept_idx[o] = i;
+    if constexpr (EXT) {
+        if (x.eig) for (int r = 0; r < 3; r++) x.eig[3 * o + r] = x.box.beig[3LL * b + r];
+        if (x.eigvec) for (int r = 0; r < 9; r++) x.eigvec[9 * o + r] = x.box.bvec[9LL * b + r];
+        if (x.dens) x.dens[o] = x.box.bdens[b];
+    }
     if (desc) {
         T *od = out_desc + o * drows;
         if (method == 1 && average) {
@@ -271,10 +301,14 @@ __global__ void k_ssn_root_box(int n, SsnBox *__restrict__ boxes, int *__restric
 }
 
 // Scratch of one call (device): see pgicp_sampling_surface_normal_*.  Returns 0, or -1 when n / knn are out of range.
-template <typename T>
-int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                            const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                            T *out_desc, int *kept_idx, int *counters /* [0] box slots, [1] boxes fused, [2] not finite, [3] kept */)
+// EXT (pgicp_ssn_ext.h): the same schedule with the EXT instantiations of the last two kernels; x names the per-box scratch and
+// the three outputs.  EXT = false launches what launch_sampling_normals always launched (those two launches keep their text and
+// their indentation).
+template <typename T, bool EXT>
+static int ssn_launch(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
+                      const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
+                      T *out_desc, int *kept_idx, int *counters /* [0] box slots, [1] boxes fused, [2] not finite, [3] kept */,
+                      typename std::conditional<EXT, SsnExtOut<T>, SsnNoExt>::type x = {})
 {
     using U = typename Bits<T>::U;
     if (n <= 0 || knn < 1 || (long long)n * 3 + 1 > 0x7FFFFFFFLL) return -1;
@@ -323,18 +357,52 @@ int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, 
         lst = w.lst[cur];
     }
     // 4. the boxes
+    if constexpr (EXT) {
+        hipLaunchKernelGGL((k_ssn_fuse<T, true>), dim3(cdiv(nbox, 128)), dim3(128), 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (int)nbox, method,
+                           ratio, max_box, seed, std::numeric_limits<T>::epsilon(), w.keep, w.box_of, (T *)w.bnrm, (T *)w.bmean, (const int *)counters, counters + 1, x.box);
+    } else {
     hipLaunchKernelGGL(k_ssn_fuse<T>, dim3(cdiv(nbox, 128)), dim3(128), 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (int)nbox, method,
                        ratio, max_box, seed, std::numeric_limits<T>::epsilon(), w.keep, w.box_of, (T *)w.bnrm, (T *)w.bmean, (const int *)counters, counters + 1);
+    }
     // 5. the kept points in index order
     scan(w.keep, n, w.pos);
+    if constexpr (EXT) {
+        hipLaunchKernelGGL((k_ssn_compact<T, true>), dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (const int *)w.keep,
+                           (const int *)w.pos, (const int *)w.box_of, (const T *)w.bnrm, (const T *)w.bmean, method, desc, drows, average, out_xyz, os,
+                           out_nrm, ns, out_desc, kept_idx, x);
+    } else {
     hipLaunchKernelGGL(k_ssn_compact<T>, dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (const int *)w.keep,
                        (const int *)w.pos, (const int *)w.box_of, (const T *)w.bnrm, (const T *)w.bmean, method, desc, drows, average, out_xyz, os,
                        out_nrm, ns, out_desc, kept_idx);
+    }
     (void)hipMemcpyAsync(counters + 3, w.pos + n, sizeof(int), hipMemcpyDeviceToDevice, st);
     return 0;
+}
+
+template <typename T>
+int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
+                            const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
+                            T *out_desc, int *kept_idx, int *counters)
+{
+    return ssn_launch<T, false>(st, X, xs, n, knn, method, ratio, max_box, seed, desc, drows, average, w, out_xyz, os, out_nrm, ns, out_desc, kept_idx,
+                                counters);
+}
+
+// pgicp_ssn_ext.h: x.box is the per-box scratch (ssn_ext_scratch), x.eig / x.eigvec / x.dens the outputs, each may be null
+template <typename T>
+int launch_sampling_normals_ext(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
+                                const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
+                                T *out_desc, int *kept_idx, int *counters, const SsnExtOut<T> &x)
+{
+    return ssn_launch<T, true>(st, X, xs, n, knn, method, ratio, max_box, seed, desc, drows, average, w, out_xyz, os, out_nrm, ns, out_desc, kept_idx,
+                               counters, x);
 }
 
 template int launch_sampling_normals<float>(hipStream_t, const float *, int, int, int, int, float, float, unsigned long long, const float *, int, int,
                                             const SsnScratch &, float *, int, float *, int, float *, int *, int *);
 template int launch_sampling_normals<double>(hipStream_t, const double *, int, int, int, int, double, double, unsigned long long, const double *, int,
                                              int, const SsnScratch &, double *, int, double *, int, double *, int *, int *);
+template int launch_sampling_normals_ext<float>(hipStream_t, const float *, int, int, int, int, float, float, unsigned long long, const float *, int, int,
+                                                const SsnScratch &, float *, int, float *, int, float *, int *, int *, const SsnExtOut<float> &);
+template int launch_sampling_normals_ext<double>(hipStream_t, const double *, int, int, int, int, double, double, unsigned long long, const double *, int,
+                                                 int, const SsnScratch &, double *, int, double *, int, double *, int *, int *, const SsnExtOut<double> &);

@@ -183,6 +183,26 @@ template <typename T>
 int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
                             const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
                             T *out_desc, int *kept_idx, int *counters);
+// include/pgicp_ssn_ext.h: what k_ssn_fuse<T, true> writes per box (3, 9 and 1 values a box slot, carved after the call's
+// SsnScratch from the same buffer) and what k_ssn_compact<T, true> copies to each kept point (every output may be null)
+template <typename T>
+struct SsnExtBox { T *beig, *bvec, *bdens; };
+template <typename T>
+struct SsnExtOut { T *eig, *eigvec, *dens; SsnExtBox<T> box; };
+template <typename T>
+SsnExtBox<T> ssn_ext_scratch(Carve &cv, int n)
+{
+    const size_t n1 = (size_t)n + 1;
+    SsnExtBox<T> b;
+    b.beig = cv.take<T>(3 * n1);
+    b.bvec = cv.take<T>(9 * n1);
+    b.bdens = cv.take<T>(n1);
+    return b;
+}
+template <typename T>
+int launch_sampling_normals_ext(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
+                                const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
+                                T *out_desc, int *kept_idx, int *counters, const SsnExtOut<T> &x);
 
 // The stable LSD radix sort of (64-bit key, index) pairs (k_pairsort.inc), 8 bits a pass, that VoxelGrid, OctreeGrid and NormalSpace
 // share: the two ping-pong buffers, the [digit][tile] counts and their scan, and the scan's block sums.  `other_scan`: the longest

@@ -82,6 +82,8 @@ NORMALS_EXT_SYMBOLS = (
 )
 # every symbol the companion header include/pgicp_quantile.h declares (checked by tests/test_axis_quantile_host.py)
 QUANTILE_SYMBOLS = ("pgicp_axis_quantile_f32", "pgicp_axis_quantile_f64")
+# every symbol the companion header include/pgicp_ssn_ext.h declares (checked by tests/test_sampling_normals_ext_host.py)
+SSN_EXT_SYMBOLS = ("pgicp_sampling_surface_normal_ext_f32", "pgicp_sampling_surface_normal_ext_f64")
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -967,6 +969,33 @@ class Context:
             C.byref(n_out), C.byref(boxes)))
         k = n_out.value
         return dict(xyz=ox[:k], normals=on[:k], kept_idx=oi[:k], descriptors=od[:k] if od is not None else None, boxes=boxes.value)
+
+    def sampling_surface_normal_ext(self, xyz, knn=7, ratio=0.5, sampling_method=0, max_box_dim=float("inf"), seed=1, descriptors=None,
+                                    average_descriptors=True, want_eigen=False, want_eigen_vectors=False, want_densities=False,
+                                    want_normals=True, dtype=None):
+        """SamplingSurfaceNormalDataPointsFilter with every output it can keep (pgicp_sampling_surface_normal_ext_*, statement in
+        include/pgicp_ssn_ext.h).  numpy in -> numpy out, torch CUDA in -> torch CUDA out.  Returns sampling_surface_normal's dict
+        and eigen_values (k,3) ascending, eigen_vectors (k,9): three columns in that order, densities (k,) -- the kept point's
+        box's; what was not asked for is None."""
+        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
+        m = max(n, 1)
+        ox, oi = mk((m, 3)), mk((m,), np.int32)
+        on = mk((m, 3)) if want_normals else None
+        od = mk((m, drows)) if d is not None else None
+        eig = mk((m, 3)) if want_eigen else None
+        vec = mk((m, 9)) if want_eigen_vectors else None
+        dens = mk((m,)) if want_densities else None
+        n_out, boxes = C.c_int(0), C.c_int(0)
+        self._check(s.fn(self.lib, "sampling_surface_normal_ext")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
+            C.c_int(sampling_method), C.c_double(max_box_dim), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
+            C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(on), C.c_int(3), ptr(od), ptr(oi),
+            C.byref(n_out), C.byref(boxes), ptr(eig), ptr(vec), ptr(dens)))
+        k = n_out.value
+        cut = lambda a: a[:k] if a is not None else None
+        return dict(xyz=ox[:k], normals=cut(on), kept_idx=oi[:k], descriptors=cut(od), boxes=boxes.value,
+                    eigen_values=cut(eig), eigen_vectors=cut(vec), densities=cut(dens))
 
     def voxel_grid(self, xyz, v_size=(1.0, 1.0, 1.0), use_centroid=True, descriptors=None, average_descriptors=True, dtype=None):
         """VoxelGridDataPointsFilter on the device (pgicp_voxel_grid_*, statement in include/pgicp.h).  numpy in -> numpy out, torch
