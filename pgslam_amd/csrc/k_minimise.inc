@@ -1,7 +1,7 @@
 // k_minimise.inc -- part of kernels.hip (one translation unit, included inside namespace pgicp): point-to-plane sums, solve + update + convergence check, Censi covariance sums.
 
 // ---------------------------------------------------------------------------
-// error minimiser: per-pair 6-DoF Jacobian, 30 sums, wave __shfl reduction
+// error minimiser: per-pair 6-DoF Jacobian, 30 sums, register fold of the wave's sums (wave_fold)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void accumulate_pair(double *acc, double w, double px, double py, double pz, double qx,
                                                 double qy, double qz, double nx, double ny, double nz)
@@ -25,16 +25,110 @@ __device__ __forceinline__ void accumulate_pair(double *acc, double w, double px
     acc[29] += w * (e * e);
 }
 
+// ---------------------------------------------------------------------------
+// T3 of the reduction tree for NT sums at once, in registers.  wave_sum(v) gives lane 0 the tree whose level o (32, 16, 8, 4, 2,
+// 1, in that order) replaces v[l] by v[l] + v[l + o] for l < o.  wave_fold adds exactly those pairs at exactly those levels for
+// each of the NT sums (IEEE addition is commutative: which lane of a pair holds the sum does not matter; nothing is
+// re-associated), but TRANSPOSES while it folds: at level o two registers (a, b) are first exchanged so that the lanes with bit o
+// clear hold both halves of a and the lanes with bit o set both halves of b, and ONE add forms the level of both.  n registers
+// become (n + 1) / 2 (an odd one out is paired with itself), and after the six levels one register holds every sum: sum k in the
+// lane whose bits are k's reversed (fold_lane).  Levels 32 / 16 are v_permlane32_swap / v_permlane16_swap per dword, levels 8 / 4
+// DPP row moves under a bank mask, levels 2 / 1 quad_perm (a bank is four lanes, so level 2 selects by lane bit instead).  No LDS
+// traffic, ~1/6 of the instructions of NT x wave_sum.
+// The swaps and DPP moves read the registers of inactive lanes as they are: ALL 64 LANES OF THE WAVE MUST BE ACTIVE here.  Every
+// return before block_reduce_store in the reduce kernels is block-uniform (a whole problem done, a whole block past the end);
+// the per-pair conditions only skip arithmetic.
+// ---------------------------------------------------------------------------
+constexpr int kDppShl4 = 0x104, kDppShr4 = 0x114, kDppRor8 = 0x128, kDppQuadXor2 = 0x4E, kDppQuadXor1 = 0xB1;
+
+__host__ __device__ constexpr int fold_lane(int k)
+{
+    return ((k & 1) << 5) | ((k & 2) << 3) | ((k & 4) << 1) | ((k & 8) >> 1) | ((k & 16) >> 3) | ((k & 32) >> 5);
+}
+
+__device__ __forceinline__ double fold_pack(unsigned lo, unsigned hi) { return __hiloint2double((int)hi, (int)lo); }
+__device__ __forceinline__ unsigned fold_lo(double v) { return (unsigned)__double2loint(v); }
+__device__ __forceinline__ unsigned fold_hi(double v) { return (unsigned)__double2hiint(v); }
+
+// levels 32 and 16: lanes [32, 64) (odd rows of 16) of a change places with lanes [0, 32) (even rows) of b
+template <int O>
+__device__ __forceinline__ double fold_swap_add(double a, double b)
+{
+    static_assert(O == 32 || O == 16, "swap levels");
+    unsigned al = fold_lo(a), ah = fold_hi(a), bl = fold_lo(b), bh = fold_hi(b);
+    if constexpr (O == 32) {
+        const auto l = __builtin_amdgcn_permlane32_swap(al, bl, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(ah, bh, false, false);
+        al = l[0]; bl = l[1]; ah = h[0]; bh = h[1];
+    } else {
+        const auto l = __builtin_amdgcn_permlane16_swap(al, bl, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(ah, bh, false, false);
+        al = l[0]; bl = l[1]; ah = h[0]; bh = h[1];
+    }
+    return fold_pack(al, ah) + fold_pack(bl, bh);
+}
+
+// x = `keep` with the lanes of the banks in BANKS replaced by src moved as CTRL says
+template <int CTRL, int BANKS>
+__device__ __forceinline__ double fold_dpp(double keep, double src)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)fold_lo(keep), (int)fold_lo(src), CTRL, 0xF, BANKS, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)fold_hi(keep), (int)fold_hi(src), CTRL, 0xF, BANKS, false);
+    return fold_pack(lo, hi);
+}
+
+// levels 8 .. 1 of a pair: lanes with bit O clear get a[l] + a[l + O], lanes with bit O set b[l - O] + b[l]
+template <int O>
+__device__ __forceinline__ double fold_row_add(double a, double b, int lane)
+{
+    if constexpr (O == 8)           // banks 2, 3 = lanes 8 .. 15 of a row take b's lanes 0 .. 7; banks 0, 1 take a's lanes 8 .. 15
+        return fold_dpp<kDppRor8, 0xC>(a, b) + fold_dpp<kDppRor8, 0x3>(b, a);
+    else if constexpr (O == 4)      // banks 1, 3 = lanes 4 .. 7, 12 .. 15 take b[l - 4]; banks 0, 2 take a[l + 4]
+        return fold_dpp<kDppShr4, 0xA>(a, b) + fold_dpp<kDppShl4, 0x5>(b, a);
+    else {
+        const bool up = (lane & O) != 0;
+        const double own = up ? b : a, sent = up ? a : b;
+        return own + fold_dpp<O == 2 ? kDppQuadXor2 : kDppQuadXor1, 0xF>(sent, sent);
+    }
+}
+
+template <int O>
+__device__ __forceinline__ double fold_pair(double a, double b, int lane)
+{
+    if constexpr (O >= 16) return fold_swap_add<O>(a, b); else return fold_row_add<O>(a, b, lane);
+}
+
+// one level: v[0 .. N) -> v[0 .. (N + 1) / 2)
+template <int O, int N>
+__device__ __forceinline__ void fold_level(double *v, int lane)
+{
+#pragma unroll
+    for (int j = 0; j < (N + 1) / 2; j++) v[j] = fold_pair<O>(v[2 * j], 2 * j + 1 < N ? v[2 * j + 1] : v[2 * j], lane);
+}
+
+// sum k of the wave ends in lane fold_lane(k) of the value returned (v is used up)
+template <int NT>
+__device__ __forceinline__ double wave_fold(double *v, int lane)
+{
+    static_assert(NT >= 1 && NT <= 64, "one lane per sum");
+    constexpr int n1 = (NT + 1) / 2, n2 = (n1 + 1) / 2, n3 = (n2 + 1) / 2, n4 = (n3 + 1) / 2, n5 = (n4 + 1) / 2;
+    fold_level<32, NT>(v, lane);
+    fold_level<16, n1>(v, lane);
+    fold_level<8, n2>(v, lane);
+    fold_level<4, n3>(v, lane);
+    fold_level<2, n4>(v, lane);
+    fold_level<1, n5>(v, lane);
+    return v[0];
+}
+
 template <int NT>
 __device__ __forceinline__ void block_reduce_store(double *acc, double *__restrict__ out)
 {
     __shared__ double red[kReduceBlock / 64][NT];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NT; k++) {
-        const double v = wave_sum(acc[k]);
-        if (lane == 0) red[wid][k] = v;
-    }
+    const double v = wave_fold<NT>(acc, lane);
+    const int k = fold_lane(lane);              // (the bit reversal is its own inverse)
+    if (k < NT) red[wid][k] = v;
     __syncthreads();
     if (threadIdx.x < NT) {
         double s = 0.0;
@@ -191,13 +285,13 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
         const int e = es[it];
         const int s = keep[it] ? ss[it] : 0;
         const int i = keep[it] ? (knn == 1 ? e : e / knn) : 0;
-        if (need_nrm) { mp[it] = M.nrm[2 * (long long)s]; mn[it] = M.nrm[2 * (long long)s + 1]; }     // one 32-byte record
-        else mp[it] = M.pts[s];
+        if (need_nrm) { mp[it] = map_rec<T>(M.nrm, 2 * (long long)s); mn[it] = map_rec<T>(M.nrm, 2 * (long long)s + 1); }     // one 32-byte record
+        else mp[it] = map_rec<T>(M.pts, s);
         const T *q = rd_pre + 3 * (P.off + i);
         qv[it][0] = q[0]; qv[it][1] = q[1]; qv[it][2] = q[2];
         if constexpr (GEN) {
             if (use_nrm) { const T *n = rd_nrm + 3 * (P.off + i); qn[it][0] = n[0]; qn[it][1] = n[1]; qn[it][2] = n[2]; }
-            if (gd) gv[it] = M.val[s - (keep[it] ? M.first : 0)];       // (s = 0 for a pair not kept: a valid index, unused)
+            if (gd) gv[it] = as_global(M.val)[s - (keep[it] ? M.first : 0)];       // (s = 0 for a pair not kept: a valid index, unused)
         }
     }
 #pragma unroll
@@ -250,9 +344,9 @@ __global__ __launch_bounds__(kReduceBlock) void k_error_stats(const MapDev<T> *_
                 const T px = rd[(long long)i * stride] - mx, py = rd[(long long)i * stride + 1] - my,
                         pz = rd[(long long)i * stride + 2] - mz;
                 const int s = slot_of[id];
-                const auto mp = M.pts[s];
+                const auto mp = map_rec<T>(M.pts, s);
                 if (MIN == 0) {
-                    const auto mn = M.nrm[2 * (long long)s + 1];
+                    const auto mn = map_rec<T>(M.nrm, 2 * (long long)s + 1);
                     accumulate_pair(acc, (double)wi, (double)px, (double)py, (double)pz, (double)mp.x, (double)mp.y,
                                     (double)mp.z, (double)mn.x, (double)mn.y, (double)mn.z);
                 } else
@@ -582,30 +676,61 @@ __global__ __launch_bounds__(kReduceBlock) void k_cov_reduce(const ProblemDev *_
     double acc[kCovTerms];
 #pragma unroll
     for (int k = 0; k < kCovTerms; k++) acc[k] = 0.0;
-    for (int it = 0; it < kReduceItems * kReduceRounds; it++) {
-        const int pos = blockIdx.x * kReduceSpan + it * kReduceBlock + threadIdx.x;
-        if (pos >= np) continue;
-        const int e = !scan_pos ? pos : knn == 1 ? scan_pos[P.off + pos] : scan_pos[P.off + pos / knn] * knn + pos % knn;
-        const T dd = d2[poff + e];
-        const int s = slot[poff + e];
-        if (s < 0 || !(dd <= limit)) continue;
+    // the stages of k_p2plane_reduce, each with kReduceItems independent loads in flight per lane:
+    // (slot, d2) -> gathered (record, reading, value) -> arithmetic; a thread adds its items u = 0 .. 7 in that order
+    using V4 = typename Vec4<T>::type;
+    const bool use_nrm = rd_nrm != nullptr;
+    for (int rnd = 0; rnd < kReduceRounds; ++rnd) {
+    const int base = blockIdx.x * kReduceSpan + rnd * (kReduceBlock * kReduceItems);
+    if (base >= np) break;
+    int ss[kReduceItems], es[kReduceItems];
+    bool keep[kReduceItems];
+    T dds[kReduceItems];
+#pragma unroll
+    for (int it = 0; it < kReduceItems; it++) {
+        const int pos = base + it * kReduceBlock + threadIdx.x;
+        int e = pos;
+        if (scan_pos && pos < np) e = knn == 1 ? scan_pos[P.off + pos] : scan_pos[P.off + pos / knn] * knn + pos % knn;
+        es[it] = e;
+        ss[it] = -1;
+        T dd = Bits<T>::inf();
+        if (pos < np) { dd = d2[poff + e]; ss[it] = slot[poff + e]; }
+        keep[it] = ss[it] >= 0 && dd <= limit;
+        dds[it] = dd;
+    }
+    V4 mps[kReduceItems], mns[kReduceItems];
+    T qv[kReduceItems][3], qn[kReduceItems][3];
+    T gv[GD ? kReduceItems : 1];
+#pragma unroll
+    for (int it = 0; it < kReduceItems; it++) {
+        const int e = es[it];
+        const int s = keep[it] ? ss[it] : 0;            // (a pair not kept: valid indices, the values unused)
+        const int i = keep[it] ? (knn == 1 ? e : e / knn) : 0;
+        mps[it] = map_rec<T>(M.nrm, 2 * (long long)s);
+        mns[it] = map_rec<T>(M.nrm, 2 * (long long)s + 1);
+        const T *q = rd_pre + 3 * (P.off + i);
+        qv[it][0] = q[0]; qv[it][1] = q[1]; qv[it][2] = q[2];
+        if (use_nrm) { const T *n = rd_nrm + 3 * (P.off + i); qn[it][0] = n[0]; qn[it][1] = n[1]; qn[it][2] = n[2]; }
+        if constexpr (GD) gv[it] = as_global(M.val)[s - (keep[it] ? M.first : 0)];
+    }
+#pragma unroll
+    for (int it = 0; it < kReduceItems; it++) {
+        if (!keep[it]) continue;
+        const T dd = dds[it];
         if constexpr (GD) {
             // the pair's Robust x GenericDescriptor weight in T, as k_p2plane_reduce forms it (the GenericDescriptor soft maximum:
             // the last iteration's); a pair of weight 0 is not an error element
             T w = rb.fct != 0 ? robust_weight<T>(rb, dd, (T)P.robust_s2) : (T)1;
-            w = w * gd_weight<T>(gd_mode, gd_thr, M.val[s - M.first], Bits<T>::val((typename Bits<T>::U)P.gd_last));
+            w = w * gd_weight<T>(gd_mode, gd_thr, gv[it], Bits<T>::val((typename Bits<T>::U)P.gd_last));
             if (w == (T)0) continue;
         } else {
             if (rb.fct != 0 && robust_weight<T>(rb, dd, (T)P.robust_s2) == (T)0) continue;      // (not an error element)
         }
-        const int i = knn == 1 ? e : e / knn;
-        const T *q = rd_pre + 3 * (P.off + i);
         T pxt, pyt, pzt;
-        apply_T<T>(Tp, q[0], q[1], q[2], pxt, pyt, pzt);
-        const auto mp = M.nrm[2 * (long long)s];
-        const auto mn = M.nrm[2 * (long long)s + 1];
-        if (rd_nrm) {                                   // (the SurfaceNormalOutlierFilter's weight of the pair: as in k_p2plane_reduce)
-            const T *n = rd_nrm + 3 * (P.off + i);
+        apply_T<T>(Tp, qv[it][0], qv[it][1], qv[it][2], pxt, pyt, pzt);
+        const V4 mp = mps[it], mn = mns[it];
+        if (use_nrm) {                                  // (the SurfaceNormalOutlierFilter's weight of the pair: as in k_p2plane_reduce)
+            const T *n = qn[it];
             T ax = ((T)Tp[0] * n[0] + (T)Tp[1] * n[1]) + (T)Tp[2] * n[2];
             T ay = ((T)Tp[4] * n[0] + (T)Tp[5] * n[1]) + (T)Tp[6] * n[2];
             T az = ((T)Tp[8] * n[0] + (T)Tp[9] * n[1]) + (T)Tp[10] * n[2];
@@ -642,6 +767,7 @@ __global__ __launch_bounds__(kReduceBlock) void k_cov_reduce(const ProblemDev *_
                 acc[21 + k] += gr[a] * gr[b] + gq[a] * gq[b];
                 k++;
             }
+    }
     }
     block_reduce_store<kCovTerms>(acc, partials + ((long long)blockIdx.y * max_blocks + blockIdx.x) * kCovTerms);
 }

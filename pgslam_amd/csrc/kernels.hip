@@ -121,6 +121,14 @@ __device__ __forceinline__ typename Vec4<T>::type load_rec(const typename Vec4<T
     const R4 r = as_global(reinterpret_cast<const R4 *>(p))[j + K];
     return make_v4(r.x, r.y, r.z, r.w);
 }
+// the reduce kernels' gather of record j (the minimiser's records are two to a slot: a 64-bit index)
+template <typename T>
+__device__ __forceinline__ typename Vec4<T>::type map_rec(const typename Vec4<T>::type *p, long long j)
+{
+    using R4 = typename Raw4<T>::type;
+    const R4 r = as_global(reinterpret_cast<const R4 *>(p))[j];
+    return make_v4(r.x, r.y, r.z, r.w);
+}
 // the same for the int tables (the cell tables of ONE map: fewer than 2^30 entries by construction)
 __device__ __forceinline__ int load_tab(const int *p, int i)
 {
