@@ -325,6 +325,7 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
             if (each_pass) {
                 unsigned long long ph[48];
                 (void)stream_sync(c);
+                (void)knn_xcc_report(use_seed, 1);
                 if (knn_phase_read(ph, 1) == 0)
                     std::fprintf(stderr, "    pass (seeded %d): wave-per-query kernel entries=%llu, longest wave %llu, longest entry %llu cycles; per entry: walk %.0f\n",
                                  use_seed, ph[46], ph[44], ph[45], (double)ph[36] / (double)std::max<unsigned long long>(1ULL, ph[46]));

@@ -114,6 +114,9 @@ void launch_transform(hipStream_t st, const T *in, int in_stride, T *out, int ou
 }
 
 // queries of one XCD's span of tiles (+ one tile: with fewer than 64 queries per wave the spans are cut elsewhere)
+// (The capacity does not depend on WHICH tiles an XCD runs, only on how many: the fast matcher's grid is a multiple of 8
+// blocks, and tile_of_block (tile_map.hpp) hands every class b & 7 exactly nb / 8 = ceil(nb / 8) of a problem's tiles for
+// every group size, as the spans did -- at most that many times `lanes` queries can reach the segment of (problem, XCD).)
 static inline int knn_q_cap(int max_n) { return (round8(cdiv(max_n, kFastBlock)) / 8) * kFastBlock + kFastBlock; }
 
 size_t knn_queue_bytes(int n_problems, int max_n, size_t elem)
@@ -128,6 +131,9 @@ static inline int env_knob(const char *name, int dflt)
     const char *v = std::getenv(name);
     return v && *v ? std::atoi(v) : dflt;
 }
+// the fast matcher's tile groups (tile_map.hpp, DESIGN §4): what an unset PGICP_TILE_GROUP means
+constexpr int kTileGroupUnset = -0x7fffffff;
+constexpr int kTileGroupDefault = 4;
 
 template <typename T>
 void launch_knn(hipStream_t st, int matcher, const ProblemDev *probs, const MapDev<T> *maps, const T *rd, int *slot,
@@ -162,13 +168,16 @@ void launch_knn(hipStream_t st, int matcher, const ProblemDev *probs, const MapD
         if ((long long)P * max_n >= 50000)
             while (lanes > 16 && (long long)P * cdiv(max_n, lanes >> 1) <= 8192) lanes >>= 1;
         if (forced_lanes > 0) lanes = std::min(forced_lanes, kFastBlock);
+        // tiles per group dealt round the XCDs (tile_of_block, tile_map.hpp): PGICP_TILE_GROUP; <= 0 one contiguous span per XCD
+        static const int forced_group = env_knob("PGICP_TILE_GROUP", kTileGroupUnset);
+        const int tile_group = forced_group != kTileGroupUnset ? forced_group : kTileGroupDefault;
         // (table_kinds: bit 0 -- some map of the batch carries the dense tables, bit 1 -- some map the succinct one)
         if (table_kinds & 1)
             hipLaunchKernelGGL((k_knn_grid<T, 1, 0>), dim3(round8(cdiv(max_n, lanes)), P), dim3(kFastBlock), 0, st, probs, maps, rd, slot, d2, ch,
-                               use_seed, fast_rings, seg_count, seg_list, seg_lb, seg_ring, active, none_r, q_cap, lanes);
+                               use_seed, fast_rings, seg_count, seg_list, seg_lb, seg_ring, active, none_r, q_cap, lanes, tile_group);
         if (table_kinds & 2)
             hipLaunchKernelGGL((k_knn_grid<T, 1, 1>), dim3(round8(cdiv(max_n, lanes)), P), dim3(kFastBlock), 0, st, probs, maps, rd, slot, d2, ch,
-                               use_seed, fast_rings, seg_count, seg_list, seg_lb, seg_ring, active, none_r, q_cap, lanes);
+                               use_seed, fast_rings, seg_count, seg_list, seg_lb, seg_ring, active, none_r, q_cap, lanes, tile_group);
     }
     if (P <= 8) {                                     // up to eight ACTIVE problems -- a small batch, or the last iterations of a large one
                                                       // (a finished problem's counters are zero: its last first selection cleared them): see k_queue_small

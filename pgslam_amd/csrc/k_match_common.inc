@@ -75,6 +75,30 @@ __device__ unsigned long long g_slow_worst[16];      // the slowest entry of the
 #define SPH_FLUSH() do { } while (0)
 #endif
 
+#ifdef PGICP_XCC_STATS
+// Diagnostics build of its own (-DPGICP_XCC_STATS alone: the phase marks above make a wave wait for its loads at every mark
+// and triple the kernel's time): how a launch of the fast kernel spreads over the XCDs.  Per hardware XCC (the XCC_ID
+// register) and launch: [0] ~(first start of a wave), [1] last end, [2] wave time summed, [3] waves, [8 + c] waves of the
+// blocks with blockIdx.x & 7 == c -- on the constant 100 MHz clock all XCDs share.  Two clock reads and six atomics without
+// a return value per wave, into one of kXccCopies 128-byte lines of the wave's XCC (each touched by that XCD's L2 only; with
+// ONE line per XCC the 150 000 atomics of a seeded launch's short waves queued on it for 1.2 ms and levelled the XCDs' end
+// times); zero means "nothing yet" everywhere (hence the complement in [0]).  Read with PGICP_PHASE_EACH_PASS=1
+// (knn_xcc_report), digested by tools/xcd_balance.py.
+constexpr int kXccCopies = 32;
+__device__ unsigned long long g_xcc[8][kXccCopies][16];
+#define XCC_BEGIN() const unsigned long long xc_t0 = wall_clock64()
+#define XCC_END() do {                                                                                                      \
+        if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) {                                              \
+            const unsigned long long xc_t1 = wall_clock64();                                                                \
+            unsigned long long *xc_ = g_xcc[__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u][(blockIdx.x >> 3) % kXccCopies];   /* hwreg(HW_REG_XCC_ID, 0, 4) */ \
+            atomicMax(xc_ + 0, ~xc_t0); atomicMax(xc_ + 1, xc_t1); atomicAdd(xc_ + 2, xc_t1 - xc_t0); atomicAdd(xc_ + 3, 1ULL); \
+            atomicAdd(xc_ + 8 + (blockIdx.x & 7u), 1ULL);                                                                   \
+        } } while (0)
+#else
+#define XCC_BEGIN() do { } while (0)
+#define XCC_END() do { } while (0)
+#endif
+
 // (squared distance, index) as one 64-bit key: distances are >= +0, so the order of the keys is the matcher's order --
 // smaller distance first, then smaller index
 __device__ __forceinline__ unsigned long long item_key(float d2, int idx)

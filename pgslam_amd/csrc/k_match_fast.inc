@@ -152,7 +152,7 @@ __global__ __launch_bounds__(kFastBlock) PGICP_FAST_ATTR void k_knn_grid(const P
                                                   T *__restrict__ d2_out, ChainDev<T> ch, int use_seed, int fast_rings,
                                                   int *__restrict__ slow_count, int2 *__restrict__ slow_list,
                                                   T *__restrict__ slow_lb, int *__restrict__ slow_ring,
-                                                  const int *__restrict__ active, T *__restrict__ none_r, int q_cap, int lanes)
+                                                  const int *__restrict__ active, T *__restrict__ none_r, int q_cap, int lanes, int tile_group)
 {
     using V4 = typename Vec4<T>::type;
     constexpr int NR = (2 * R + 1) * (2 * R + 1);
@@ -169,13 +169,15 @@ __global__ __launch_bounds__(kFastBlock) PGICP_FAST_ATTR void k_knn_grid(const P
     const int prob = active[blockIdx.y];           // only problems still iterating are launched
     const ProblemDev &P = probs[prob];
     if (P.done) return;
-    const int tile = xcd_tile(blockIdx.x, gridDim.x);
+    // (which tile: groups of `tile_group` tiles dealt round the XCDs, tile_map.hpp; the queue segment stays keyed by the XCD)
+    const int tile = tile_of_block(blockIdx.x, gridDim.x, tile_group);
     const int lane = threadIdx.x;
     // `lanes` queries per wave: 64 when the launch fills the chip; a small launch (one streamed scan) is spread over more
     // waves with fewer queries each -- a wave walks as long as its busiest lane, and idle SIMDs cost nothing
     const int i = tile * lanes + lane;
     if (tile * lanes >= P.n) return;
     PHASE_BEGIN();
+    XCC_BEGIN();
     bool live = lane < lanes && i < P.n;
     const MapDev<T> M = maps[P.map];
     if ((M.sw != nullptr) != (TK == 1)) return;
@@ -429,7 +431,7 @@ __global__ __launch_bounds__(kFastBlock) PGICP_FAST_ATTR void k_knn_grid(const P
     }
 #endif
     PHASE_MARK(4);
-    if (!__any(live)) PHASE_FLUSH();
+    if (!__any(live)) { PHASE_FLUSH(); XCC_END(); }
     if constexpr (!kBallPool) { if (!live) return; }
 
     // ---- phase B: continuation from ring R+1 ----
@@ -485,4 +487,5 @@ __global__ __launch_bounds__(kFastBlock) PGICP_FAST_ATTR void k_knn_grid(const P
                     free_r, slot_io, d2_out, none_r, slow_count, slow_list, slow_lb, slow_ring, q_cap);
     PHASE_MARK(6);
     PHASE_FLUSH();
+    XCC_END();
 }

@@ -591,6 +591,32 @@ int knn_phase_read(unsigned long long out[48], int reset)
 #endif
 }
 
+// diagnostics build (-DPGICP_XCC_STATS) only: the fast matcher's launches since the last reset, per hardware XCC, to stderr
+int knn_xcc_report(int use_seed, int reset)
+{
+#ifdef PGICP_XCC_STATS
+    static unsigned long long h[8][kXccCopies][16];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_xcc), sizeof h) != hipSuccess) return -1;
+    unsigned long long x[8][16] = {};
+    for (int c = 0; c < 8; c++)
+        for (int k = 0; k < kXccCopies; k++)
+            for (int s = 0; s < 16; s++) x[c][s] = s < 2 ? std::max(x[c][s], h[c][k][s]) : x[c][s] + h[c][k][s];
+    unsigned long long first = ~0ULL;
+    for (int c = 0; c < 8; c++) if (x[c][3]) first = std::min(first, ~x[c][0]);
+    std::fprintf(stderr, "    fast kernel per XCC (seeded %d) [last end after the launch's first start | wave time summed | waves | waves by blockIdx.x & 7], ticks of 10 ns:", use_seed);
+    for (int c = 0; c < 8; c++) {
+        std::fprintf(stderr, " %llu|%llu|%llu|", x[c][3] ? x[c][1] - first : 0ULL, x[c][2], x[c][3]);
+        for (int k = 0; k < 8; k++) std::fprintf(stderr, "%s%llu", k ? "," : "", x[c][8 + k]);
+    }
+    std::fprintf(stderr, "\n");
+    if (reset) { std::memset(h, 0, sizeof h); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_xcc), h, sizeof h); }
+    return 0;
+#else
+    (void)use_seed; (void)reset;
+    return -1;
+#endif
+}
+
 int knn_stats_read(unsigned long long out[56], int reset)
 {
 #ifdef PGICP_KNN_STATS

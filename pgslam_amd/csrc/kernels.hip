@@ -9,6 +9,7 @@
 //
 // wave = 64 lanes everywhere; no warp-size-32 idiom is used.
 #include "kernels.hpp"
+#include "tile_map.hpp"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -64,6 +65,8 @@ __device__ __forceinline__ double4 make_v4(double x, double y, double z, double 
 // Blocks b and b+8 share an XCD (round-robin dispatch, observed; used for L2
 // locality only).  Give every XCD one contiguous span of tiles so that the map
 // cells a span touches stay in that XCD's 4 MiB L2.  Bijective for any nb.
+// (The reduce kernels' map.  The fast matcher, whose tiles do not cost the same, deals groups of tiles round the
+// XCDs: tile_of_block, tile_map.hpp -- this function is its G <= 0 case.)
 __device__ __forceinline__ int xcd_tile(int b, int nb)
 {
     const int q = nb >> 3, r = nb & 7;

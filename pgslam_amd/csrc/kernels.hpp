@@ -46,6 +46,7 @@ size_t trim_select_table_bytes(int P);
 int sel_fallbacks_read(int reset);
 int knn_stats_read(unsigned long long out[56], int reset);
 int knn_phase_read(unsigned long long out[48], int reset);   // diagnostics build only: wave cycles per phase of the fast kernel
+int knn_xcc_report(int use_seed, int reset);                 // diagnostics build (-DPGICP_XCC_STATS) only: the fast kernel's launches per XCC
 int knn_dump_setup(long long total, int passes);              // diagnostics build only: per-query candidate dump
 int knn_dump_read(unsigned *cnt, float *d2, long long n);
 int knn_trace_set(int sorted_index);                       // diagnostics build only   // diagnostics build (-DPGICP_KNN_STATS) only
