@@ -300,20 +300,15 @@ __global__ void k_ssn_root_box(int n, SsnBox *__restrict__ boxes, int *__restric
     *box_count = 1;
 }
 
-// Scratch of one call (device): see pgicp_sampling_surface_normal_*.  Returns 0, or -1 when n / knn are out of range.
-// EXT (pgicp_ssn_ext.h): the same schedule with the EXT instantiations of the last two kernels; x names the per-box scratch and
-// the three outputs.  EXT = false launches what launch_sampling_normals always launched (those two launches keep their text and
-// their indentation).
-template <typename T, bool EXT>
-static int ssn_launch(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                      const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                      T *out_desc, int *kept_idx, int *counters /* [0] box slots, [1] boxes fused, [2] not finite, [3] kept */,
-                      typename std::conditional<EXT, SsnExtOut<T>, SsnNoExt>::type x = {})
+// Steps 1.-3. of one call: the counters and the keep flags cleared, the three lists sorted, the tree cut level by level, the box
+// list made.  Returns the lists the boxes' member ranges index (w.lst[0] or w.lst[1]); `nbox` gets the number of boxes the tree has.
+// (Shared by the SamplingSurfaceNormal launcher below and by k_elipsoids.inc: the same launches in the same order.)
+template <typename T>
+static const int *ssn_build_tree(hipStream_t st, const T *X, int xs, int n, int knn, const SsnScratch &w, int *counters, long long &nbox)
 {
     using U = typename Bits<T>::U;
-    if (n <= 0 || knn < 1 || (long long)n * 3 + 1 > 0x7FFFFFFFLL) return -1;
     std::map<long long, long long> memo;
-    const long long nbox = ssn_leaves(n, knn, memo);
+    nbox = ssn_leaves(n, knn, memo);
     const dim3 b256(256);
     const long long n3 = 3LL * n;
     (void)hipMemsetAsync(counters, 0, 4 * sizeof(int), st);
@@ -356,6 +351,25 @@ static int ssn_launch(hipStream_t st, const T *X, int xs, int n, int knn, int me
         }
         lst = w.lst[cur];
     }
+    return lst;
+}
+
+// Scratch of one call (device): see pgicp_sampling_surface_normal_*.  Returns 0, or -1 when n / knn are out of range.
+// EXT (pgicp_ssn_ext.h): the same schedule with the EXT instantiations of the last two kernels; x names the per-box scratch and
+// the three outputs.  EXT = false launches what launch_sampling_normals always launched (those two launches keep their text and
+// their indentation).
+template <typename T, bool EXT>
+static int ssn_launch(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
+                      const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
+                      T *out_desc, int *kept_idx, int *counters /* [0] box slots, [1] boxes fused, [2] not finite, [3] kept */,
+                      typename std::conditional<EXT, SsnExtOut<T>, SsnNoExt>::type x = {})
+{
+    if (n <= 0 || knn < 1 || (long long)n * 3 + 1 > 0x7FFFFFFFLL) return -1;
+    long long nbox = 0;
+    const int *lst = ssn_build_tree<T>(st, X, xs, n, knn, w, counters, nbox);
+    const dim3 b256(256);
+    auto scan = [&](const int *in, int len, int *out) { launch_exclusive_scan(st, in, len, out, w.bsum); };
+    const SsnBox *boxes = (const SsnBox *)w.boxes;
     // 4. the boxes
     if constexpr (EXT) {
         hipLaunchKernelGGL((k_ssn_fuse<T, true>), dim3(cdiv(nbox, 128)), dim3(128), 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (int)nbox, method,

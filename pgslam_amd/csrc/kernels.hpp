@@ -2,6 +2,10 @@
 #pragma once
 #include "device_types.hpp"
 #include "pgslam_amd/octree_host.hpp"
+#ifdef __HIPCC__
+#define PGSLAM_ELIP_HD __host__ __device__
+#endif
+#include "pgslam_amd/elipsoids_host.hpp"
 
 namespace pgicp {
 
@@ -204,6 +208,36 @@ template <typename T>
 int launch_sampling_normals_ext(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
                                 const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
                                 T *out_desc, int *kept_idx, int *counters, const SsnExtOut<T> &x);
+
+// include/pgicp_elipsoids.h (k_elipsoids.inc): the tree, SsnScratch and the counters are SamplingSurfaceNormal's.  ElipBox: what
+// k_elip_fuse<T, true> writes per box slot besides SsnScratch's bnrm / bmean -- 3, 9, 1, 9, 1 and 3 values; a null pointer is a row
+// nobody asked for, and is not written.  ElipOut: what k_elip_compact<T, true> copies to each kept point (every output may be null;
+// `means` is gathered from bmean).  The scratch's size does not depend on what is asked for.
+template <typename T>
+struct ElipBox { T *beig, *bvec, *bdens, *bcov, *bweight, *bshape; };
+template <typename T>
+struct ElipOut {
+    T *eig, *eigvec, *dens, *cov, *weights, *means, *shapes;
+    ElipBox<T> box;
+    bool any() const { return eig || eigvec || dens || cov || weights || means || shapes; }
+};
+template <typename T>
+ElipBox<T> elip_scratch(Carve &cv, int n, const ElipOut<T> &want)
+{
+    const size_t n1 = (size_t)n + 1;
+    ElipBox<T> b;
+    b.beig = cv.take<T>(3 * n1, want.eig != nullptr);
+    b.bvec = cv.take<T>(9 * n1, want.eigvec != nullptr);
+    b.bdens = cv.take<T>(n1, want.dens != nullptr);
+    b.bcov = cv.take<T>(9 * n1, want.cov != nullptr);
+    b.bweight = cv.take<T>(n1, want.weights != nullptr);
+    b.bshape = cv.take<T>(3 * n1, want.shapes != nullptr);
+    return b;
+}
+template <typename T>
+int launch_elipsoids(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, T min_planarity, unsigned long long seed,
+                     const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns, T *out_desc,
+                     int *kept_idx, int *counters, const ElipOut<T> &x);
 
 // The stable LSD radix sort of (64-bit key, index) pairs (k_pairsort.inc), 8 bits a pass, that VoxelGrid, OctreeGrid and NormalSpace
 // share: the two ping-pong buffers, the [digit][tile] counts and their scan, and the scan's block sums.  `other_scan`: the longest

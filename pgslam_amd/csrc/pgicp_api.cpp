@@ -16,6 +16,7 @@
 #include "pgicp_normals_ext.h"
 #include "pgicp_quantile.h"
 #include "pgicp_ssn_ext.h"
+#include "pgicp_elipsoids.h"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -54,6 +55,7 @@ using namespace pgicp;
 #include "api_normals_ext.inc"        // pgicp_surface_normals_ext_*, pgicp_smooth_normals_* (pgicp_normals_ext.h)
 #include "api_quantile.inc"           // pgicp_axis_quantile_* (pgicp_quantile.h); the list entry runs in launch_filter_cloud
 #include "api_ssn_ext.inc"            // pgicp_sampling_surface_normal_ext_* (pgicp_ssn_ext.h)
+#include "api_elipsoids.inc"          // pgicp_elipsoids_* (pgicp_elipsoids.h)
 
 extern "C" {
 

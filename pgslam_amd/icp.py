@@ -84,6 +84,8 @@ NORMALS_EXT_SYMBOLS = (
 QUANTILE_SYMBOLS = ("pgicp_axis_quantile_f32", "pgicp_axis_quantile_f64")
 # every symbol the companion header include/pgicp_ssn_ext.h declares (checked by tests/test_sampling_normals_ext_host.py)
 SSN_EXT_SYMBOLS = ("pgicp_sampling_surface_normal_ext_f32", "pgicp_sampling_surface_normal_ext_f64")
+# every symbol the companion header include/pgicp_elipsoids.h declares (checked by tests/test_elipsoids_host.py)
+ELIPSOIDS_SYMBOLS = ("pgicp_elipsoids_f32", "pgicp_elipsoids_f64")
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -996,6 +998,36 @@ class Context:
         cut = lambda a: a[:k] if a is not None else None
         return dict(xyz=ox[:k], normals=cut(on), kept_idx=oi[:k], descriptors=cut(od), boxes=boxes.value,
                     eigen_values=cut(eig), eigen_vectors=cut(vec), densities=cut(dens))
+
+    ELIPSOIDS_ROWS = dict(normals=3, densities=1, eigen_values=3, eigen_vectors=9, covariance=9, weights=1, means=3, shapes=3)
+
+    def elipsoids(self, xyz, knn=7, ratio=0.5, method=0, max_box=float("inf"), min_planarity=0.0, seed=1, desc=None, average=True,
+                  keep=("normals",), mem=None, dtype=None):
+        """ElipsoidsDataPointsFilter on the device (pgicp_elipsoids_*, statement in include/pgicp_elipsoids.h).  numpy in -> numpy out,
+        torch CUDA in -> torch CUDA out; `mem` ("host" or "device"), when given, must name the memory xyz lies in.  `keep`: the rows
+        asked for, of ELIPSOIDS_ROWS.  Returns sampling_surface_normal_ext's dict and covariance (k,9), weights (k,), means (k,3),
+        shapes (k,3): planarity, cylindricality, sphericality -- the kept point's box's; what was not asked for is None."""
+        unknown = set(keep) - set(self.ELIPSOIDS_ROWS)
+        if unknown:
+            raise ValueError(f"elipsoids: unknown rows {sorted(unknown)} (known: {sorted(self.ELIPSOIDS_ROWS)})")
+        s = _Staged(xyz, descriptors=desc, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
+        if mem is not None and {"host": HOST, "device": DEVICE}[mem] != x.mem:
+            raise ValueError(f"elipsoids: mem={mem!r} but xyz lies in {'host' if x.mem == HOST else 'device'} memory")
+        m = max(n, 1)
+        ox, oi = mk((m, 3)), mk((m,), np.int32)
+        od = mk((m, drows)) if d is not None else None
+        rows = {k: (mk((m, w) if w > 1 else (m,)) if k in keep else None) for k, w in self.ELIPSOIDS_ROWS.items()}
+        n_out, boxes = C.c_int(0), C.c_int(0)
+        self._check(s.fn(self.lib, "elipsoids")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
+            C.c_int(method), C.c_double(max_box), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
+            C.c_int(int(bool(average))), ptr(ox), C.c_int(3), ptr(rows["normals"]), C.c_int(3), ptr(od), ptr(oi),
+            C.byref(n_out), C.byref(boxes), ptr(rows["eigen_values"]), ptr(rows["eigen_vectors"]), ptr(rows["densities"]),
+            C.c_double(min_planarity), ptr(rows["covariance"]), ptr(rows["weights"]), ptr(rows["means"]), ptr(rows["shapes"])))
+        k = n_out.value
+        cut = lambda a: a[:k] if a is not None else None
+        return dict(xyz=ox[:k], kept_idx=oi[:k], descriptors=cut(od), boxes=boxes.value, **{key: cut(a) for key, a in rows.items()})
 
     def voxel_grid(self, xyz, v_size=(1.0, 1.0, 1.0), use_centroid=True, descriptors=None, average_descriptors=True, dtype=None):
         """VoxelGridDataPointsFilter on the device (pgicp_voxel_grid_*, statement in include/pgicp.h).  numpy in -> numpy out, torch
