@@ -42,6 +42,8 @@
 #include "../pgicp_ssn_ext.h"
 #include "../pgicp_elipsoids.h"
 #include "elipsoids_host.hpp"
+#include "../pgicp_sensor_chain.h"
+#include "sensor_chain_host.hpp"
 #include "axis_quantile_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
@@ -187,6 +189,9 @@ template <typename T> struct Abi {
     static int elipsoids(pgicp_ctx *c, const T *x, int xs, int n, int knn, double r, int m, double box, double minp, uint64_t sd, const T *d, int dr, int avg,
                          T *ox, T *on, T *od, int32_t *idx, int *n_out, T *eig, T *vec, T *dens, T *cov, T *wgt, T *mean, T *shp)
     { return pick<T>(pgicp_elipsoids_f32, pgicp_elipsoids_f64)(c, x, xs, n, PGICP_HOST, knn, r, m, box, sd, d, dr, avg, ox, 3, on, 3, od, idx, n_out, nullptr, eig, vec, dens, minp, cov, wgt, mean, shp); }
+    static int sensor_chain(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, int kn, int ke, int kd, int ns, const pgicp_chain_stage *st, const T *d, int dr,
+                            T *ox, T *on, T *oe, T *odn, T *oobs, T *onoise, T *od, int32_t *idx, int *n_out)
+    { return pick<T>(pgicp_sensor_chain_f32, pgicp_sensor_chain_f64)(c, x, xs, n, PGICP_HOST, knn, md, kn, ke, kd, ns, st, d, dr, ox, on, 3, oe, odn, oobs, onoise, od, idx, n_out); }
     static int covariance_sampling(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pick<T>(pgicp_covariance_sampling_f32, pgicp_covariance_sampling_f64)(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
     static int normal_space(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
@@ -600,8 +605,12 @@ struct PointMatcher {
         {
             const int n = (int)c.features.cols();
             Matrix d(3, n);
-            for (int j = 0; j < n; j++)
-                for (int a = 0; a < 3; a++) d(a, j) = c0[a] - c.features(a, j);
+            for (int j = 0; j < n; j++) {
+                const T x[3] = {c.features(0, j), c.features(1, j), c.features(2, j)};
+                T o[3];
+                pgslam_amd::sensor_chain::observation_direction<T>(c0, x, o);
+                for (int a = 0; a < 3; a++) d(a, j) = o[a];
+            }
             c.addDescriptor("observationDirections", d);
         }
     };
@@ -617,9 +626,9 @@ struct PointMatcher {
             const int rn = c.getDescriptorStartingRow("normals"), ro = c.getDescriptorStartingRow("observationDirections");
             const int n = (int)c.features.cols();
             for (int j = 0; j < n; j++) {
-                T dot = 0;
-                for (int a = 0; a < 3; a++) dot += c.descriptors(rn + a, j) * c.descriptors(ro + a, j);
-                if (towardCenter ? dot < 0 : dot > 0)
+                const T nv[3] = {c.descriptors(rn, j), c.descriptors(rn + 1, j), c.descriptors(rn + 2, j)};
+                const T ov[3] = {c.descriptors(ro, j), c.descriptors(ro + 1, j), c.descriptors(ro + 2, j)};
+                if (pgslam_amd::sensor_chain::orient_flips<T>(nv, ov, towardCenter))
                     for (int a = 0; a < 3; a++) c.descriptors(rn + a, j) = -c.descriptors(rn + a, j);
             }
         }
@@ -629,19 +638,15 @@ struct PointMatcher {
     //! origin.  Needs the normals descriptor; host side (it reads a descriptor the device input stage does not carry).
     struct ShadowDataPointsFilter : DataPointsFilter {
         T epsAngle, eps;
-        explicit ShadowDataPointsFilter(T e) : epsAngle(e), eps(std::sin(e)) {}
+        explicit ShadowDataPointsFilter(T e) : epsAngle(e), eps(pgslam_amd::sensor_chain::shadow_threshold<T>(e)) {}
         void inPlaceFilter(DataPoints &c) override
         {
             if (!c.descriptorExists("normals")) throw std::runtime_error("ShadowDataPointsFilter: cannot find normals in descriptors");
             const int rn = c.getDescriptorStartingRow("normals");
-            auto normalized = [](T &x, T &y, T &z) { const T zz = (x * x + y * y) + z * z; if (zz > T(0)) { const T s = std::sqrt(zz); x = x / s; y = y / s; z = z / s; } };
             compactColumns(c, [&](int j) {
-                T ax = c.descriptors(rn, j), ay = c.descriptors(rn + 1, j), az = c.descriptors(rn + 2, j);
-                T bx = c.features(0, j), by = c.features(1, j), bz = c.features(2, j);
-                normalized(ax, ay, az);
-                normalized(bx, by, bz);
-                const T d = (ax * bx + ay * by) + az * bz;
-                return (d < T(0) ? -d : d) > eps;
+                const T nv[3] = {c.descriptors(rn, j), c.descriptors(rn + 1, j), c.descriptors(rn + 2, j)};
+                const T x[3] = {c.features(0, j), c.features(1, j), c.features(2, j)};
+                return pgslam_amd::sensor_chain::shadow_keep<T>(nv, x, eps);
             });
         }
     };
@@ -1567,17 +1572,13 @@ struct PointMatcher {
         }
         void inPlaceFilter(DataPoints &c) override
         {
-            static const T prm[5][3] = {{T(0.012), T(0.0068), T(0.0008)}, {T(0.028), T(0.0013), T(0.0001)}, {T(0.018), T(0.0006), T(0.0015)},
-                                        {T(0), T(0), T(0)}, {T(0.004), T(0.0053), T(-0.0092)}};
+            pgslam_amd::sensor_chain::NoiseModel<T> model;
+            pgslam_amd::sensor_chain::noise_model<T>(sensorType, gain, model);          // (the constructor has checked the type)
             const int n = (int)c.features.cols();
             Matrix noise(1, n);
             for (int i = 0; i < n; i++) {
-                const T x = c.features(0, i), y = c.features(1, i), z = c.features(2, i);
-                const T r = std::sqrt((x * x + y * y) + z * z);
-                T v;
-                if (sensorType == 3) v = (r * r) * (T)(0.5 * 0.00285);
-                else { v = prm[sensorType][1] * r + prm[sensorType][2]; if (v < prm[sensorType][0]) v = prm[sensorType][0]; }
-                noise(0, i) = gain * v;
+                const T x[3] = {c.features(0, i), c.features(1, i), c.features(2, i)};
+                noise(0, i) = pgslam_amd::sensor_chain::noise_value<T>(model, x);
             }
             c.setDescriptor("simpleSensorNoise", noise);
         }
@@ -1773,11 +1774,129 @@ struct PointMatcher {
             }
         }
         void init() { for (auto &f : *this) f->init(); }
-        //! the filters in order; one pattern is fused: SurfaceNormalDataPointsFilter{keepDensities} directly followed by
-        //! MaxDensityDataPointsFilter runs as one device pass (MaxDensityDataPointsFilter::fusedWith), every other list as before
+        size_t lastFused = 0;
+        //! A sensor-chain RUN starting at filter k (include/pgicp_sensor_chain.h): the longest contiguous sub-list from k made of one
+        //! SurfaceNormalDataPointsFilter (no ext output, knn in [3, 32]) and ObservationDirection, OrientNormals, Shadow, MaxDensity,
+        //! SimpleSensorNoise, each at most once, that the device call accepts -- only ObservationDirection and SimpleSensorNoise may
+        //! stand ahead of the SurfaceNormal (they read coordinates, and nothing ahead of the head drops points); OrientNormals needs
+        //! keepNormals and the run's ObservationDirection before it, Shadow keepNormals, MaxDensity keepDensities and parameters
+        //! the device takes -- and that holds at least one of the four filters which otherwise run on the host.  Returns the run's
+        //! length, 0 when there is none at k.  Needs no device.
+        size_t sensorChainRunAt(size_t k) const
+        {
+            SurfaceNormalDataPointsFilter *sn = nullptr;
+            bool obs = false, orient = false, shadow = false, md = false, noise = false;
+            size_t j = k;
+            for (; j < this->size(); j++) {
+                DataPointsFilter *f = (*this)[j].get();
+                if (auto *s = dynamic_cast<SurfaceNormalDataPointsFilter *>(f)) {
+                    if (sn || s->wantsExt() || s->knn < 3 || s->knn > 32) break;
+                    sn = s;
+                } else if (dynamic_cast<ObservationDirectionDataPointsFilter *>(f)) {
+                    if (obs) break;
+                    obs = true;
+                } else if (dynamic_cast<SimpleSensorNoiseDataPointsFilter *>(f)) {
+                    if (noise) break;
+                    noise = true;
+                } else if (dynamic_cast<OrientNormalsDataPointsFilter *>(f)) {
+                    if (orient || !sn || !sn->keepNormals || !obs) break;
+                    orient = true;
+                } else if (dynamic_cast<ShadowDataPointsFilter *>(f)) {
+                    if (shadow || !sn || !sn->keepNormals) break;
+                    shadow = true;
+                } else if (auto *m = dynamic_cast<MaxDensityDataPointsFilter *>(f)) {
+                    if (md || !sn || !sn->keepDensities || !m->deviceTakesParameters()) break;
+                    md = true;
+                } else
+                    break;
+            }
+            if (!sn || !(obs || orient || shadow || noise)) return 0;
+            return j - k;
+        }
+        //! the number of filters the last apply() ran inside one pgicp_sensor_chain_* call; 0 when it ran none
+        size_t lastFusedRun() const { return lastFused; }
+        //! The run [k, k + len) as ONE device call: one upload of the cloud, one download of the kept points; the cloud ends in the
+        //! state filter-by-filter application leaves (the same labels in the same order, the same bytes).  false: nothing was done
+        //! (no device, PGSLAM_HOST_SENSOR_CHAIN=1, an empty cloud or one of fewer than 3 feature rows, a cloud that already carries a
+        //! descriptor the run writes -- setDescriptor would reuse its rows --, or arguments the device call refuses, e.g. a
+        //! coordinate that is not finite) and the caller applies the filters one by one as before; any other failure throws.
+        bool applySensorChain(size_t k, size_t len, DataPoints &c)
+        {
+            const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            if (n == 0 || frows < 3 || len > PGICP_CHAIN_MAX_STAGES + 1 || !DeviceBackedDataPointsFilter::deviceWanted("PGSLAM_HOST_SENSOR_CHAIN")) return false;
+            SurfaceNormalDataPointsFilter *sn = nullptr;
+            MaxDensityDataPointsFilter *mdf = nullptr;
+            std::vector<pgicp_chain_stage> stages;
+            for (size_t j = k; j < k + len; j++) {
+                DataPointsFilter *f = (*this)[j].get();
+                pgicp_chain_stage s;
+                std::memset(&s, 0, sizeof s);
+                if (auto *p = dynamic_cast<SurfaceNormalDataPointsFilter *>(f)) { sn = p; continue; }
+                else if (auto *p = dynamic_cast<ObservationDirectionDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_OBSERVATION_DIRECTION; for (int a = 0; a < 3; a++) s.p[a] = (double)p->c0[a]; }
+                else if (auto *p = dynamic_cast<SimpleSensorNoiseDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_SIMPLE_SENSOR_NOISE; s.p[0] = (double)p->sensorType; s.p[1] = (double)p->gain; }
+                else if (auto *p = dynamic_cast<OrientNormalsDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_ORIENT_NORMALS; s.p[0] = p->towardCenter ? 1.0 : 0.0; }
+                else if (auto *p = dynamic_cast<ShadowDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_SHADOW; s.p[0] = (double)p->epsAngle; }
+                else if (auto *p = dynamic_cast<MaxDensityDataPointsFilter *>(f)) { mdf = p; s.type = PGICP_CHAIN_MAX_DENSITY; s.p[0] = (double)p->maxDensity; s.p[1] = (double)p->seed; }
+                else return false;
+                stages.push_back(s);
+            }
+            if (!sn) return false;
+            const bool kn = sn->keepNormals, ke = sn->keepEigenValues, kd = sn->keepDensities;
+            bool obs = false, noise = false;
+            for (auto &s : stages) { obs = obs || s.type == PGICP_CHAIN_OBSERVATION_DIRECTION; noise = noise || s.type == PGICP_CHAIN_SIMPLE_SENSOR_NOISE; }
+            // the labels the run appends, in the order the filters append them one by one (SurfaceNormal: normals, densities, eigValues)
+            typename DataPoints::Labels added;
+            for (size_t j = k; j < k + len; j++) {
+                DataPointsFilter *f = (*this)[j].get();
+                if (dynamic_cast<SurfaceNormalDataPointsFilter *>(f)) {
+                    if (kn) added.push_back(typename DataPoints::Label("normals", 3));
+                    if (kd) added.push_back(typename DataPoints::Label("densities", 1));
+                    if (ke) added.push_back(typename DataPoints::Label("eigValues", 3));
+                } else if (dynamic_cast<ObservationDirectionDataPointsFilter *>(f)) added.push_back(typename DataPoints::Label("observationDirections", 3));
+                else if (dynamic_cast<SimpleSensorNoiseDataPointsFilter *>(f)) added.push_back(typename DataPoints::Label("simpleSensorNoise", 1));
+            }
+            for (auto &l : added) if (c.descriptorExists(l.text)) return false;
+            Matrix ox(frows, n), on(3, kn ? n : 0), oe(3, ke ? n : 0), od(1, kd ? n : 0), oo(3, obs ? n : 0), oz(1, noise ? n : 0), oc(drows, drows > 0 ? n : 0);
+            std::vector<int32_t> idx((size_t)n);
+            const double md = std::isfinite((double)sn->maxDist) ? (double)sn->maxDist : 1e300;
+            int kept = 0;
+            const int st = pgslam_amd::Abi<T>::sensor_chain(sn->ctx, c.features.data(), frows, n, sn->knn, md, kn, ke, kd, (int)stages.size(), stages.data(),
+                                                            drows > 0 ? c.descriptors.data() : nullptr, drows, ox.data(), kn ? on.data() : nullptr,
+                                                            ke ? oe.data() : nullptr, kd ? od.data() : nullptr, obs ? oo.data() : nullptr,
+                                                            noise ? oz.data() : nullptr, drows > 0 ? oc.data() : nullptr, idx.data(), &kept);
+            if (st == PGICP_ERR_ARG) return false;
+            check(sn->ctx, st);
+            int nd = drows;
+            for (auto &l : added) nd += (int)l.span;
+            std::vector<const Matrix *> rows;               // the call's output behind each added label
+            for (auto &l : added)
+                rows.push_back(l.text == "normals" ? &on : l.text == "densities" ? &od : l.text == "eigValues" ? &oe : l.text == "observationDirections" ? &oo : &oz);
+            Matrix f(frows, kept), d(nd, kept);
+            for (int o = 0; o < kept; o++) {
+                const int i = idx[(size_t)o];
+                for (int r = 0; r < 3; r++) f(r, o) = ox(r, o);
+                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
+                int q = 0;
+                for (int r = 0; r < drows; r++) d(q++, o) = oc(r, o);
+                for (size_t a = 0; a < added.size(); a++)
+                    for (int r = 0; r < (int)added[a].span; r++) d(q++, o) = (*rows[a])(r, o);
+            }
+            c.features = f;
+            c.descriptors = d;
+            for (auto &l : added) c.descriptorLabels.push_back(l);
+            if (mdf) mdf->onDevice = true;
+            return true;
+        }
+        //! the filters in order.  Two patterns are fused: a sensor-chain run (sensorChainRunAt) goes as one device call
+        //! (applySensorChain) when it can, and SurfaceNormalDataPointsFilter{keepDensities} directly followed by
+        //! MaxDensityDataPointsFilter runs as one device pass (MaxDensityDataPointsFilter::fusedWith); every other list as before
         void apply(DataPoints &cloud)
         {
+            lastFused = 0;
             for (size_t k = 0; k < this->size(); k++) {
+                if (const size_t run = sensorChainRunAt(k)) {
+                    if (applySensorChain(k, run, cloud)) { lastFused = run; k += run - 1; continue; }
+                }
                 if (k + 1 < this->size()) {
                     auto *sn = dynamic_cast<SurfaceNormalDataPointsFilter *>((*this)[k].get());
                     auto *md = dynamic_cast<MaxDensityDataPointsFilter *>((*this)[k + 1].get());

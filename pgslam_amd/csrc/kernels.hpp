@@ -6,6 +6,11 @@
 #define PGSLAM_ELIP_HD __host__ __device__
 #endif
 #include "pgslam_amd/elipsoids_host.hpp"
+#ifdef __HIPCC__
+#define PGSLAM_CHAIN_HD __host__ __device__
+#endif
+#include "pgicp_sensor_chain.h"
+#include "pgslam_amd/sensor_chain_host.hpp"
 
 namespace pgicp {
 
@@ -372,6 +377,42 @@ template <typename T>
 void launch_density_compact(hipStream_t st, int n, const int *keep, const int *pos, const T *xyz, int stride, const T *desc, int drows,
                             const T *nrm, const T *eig, const T *dens, T *out_xyz, T *out_desc, T *out_nrm, int out_nstride, T *out_eig,
                             T *out_dens, int *kept_idx);
+
+// include/pgicp_sensor_chain.h (k_sensor_chain.inc): the stages behind the normals kernel.  ChainSeg: the parameters of every stage
+// type (each appears at most once) and the stages of ONE segment, in list order.  ChainRows: the scratch of a call -- the rows at
+// the points' input indices (null: not made), the survivors' densities by rank, and per dropping stage (at most two) the flags, their
+// scan (n + 1 each; pos[n] = the number kept) and the survivor list.  ChainOut: where the kept points' rows go (null: not asked for)
+template <typename T>
+struct ChainSeg {
+    int n_ops, op[PGICP_CHAIN_MAX_STAGES];
+    T c[3]; int toward; T sin_eps; T max_density; unsigned long long seed;
+    pgslam_amd::sensor_chain::NoiseModel<T> noise;
+};
+template <typename T>
+struct ChainRows { T *nrm, *eig, *dens, *obs, *noise, *dens_rank; int *keep[2], *pos[2], *idx[2], *bsum; };
+template <typename T>
+struct ChainOut { T *xyz, *desc, *nrm; int nstride; T *eig, *dens, *obs, *noise; int *kept_idx; };
+template <typename T>
+ChainRows<T> chain_scratch(Carve &cv, int n, bool nrm, bool eig, bool dens, bool obs, bool noise, bool max_density, int drops)
+{
+    ChainRows<T> w{};
+    w.nrm = cv.take<T>(3 * (size_t)n, nrm);
+    w.eig = cv.take<T>(3 * (size_t)n, eig);
+    w.dens = cv.take<T>((size_t)n, dens);
+    w.obs = cv.take<T>(3 * (size_t)n, obs);
+    w.noise = cv.take<T>((size_t)n, noise);
+    w.dens_rank = cv.take<T>((size_t)n, max_density);
+    for (int k = 0; k < drops; k++) {
+        w.keep[k] = cv.take<int>((size_t)n + 1);
+        w.pos[k] = cv.take<int>((size_t)n + 1);
+        w.idx[k] = cv.take<int>((size_t)n);
+    }
+    w.bsum = cv.take<int>(scan_scratch_ints(n));
+    return w;
+}
+template <typename T>
+void launch_sensor_chain(hipStream_t st, const T *xyz, int stride, int n, const T *desc, int drows, int n_stages, const int *types,
+                         const ChainSeg<T> &params, const ChainRows<T> &w, DensStat *stat, const ChainOut<T> &out, const int **last_pos);
 
 // include/pgicp_covsample.h (k_covsample.inc): CovarianceSamplingDataPointsFilter
 constexpr int kCovBlocks = 1024;        // the most blocks of a frame reduction: one row of partials each

@@ -17,6 +17,7 @@
 #include "pgicp_quantile.h"
 #include "pgicp_ssn_ext.h"
 #include "pgicp_elipsoids.h"
+#include "pgicp_sensor_chain.h"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -56,6 +57,7 @@ using namespace pgicp;
 #include "api_quantile.inc"           // pgicp_axis_quantile_* (pgicp_quantile.h); the list entry runs in launch_filter_cloud
 #include "api_ssn_ext.inc"            // pgicp_sampling_surface_normal_ext_* (pgicp_ssn_ext.h)
 #include "api_elipsoids.inc"          // pgicp_elipsoids_* (pgicp_elipsoids.h)
+#include "api_sensor_chain.inc"       // pgicp_sensor_chain_* (pgicp_sensor_chain.h)
 
 extern "C" {
 

@@ -86,6 +86,10 @@ QUANTILE_SYMBOLS = ("pgicp_axis_quantile_f32", "pgicp_axis_quantile_f64")
 SSN_EXT_SYMBOLS = ("pgicp_sampling_surface_normal_ext_f32", "pgicp_sampling_surface_normal_ext_f64")
 # every symbol the companion header include/pgicp_elipsoids.h declares (checked by tests/test_elipsoids_host.py)
 ELIPSOIDS_SYMBOLS = ("pgicp_elipsoids_f32", "pgicp_elipsoids_f64")
+# every symbol the companion header include/pgicp_sensor_chain.h declares (checked by tests/test_sensor_chain_host.py)
+SENSOR_CHAIN_SYMBOLS = ("pgicp_sensor_chain_f32", "pgicp_sensor_chain_f64")
+CHAIN_OBSERVATION_DIRECTION, CHAIN_ORIENT_NORMALS, CHAIN_SHADOW, CHAIN_MAX_DENSITY, CHAIN_SIMPLE_SENSOR_NOISE = range(1, 6)
+CHAIN_MAX_STAGES = 8
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -118,6 +122,11 @@ class Problem(C.Structure):
 
 class Filter(C.Structure):
     _fields_ = [("type", C.c_int), ("p", C.c_double * 8)]
+
+
+class ChainStage(C.Structure):
+    """pgicp_chain_stage (include/pgicp_sensor_chain.h)"""
+    _fields_ = [("type", C.c_int), ("p", C.c_double * 4)]
 
 
 FILTER_IDENTITY, FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_REMOVE_NAN, FILTER_FIX_STEP, FILTER_RANDOM_SAMPLING, \
@@ -1103,6 +1112,68 @@ class Context:
         k = n_out.value
         return dict(xyz=ox[:k, :3], normals=on[:k], eigen_values=oe[:k], densities=od[:k],
                     descriptors=oc[:k] if oc is not None else None, kept_idx=oi[:k])
+
+    # ---- the sensor filter chain (include/pgicp_sensor_chain.h) ------------------------
+    SENSOR_CHAIN_STAGES = dict(observation_direction=(CHAIN_OBSERVATION_DIRECTION, 3), orient_normals=(CHAIN_ORIENT_NORMALS, 1),
+                               shadow=(CHAIN_SHADOW, 1), max_density=(CHAIN_MAX_DENSITY, 2), simple_sensor_noise=(CHAIN_SIMPLE_SENSOR_NOISE, 2))
+    SENSOR_CHAIN_ROWS = dict(normals=3, eigen_values=3, densities=1)
+
+    @classmethod
+    def chain_stages(cls, stages):
+        """a list of tuples such as ("shadow", 0.1), ("observation_direction", 0, 0, 0), ("max_density", 100.0, 1) as an array of
+        pgicp_chain_stage; a stage may also be given as (type number, p0, ...).  Parameters left out are 0 (max_density's seed: 1)."""
+        arr = (ChainStage * max(len(stages), 1))()
+        for k, s in enumerate(stages):
+            name, args = s[0], [float(v) for v in s[1:]]
+            if isinstance(name, str):
+                if name not in cls.SENSOR_CHAIN_STAGES:
+                    raise ValueError(f"sensor_chain: unknown stage {name!r} (known: {sorted(cls.SENSOR_CHAIN_STAGES)})")
+                typ, np_ = cls.SENSOR_CHAIN_STAGES[name]
+                if len(args) > np_:
+                    raise ValueError(f"sensor_chain: stage {name!r} takes at most {np_} parameters")
+                if name == "max_density" and len(args) == 1:
+                    args.append(1.0)
+            else:
+                typ = int(name)
+            arr[k].type = typ
+            for j, v in enumerate(args[:4]):
+                arr[k].p[j] = v
+        return arr
+
+    def sensor_chain(self, xyz, knn=10, max_dist=float("inf"), stages=(), keep=("normals", "densities"), desc=None, mem=None, dtype=None):
+        """SurfaceNormalDataPointsFilter{knn, maxDist} and a list of stages -- ObservationDirection, OrientNormals, Shadow,
+        MaxDensity, SimpleSensorNoise -- as one device call (pgicp_sensor_chain_*, statement in include/pgicp_sensor_chain.h).  numpy
+        in -> numpy out, torch CUDA in -> torch CUDA out; `mem` ("host" or "device"), when given, must name the memory xyz lies in.
+        `stages`: see chain_stages.  `keep`: the head's rows, of SENSOR_CHAIN_ROWS.  Returns dict(xyz (k,3), kept_idx (k,) int32,
+        count, descriptors (k,drows) or None, normals, eigen_values, densities, observation_directions (k,3), noise (k,)) for the k
+        kept points in input order; a row that is not kept, or whose stage is not listed, is None."""
+        unknown = set(keep) - set(self.SENSOR_CHAIN_ROWS)
+        if unknown:
+            raise ValueError(f"sensor_chain: unknown rows {sorted(unknown)} (known: {sorted(self.SENSOR_CHAIN_ROWS)})")
+        stages = list(stages)
+        arr = self.chain_stages(stages)
+        listed = {int(arr[k].type) for k in range(len(stages))}
+        s = _Staged(xyz, descriptors=desc, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
+        if mem is not None and {"host": HOST, "device": DEVICE}[mem] != x.mem:
+            raise ValueError(f"sensor_chain: mem={mem!r} but xyz lies in {'host' if x.mem == HOST else 'device'} memory")
+        md = 1e300 if not np.isfinite(max_dist) else float(max_dist)
+        m = max(n, 1)
+        ox, oi = mk((m, x.stride)), mk((m,), np.int32)
+        oc = mk((m, drows)) if d is not None else None
+        rows = {k: (mk((m, w) if w > 1 else (m,)) if k in keep else None) for k, w in self.SENSOR_CHAIN_ROWS.items()}
+        obs = mk((m, 3)) if CHAIN_OBSERVATION_DIRECTION in listed else None
+        noise = mk((m,)) if CHAIN_SIMPLE_SENSOR_NOISE in listed else None
+        n_out = C.c_int(0)
+        self._check(s.fn(self.lib, "sensor_chain")(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+            C.c_int(int("normals" in keep)), C.c_int(int("eigen_values" in keep)), C.c_int(int("densities" in keep)),
+            C.c_int(len(stages)), arr, ptr(d), C.c_int(drows), ptr(ox), ptr(rows["normals"]), C.c_int(3), ptr(rows["eigen_values"]),
+            ptr(rows["densities"]), ptr(obs), ptr(noise), ptr(oc), ptr(oi), C.byref(n_out)))
+        k = n_out.value
+        cut = lambda a: a[:k] if a is not None else None
+        return dict(xyz=ox[:k, :3], kept_idx=oi[:k], count=k, descriptors=cut(oc), observation_directions=cut(obs), noise=cut(noise),
+                    **{key: cut(a) for key, a in rows.items()})
 
     # ---- CovarianceSampling (include/pgicp_covsample.h) ------------------------
     def covariance_sampling(self, xyz, normals, nb_sample=5000, torque_norm=1, descriptors=None, dtype=None, frame=None):
