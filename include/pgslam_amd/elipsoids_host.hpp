@@ -1,6 +1,6 @@
 // elipsoids_host.hpp -- the part of ElipsoidsDataPointsFilter's statement (include/pgicp_elipsoids.h) that is new beside
 // SamplingSurfaceNormalDataPointsFilter's, in plain C++: the shape values of a box, the planarity test and the assembly of a box's rows
-// from (count, mean, scatter, ev, V, l, mid, h).  The device kernel (pgslam_amd/csrc/k_elipsoids.inc), the C++ drop-in's host form
+// from (count, mean, scatter, ev, V, l, mid, h).  The device kernel (pgslam_amd/csrc/k_ssn.inc), the C++ drop-in's host form
 // (pointmatcher.hpp) and the stand-alone test program (tests/cpp/test_elipsoids_cpu.cpp) all call these functions, so the three cannot
 // drift apart.  Everything is in T unless said; no product is fused with a sum (the translation units that include this are built
 // without contraction); divisions are correctly rounded.

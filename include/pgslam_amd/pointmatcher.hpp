@@ -513,6 +513,30 @@ struct PointMatcher {
             if (!c.descriptorExists("normals") || c.getDescriptorDimension("normals") != 3)
                 throw std::runtime_error(std::string(filter) + ": Error, cannot find normals in descriptors.");
         }
+        //! What a box filter's device call returned (SamplingSurfaceNormal, Elipsoids), made into what its host recursion leaves: the
+        //! kept columns in input order, rows 0-2 from the device (the box mean with samplingMethod 1, row 3 then 1), the other
+        //! feature rows gathered, the descriptors compacted or averaged
+        static void takeKept(DataPoints &c, const std::vector<int32_t> &idx, int kept, const Matrix &ox, const Matrix &od, int samplingMethod)
+        {
+            const int frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
+            Matrix f(frows, kept), d(drows, kept);
+            for (int o = 0; o < kept; o++) {
+                const int i = idx[o];
+                for (int r = 0; r < 3; r++) f(r, o) = ox(r, o);
+                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
+                if (samplingMethod != 0 && frows > 3) f(3, o) = T(1);
+                for (int r = 0; r < drows; r++) d(r, o) = od(r, o);
+            }
+            c.features = f;
+            if (drows > 0) c.descriptors = d;
+        }
+        //! a row that came packed from the device cut to its first `kept` columns, the kept points' (a row not asked for has none)
+        static void head(Matrix &m, int kept)
+        {
+            Matrix h(m.rows(), m.cols() > 0 ? kept : 0);
+            for (int o = 0; o < (int)h.cols(); o++) for (int r = 0; r < (int)m.rows(); r++) h(r, o) = m(r, o);
+            m = h;
+        }
     };
     //! [EXT] MaxDistDataPointsFilter{maxDist, dim} / MinDistDataPointsFilter{minDist, dim} (DataPointsFilters/MaxDist.cpp, MinDist.cpp):
     //! dim = -1: keeps points whose distance to the origin -- features.col(i).head(3).norm() in T -- is below |maxDist| (above
@@ -793,6 +817,117 @@ struct PointMatcher {
         }
         for (int i = 0; i < 3; i++) ev[i] = A[i][i];
     }
+    //! The host form of the box filters (SamplingSurfaceNormalDataPointsFilter, ElipsoidsDataPointsFilter), the statement the device
+    //! kernels restate bit for bit (pgslam_amd/csrc/k_ssn.inc): the cloud is cut at the median of its widest carried side, ordered by
+    //! (coordinate, index), until a range holds at most knn points; such a box's extent, mean and scatter are summed in T in box
+    //! order and decomposed in double; a box larger than maxBoxDim, of rank < 2 or (minPlanarity > 0) of a planarity below
+    //! minPlanarity is dropped; a fused box keeps every point with probability `ratio` (samplingMethod 0) or its first point, moved
+    //! to its mean, the existing descriptors averaged (samplingMethod 1).  rowsOf(i) says where kept point i's rows of its box go
+    //! (elipsoids_host.hpp's assemble_rows writes them; the density is pgicp_density.h's statement over the members around the
+    //! box's mean).  Returns the keep flag of every point; c's columns are not compacted yet.
+    struct BoxPointRows { pgslam_amd::elipsoids::Rows<T> rows; T *dens = nullptr; };
+    template <typename RowsOf>
+    static std::vector<char> boxFilterHost(DataPoints &c, int knn, int samplingMethod, T maxBoxDim, T minPlanarity, T ratio, unsigned long long seed,
+                                           bool averageExistingDescriptors, bool wantDensity, bool wantShape, RowsOf rowsOf)
+    {
+        namespace eh = pgslam_amd::elipsoids;
+        const int n = (int)c.features.cols(), drows = (int)c.descriptors.rows();
+        std::vector<int> idx(n);
+        for (int i = 0; i < n; i++) idx[i] = i;
+        std::vector<char> keep(n, 0);
+        struct Range { int first, last; T lo[3], hi[3]; };
+        std::vector<Range> stack;
+        Range all{0, n, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}};
+        for (int i = 0; i < n; i++)
+            for (int a = 0; a < 3; a++) { const T v = c.features(a, i); if (v < all.lo[a]) all.lo[a] = v; if (v > all.hi[a]) all.hi[a] = v; }
+        stack.push_back(all);
+        Matrix merged(drows > 0 ? drows : 1, 1);
+        while (!stack.empty()) {
+            const Range R = stack.back();
+            stack.pop_back();
+            const int count = R.last - R.first;
+            if (count > knn) {
+                int cut = 0;
+                for (int a = 1; a < 3; a++) if (R.hi[a] - R.lo[a] > R.hi[cut] - R.lo[cut]) cut = a;
+                std::sort(idx.begin() + R.first, idx.begin() + R.last, [&](int i, int j) {
+                    const T x = c.features(cut, i), y = c.features(cut, j);
+                    return x < y || (x == y && i < j);
+                });
+                const int right = count / 2, left = count - right;
+                const T cv = c.features(cut, idx[R.first + left]);
+                Range L = R, G = R;
+                L.last = R.first + left; L.hi[cut] = cv;
+                G.first = R.first + left; G.lo[cut] = cv;
+                stack.push_back(G);                  // (the left half is taken first; boxes are independent of one another)
+                stack.push_back(L);
+                continue;
+            }
+            // ---- a box
+            T lo[3], hi[3], sum[3] = {0, 0, 0};
+            for (int a = 0; a < 3; a++) { lo[a] = c.features(a, idx[R.first]); hi[a] = lo[a]; }
+            for (int k = R.first; k < R.last; k++)
+                for (int a = 0; a < 3; a++) { const T v = c.features(a, idx[k]); if (v < lo[a]) lo[a] = v; if (v > hi[a]) hi[a] = v; sum[a] += v; }
+            T box = hi[0] - lo[0];
+            if (hi[1] - lo[1] > box) box = hi[1] - lo[1];
+            if (hi[2] - lo[2] > box) box = hi[2] - lo[2];
+            if (box > maxBoxDim) continue;
+            const T mean[3] = {sum[0] / (T)count, sum[1] / (T)count, sum[2] / (T)count};
+            const T mx = mean[0], my = mean[1], mz = mean[2];
+            T c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
+            for (int k = R.first; k < R.last; k++) {
+                const int i = idx[k];
+                const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
+                c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
+            }
+            double A[3][3] = {{(double)c00, (double)c01, (double)c02}, {(double)c01, (double)c11, (double)c12}, {(double)c02, (double)c12, (double)c22}}, V[3][3], ev[3];
+            symEigen3(A, V, ev);
+            int l = 0, h = 0;
+            for (int k = 1; k < 3; k++) { if (ev[k] < ev[l]) l = k; if (ev[k] > ev[h]) h = k; }
+            const int mid = 3 - l - h;
+            if (l == h || !(ev[h] > 0.0) || !(ev[mid] > 3.0 * (double)std::numeric_limits<T>::epsilon() * ev[h])) continue;   // rank < 2
+            // include/pgicp_elipsoids.h: the shape values and the planarity drop, before the draw
+            eh::Shape<T> shape{};
+            if (minPlanarity > T(0) || wantShape) {
+                shape = eh::shape_of<T>(ev, l, mid, h);
+                if (eh::dropped_by_planarity<T>(shape, minPlanarity)) continue;
+            }
+            // include/pgicp_ssn_ext.h: the box's density
+            T boxDens = 0;
+            if (wantDensity) {
+                T r2 = 0;
+                for (int k = R.first; k < R.last; k++) {
+                    const int i = idx[k];
+                    const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
+                    const T q = (dx * dx + dy * dy) + dz * dz;
+                    if (q > r2) r2 = q;
+                }
+                const T r = std::sqrt(r2);
+                boxDens = (T)count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
+            }
+            const T scatter[6] = {c00, c01, c02, c11, c12, c22};
+            auto rowsTo = [&](int i) {
+                keep[i] = 1;
+                const BoxPointRows o = rowsOf(i);
+                eh::assemble_rows<T>(count, mean, scatter, ev, V, l, mid, h, shape, o.rows);
+                if (o.dens) *o.dens = boxDens;
+            };
+            if (samplingMethod == 0) {
+                for (int k = R.first; k < R.last; k++)
+                    if (seededDraw(seed, idx[k]) < (double)ratio) rowsTo(idx[k]);
+            } else {
+                const int i = idx[R.first];
+                rowsTo(i);
+                if (drows > 0 && averageExistingDescriptors) {
+                    for (int r = 0; r < drows; r++) merged(r, 0) = 0;
+                    for (int k = R.first; k < R.last; k++) for (int r = 0; r < drows; r++) merged(r, 0) += c.descriptors(r, idx[k]);
+                    for (int r = 0; r < drows; r++) c.descriptors(r, i) = merged(r, 0) / (T)count;
+                }
+                c.features(0, i) = mx; c.features(1, i) = my; c.features(2, i) = mz;
+                if (c.features.rows() > 3) c.features(3, i) = T(1);
+            }
+        }
+        return keep;
+    }
     //! [EXT] SamplingSurfaceNormalDataPointsFilter{ratio, knn, samplingMethod, maxBoxDim, averageExistingDescriptors, keepNormals}
     //! (DataPointsFilters/SamplingSurfaceNormal.cpp; upstream's setDefault() reference filter): the cloud is cut at the median of
     //! its widest dimension until a range holds at most knn points; each such box gets ONE normal (PCA of its points) and keeps
@@ -802,7 +937,7 @@ struct PointMatcher {
     //! cannot be: nth_element's arrangement -> a sort on (coordinate, index); rand() -> the seeded draw; EigenSolver -> Jacobi).
     //! It runs once per keyframe / map, on the reference (Localizer.hpp:314-315), and per loop-closure candidate: on the device
     //! (pgicp_sampling_surface_normal_*, the same bits) when there is one, unless PGSLAM_HOST_SAMPLING_NORMALS=1 or the device
-    //! refuses the cloud (a NaN or infinite coordinate, an out-of-range knn); then the host recursion below.
+    //! refuses the cloud (a NaN or infinite coordinate, an out-of-range knn); then the host recursion (boxFilterHost, above).
     //! keepDensities (`densities`, 1 row), keepEigenValues (`eigValues`, 3 rows, ascending) and keepEigenVectors (`eigVectors`, 9 rows:
     //! three columns in that order) append the kept point's BOX's values after `normals`, in upstream's order; they go through
     //! pgicp_sampling_surface_normal_ext_*, and the host recursion computes them by the same statement (include/pgicp_ssn_ext.h,
@@ -845,28 +980,12 @@ struct PointMatcher {
                                                            keepEigenVectors ? vec.data() : nullptr, keepDensities ? dens.data() : nullptr);
             if (st == PGICP_ERR_ARG) return false;
             check(ctx, st);
-            // what the host recursion leaves: the kept columns in input order, rows 0-2 from the device (the box mean with
-            // samplingMethod 1, row 3 then 1), the other feature rows gathered, the descriptors compacted or averaged
-            Matrix f(frows, kept), d(drows, kept), nrm(3, kept);
-            for (int o = 0; o < kept; o++) {
-                const int i = idx[o];
-                for (int r = 0; r < 3; r++) f(r, o) = ox(r, o);
-                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
-                if (samplingMethod != 0 && frows > 3) f(3, o) = T(1);
-                for (int r = 0; r < drows; r++) d(r, o) = od(r, o);
-                for (int r = 0; r < 3; r++) nrm(r, o) = on(r, o);
-            }
-            c.features = f;
-            if (drows > 0) c.descriptors = d;
-            if (keepNormals) c.setDescriptor("normals", nrm);
+            this->takeKept(c, idx, kept, ox, od, samplingMethod);
+            this->head(on, kept);
+            if (keepNormals) c.setDescriptor("normals", on);
             if (wantsExt()) {
-                // (the rows came packed: the first `kept` columns are the kept points')
-                auto head = [&](const Matrix &m, bool want) {
-                    Matrix h(m.rows(), want ? kept : 0);
-                    for (int o = 0; o < (int)h.cols(); o++) for (int r = 0; r < (int)m.rows(); r++) h(r, o) = m(r, o);
-                    return h;
-                };
-                setExtDescriptors(c, head(dens, keepDensities), head(eig, keepEigenValues), head(vec, keepEigenVectors));
+                this->head(dens, kept); this->head(eig, kept); this->head(vec, kept);
+                setExtDescriptors(c, dens, eig, vec);
             }
             return true;
         }
@@ -876,108 +995,19 @@ struct PointMatcher {
             const int n = (int)c.features.cols();
             if (n == 0) return;
             if (this->deviceWanted("PGSLAM_HOST_SAMPLING_NORMALS") && deviceFilter(c)) { onDevice = true; return; }
-            const int drows = (int)c.descriptors.rows();
-            std::vector<int> idx(n);
-            for (int i = 0; i < n; i++) idx[i] = i;
-            std::vector<char> keep(n, 0);
             Matrix nrm(3, n);
-            const bool ext = wantsExt();
             Matrix dens(1, keepDensities ? n : 0), eig(3, keepEigenValues ? n : 0), vec(9, keepEigenVectors ? n : 0);
-            struct Range { int first, last; T lo[3], hi[3]; };
-            std::vector<Range> stack;
-            Range all{0, n, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}};
-            for (int i = 0; i < n; i++)
-                for (int a = 0; a < 3; a++) { const T v = c.features(a, i); if (v < all.lo[a]) all.lo[a] = v; if (v > all.hi[a]) all.hi[a] = v; }
-            stack.push_back(all);
-            Matrix merged(drows > 0 ? drows : 1, 1);
-            while (!stack.empty()) {
-                const Range R = stack.back();
-                stack.pop_back();
-                const int count = R.last - R.first;
-                if (count > knn) {
-                    int cut = 0;
-                    for (int a = 1; a < 3; a++) if (R.hi[a] - R.lo[a] > R.hi[cut] - R.lo[cut]) cut = a;
-                    std::sort(idx.begin() + R.first, idx.begin() + R.last, [&](int i, int j) {
-                        const T x = c.features(cut, i), y = c.features(cut, j);
-                        return x < y || (x == y && i < j);
-                    });
-                    const int right = count / 2, left = count - right;
-                    const T cv = c.features(cut, idx[R.first + left]);
-                    Range L = R, G = R;
-                    L.last = R.first + left; L.hi[cut] = cv;
-                    G.first = R.first + left; G.lo[cut] = cv;
-                    stack.push_back(G);                  // (the left half is taken first; boxes are independent of one another)
-                    stack.push_back(L);
-                    continue;
-                }
-                // ---- a box
-                T lo[3], hi[3], sum[3] = {0, 0, 0};
-                for (int a = 0; a < 3; a++) { lo[a] = c.features(a, idx[R.first]); hi[a] = lo[a]; }
-                for (int k = R.first; k < R.last; k++)
-                    for (int a = 0; a < 3; a++) { const T v = c.features(a, idx[k]); if (v < lo[a]) lo[a] = v; if (v > hi[a]) hi[a] = v; sum[a] += v; }
-                T box = hi[0] - lo[0];
-                if (hi[1] - lo[1] > box) box = hi[1] - lo[1];
-                if (hi[2] - lo[2] > box) box = hi[2] - lo[2];
-                if (box > maxBoxDim) continue;
-                const T mx = sum[0] / (T)count, my = sum[1] / (T)count, mz = sum[2] / (T)count;
-                T c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-                for (int k = R.first; k < R.last; k++) {
-                    const int i = idx[k];
-                    const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
-                    c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
-                }
-                double A[3][3] = {{(double)c00, (double)c01, (double)c02}, {(double)c01, (double)c11, (double)c12}, {(double)c02, (double)c12, (double)c22}}, V[3][3], ev[3];
-                symEigen3(A, V, ev);
-                int l = 0, h = 0;
-                for (int k = 1; k < 3; k++) { if (ev[k] < ev[l]) l = k; if (ev[k] > ev[h]) h = k; }
-                const int mid = 3 - l - h;
-                if (l == h || !(ev[h] > 0.0) || !(ev[mid] > 3.0 * (double)std::numeric_limits<T>::epsilon() * ev[h])) continue;   // rank < 2
-                // include/pgicp_ssn_ext.h: the box's density (pgicp_density.h's statement over the members, around the box's mean)
-                T boxDens = 0;
-                if (keepDensities) {
-                    T r2 = 0;
-                    for (int k = R.first; k < R.last; k++) {
-                        const int i = idx[k];
-                        const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
-                        const T q = (dx * dx + dy * dy) + dz * dz;
-                        if (q > r2) r2 = q;
-                    }
-                    const T r = std::sqrt(r2);
-                    boxDens = (T)count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
-                }
-                // ... and its eigenvalues and eigenvectors, ascending (first minimum, first maximum), to a kept point
-                auto extRows = [&](int i) {
-                    const int col[3] = {l, mid, h};
-                    if (keepDensities) dens(0, i) = boxDens;
-                    for (int cc = 0; cc < 3; cc++) {
-                        if (keepEigenValues) eig(cc, i) = (T)ev[col[cc]];
-                        if (keepEigenVectors) for (int r = 0; r < 3; r++) vec(3 * cc + r, i) = (T)V[r][col[cc]];
-                    }
-                };
-                if (samplingMethod == 0) {
-                    for (int k = R.first; k < R.last; k++) {
-                        const int i = idx[k];
-                        if (!(seededDraw(seed, i) < (double)ratio)) continue;
-                        keep[i] = 1;
-                        nrm(0, i) = (T)V[0][l]; nrm(1, i) = (T)V[1][l]; nrm(2, i) = (T)V[2][l];
-                        if (ext) extRows(i);
-                    }
-                } else {
-                    const int i = idx[R.first];
-                    keep[i] = 1;
-                    nrm(0, i) = (T)V[0][l]; nrm(1, i) = (T)V[1][l]; nrm(2, i) = (T)V[2][l];
-                    if (ext) extRows(i);
-                    if (drows > 0 && averageExistingDescriptors) {
-                        for (int r = 0; r < drows; r++) merged(r, 0) = 0;
-                        for (int k = R.first; k < R.last; k++) for (int r = 0; r < drows; r++) merged(r, 0) += c.descriptors(r, idx[k]);
-                        for (int r = 0; r < drows; r++) c.descriptors(r, i) = merged(r, 0) / (T)count;
-                    }
-                    c.features(0, i) = mx; c.features(1, i) = my; c.features(2, i) = mz;
-                    if (c.features.rows() > 3) c.features(3, i) = T(1);
-                }
-            }
+            const std::vector<char> keep = boxFilterHost(c, knn, samplingMethod, maxBoxDim, T(0), ratio, seed, averageExistingDescriptors,
+                                                         keepDensities, false, [&](int i) {
+                BoxPointRows o;               // (a matrix column is contiguous)
+                o.rows.normal = &nrm(0, i);
+                if (keepEigenValues) o.rows.eig = &eig(0, i);
+                if (keepEigenVectors) o.rows.vec = &vec(0, i);
+                if (keepDensities) o.dens = &dens(0, i);
+                return o;
+            });
             if (keepNormals) c.setDescriptor("normals", nrm);
-            if (ext) setExtDescriptors(c, dens, eig, vec);
+            if (wantsExt()) setExtDescriptors(c, dens, eig, vec);
             compactColumns(c, [&](int j) { return keep[j] != 0; });
         }
     };
@@ -989,8 +1019,8 @@ struct PointMatcher {
     //! are appended in this order, each only when asked, each overwriting a descriptor of the same name: `normals` (3), `densities` (1),
     //! `eigValues` (3, ascending), `eigVectors` (9), `covariance` (9, the scatter sums, not normalised), `weights` (1, the box's count),
     //! `means` (3), `shapes` (3: planarity, cylindricality, sphericality).  3-D clouds.  On the device (pgicp_elipsoids_*, the same bits)
-    //! when there is one, unless PGSLAM_HOST_ELIPSOIDS=1 or the device refuses the arguments; then the host recursion below, which is
-    //! SamplingSurfaceNormal's with the new rows.  No deviceSpec: a chain that holds it takes the per-filter path (it changes values).
+    //! when there is one, unless PGSLAM_HOST_ELIPSOIDS=1 or the device refuses the arguments; then the host recursion (boxFilterHost,
+    //! the one SamplingSurfaceNormal runs).  No deviceSpec: a chain that holds it takes the per-filter path (it changes values).
     //! maxTimeWindow: this DataPoints carries no times, so only +inf (the default) is accepted.  From YAML keepNormals must be given.
     struct ElipsoidsDataPointsFilter : DeviceBackedDataPointsFilter {
         using DeviceBackedDataPointsFilter::ctx; using DeviceBackedDataPointsFilter::onDevice;
@@ -1043,141 +1073,32 @@ struct PointMatcher {
                                                          out(s.cov), out(s.wgt), out(s.mean), out(s.shp));
             if (st == PGICP_ERR_ARG) return false;
             check(ctx, st);
-            // what the host recursion leaves: the kept columns in input order, rows 0-2 from the device (the box mean with
-            // samplingMethod 1, row 3 then 1), the other feature rows gathered, the descriptors compacted or averaged
-            Matrix f(frows, kept), d(drows, kept);
-            for (int o = 0; o < kept; o++) {
-                const int i = idx[o];
-                for (int r = 0; r < 3; r++) f(r, o) = ox(r, o);
-                for (int r = 3; r < frows; r++) f(r, o) = c.features(r, i);
-                if (samplingMethod != 0 && frows > 3) f(3, o) = T(1);
-                for (int r = 0; r < drows; r++) d(r, o) = od(r, o);
-            }
-            c.features = f;
-            if (drows > 0) c.descriptors = d;
-            // (the rows came packed: the first `kept` columns are the kept points')
-            auto head = [&](Matrix &m) {
-                Matrix h(m.rows(), m.cols() > 0 ? kept : 0);
-                for (int o = 0; o < (int)h.cols(); o++) for (int r = 0; r < (int)m.rows(); r++) h(r, o) = m(r, o);
-                m = h;
-            };
-            head(s.nrm); head(s.dens); head(s.eig); head(s.vec); head(s.cov); head(s.wgt); head(s.mean); head(s.shp);
+            this->takeKept(c, idx, kept, ox, od, samplingMethod);
+            for (Matrix *m : {&s.nrm, &s.dens, &s.eig, &s.vec, &s.cov, &s.wgt, &s.mean, &s.shp}) this->head(*m, kept);
             setDescriptors(c, s);
             return true;
         }
         void inPlaceFilter(DataPoints &c) override
         {
-            namespace eh = pgslam_amd::elipsoids;
             onDevice = false;
             const int n = (int)c.features.cols();
             if (n == 0) return;
             this->need3D(c, "ElipsoidsDataPointsFilter");
             if (this->deviceWanted("PGSLAM_HOST_ELIPSOIDS") && deviceFilter(c)) { onDevice = true; return; }
-            const int drows = (int)c.descriptors.rows();
-            std::vector<int> idx(n);
-            for (int i = 0; i < n; i++) idx[i] = i;
-            std::vector<char> keep(n, 0);
             RowSet s(*this, n);
-            struct Range { int first, last; T lo[3], hi[3]; };
-            std::vector<Range> stack;
-            Range all{0, n, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}, {c.features(0, 0), c.features(1, 0), c.features(2, 0)}};
-            for (int i = 0; i < n; i++)
-                for (int a = 0; a < 3; a++) { const T v = c.features(a, i); if (v < all.lo[a]) all.lo[a] = v; if (v > all.hi[a]) all.hi[a] = v; }
-            stack.push_back(all);
-            Matrix merged(drows > 0 ? drows : 1, 1);
-            while (!stack.empty()) {
-                const Range R = stack.back();
-                stack.pop_back();
-                const int count = R.last - R.first;
-                if (count > knn) {
-                    int cut = 0;
-                    for (int a = 1; a < 3; a++) if (R.hi[a] - R.lo[a] > R.hi[cut] - R.lo[cut]) cut = a;
-                    std::sort(idx.begin() + R.first, idx.begin() + R.last, [&](int i, int j) {
-                        const T x = c.features(cut, i), y = c.features(cut, j);
-                        return x < y || (x == y && i < j);
-                    });
-                    const int right = count / 2, left = count - right;
-                    const T cv = c.features(cut, idx[R.first + left]);
-                    Range L = R, G = R;
-                    L.last = R.first + left; L.hi[cut] = cv;
-                    G.first = R.first + left; G.lo[cut] = cv;
-                    stack.push_back(G);                  // (the left half is taken first; boxes are independent of one another)
-                    stack.push_back(L);
-                    continue;
-                }
-                // ---- a box: SamplingSurfaceNormal's extent, mean, scatter, decomposition and rank test
-                T lo[3], hi[3], sum[3] = {0, 0, 0};
-                for (int a = 0; a < 3; a++) { lo[a] = c.features(a, idx[R.first]); hi[a] = lo[a]; }
-                for (int k = R.first; k < R.last; k++)
-                    for (int a = 0; a < 3; a++) { const T v = c.features(a, idx[k]); if (v < lo[a]) lo[a] = v; if (v > hi[a]) hi[a] = v; sum[a] += v; }
-                T box = hi[0] - lo[0];
-                if (hi[1] - lo[1] > box) box = hi[1] - lo[1];
-                if (hi[2] - lo[2] > box) box = hi[2] - lo[2];
-                if (box > maxBoxDim) continue;
-                const T mean[3] = {sum[0] / (T)count, sum[1] / (T)count, sum[2] / (T)count};
-                const T mx = mean[0], my = mean[1], mz = mean[2];
-                T c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-                for (int k = R.first; k < R.last; k++) {
-                    const int i = idx[k];
-                    const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
-                    c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
-                }
-                double A[3][3] = {{(double)c00, (double)c01, (double)c02}, {(double)c01, (double)c11, (double)c12}, {(double)c02, (double)c12, (double)c22}}, V[3][3], ev[3];
-                symEigen3(A, V, ev);
-                int l = 0, h = 0;
-                for (int k = 1; k < 3; k++) { if (ev[k] < ev[l]) l = k; if (ev[k] > ev[h]) h = k; }
-                const int mid = 3 - l - h;
-                if (l == h || !(ev[h] > 0.0) || !(ev[mid] > 3.0 * (double)std::numeric_limits<T>::epsilon() * ev[h])) continue;   // rank < 2
-                // include/pgicp_elipsoids.h: the shape values and the planarity drop, before the draw
-                const eh::Shape<T> shape = eh::shape_of<T>(ev, l, mid, h);
-                if (eh::dropped_by_planarity<T>(shape, minPlanarity)) continue;
-                // include/pgicp_ssn_ext.h: the box's density (pgicp_density.h's statement over the members, around the box's mean)
-                T boxDens = 0;
-                if (keepDensities) {
-                    T r2 = 0;
-                    for (int k = R.first; k < R.last; k++) {
-                        const int i = idx[k];
-                        const T dx = c.features(0, i) - mx, dy = c.features(1, i) - my, dz = c.features(2, i) - mz;
-                        const T q = (dx * dx + dy * dy) + dz * dz;
-                        if (q > r2) r2 = q;
-                    }
-                    const T r = std::sqrt(r2);
-                    boxDens = (T)count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
-                }
-                const T scatter[6] = {c00, c01, c02, c11, c12, c22};
-                // the box's rows to a kept point (a matrix column is contiguous)
-                auto rowsTo = [&](int i) {
-                    eh::Rows<T> o;
-                    o.normal = &s.nrm(0, i);
-                    if (keepEigenValues) o.eig = &s.eig(0, i);
-                    if (keepEigenVectors) o.vec = &s.vec(0, i);
-                    if (keepCovariances) o.cov = &s.cov(0, i);
-                    if (keepWeights) o.weight = &s.wgt(0, i);
-                    if (keepMeans) o.mean = &s.mean(0, i);
-                    if (keepShapes) o.shape = &s.shp(0, i);
-                    eh::assemble_rows<T>(count, mean, scatter, ev, V, l, mid, h, shape, o);
-                    if (keepDensities) s.dens(0, i) = boxDens;
-                };
-                if (samplingMethod == 0) {
-                    for (int k = R.first; k < R.last; k++) {
-                        const int i = idx[k];
-                        if (!(seededDraw(seed, i) < (double)ratio)) continue;
-                        keep[i] = 1;
-                        rowsTo(i);
-                    }
-                } else {
-                    const int i = idx[R.first];
-                    keep[i] = 1;
-                    rowsTo(i);
-                    if (drows > 0 && averageExistingDescriptors) {
-                        for (int r = 0; r < drows; r++) merged(r, 0) = 0;
-                        for (int k = R.first; k < R.last; k++) for (int r = 0; r < drows; r++) merged(r, 0) += c.descriptors(r, idx[k]);
-                        for (int r = 0; r < drows; r++) c.descriptors(r, i) = merged(r, 0) / (T)count;
-                    }
-                    c.features(0, i) = mx; c.features(1, i) = my; c.features(2, i) = mz;
-                    if (c.features.rows() > 3) c.features(3, i) = T(1);
-                }
-            }
+            const std::vector<char> keep = boxFilterHost(c, knn, samplingMethod, maxBoxDim, minPlanarity, ratio, seed, averageExistingDescriptors,
+                                                         keepDensities, keepShapes, [&](int i) {
+                BoxPointRows o;               // (a matrix column is contiguous)
+                o.rows.normal = &s.nrm(0, i);
+                if (keepEigenValues) o.rows.eig = &s.eig(0, i);
+                if (keepEigenVectors) o.rows.vec = &s.vec(0, i);
+                if (keepCovariances) o.rows.cov = &s.cov(0, i);
+                if (keepWeights) o.rows.weight = &s.wgt(0, i);
+                if (keepMeans) o.rows.mean = &s.mean(0, i);
+                if (keepShapes) o.rows.shape = &s.shp(0, i);
+                if (keepDensities) o.dens = &s.dens(0, i);
+                return o;
+            });
             setDescriptors(c, s);
             compactColumns(c, [&](int j) { return keep[j] != 0; });
         }

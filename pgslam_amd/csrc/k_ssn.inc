@@ -1,4 +1,7 @@
-// k_ssn.inc -- part of kernels.hip (one translation unit, included inside namespace pgicp): SamplingSurfaceNormalDataPointsFilter.
+// k_ssn.inc -- part of kernels.hip (one translation unit, included inside namespace pgicp): the box filters,
+// SamplingSurfaceNormalDataPointsFilter (pgicp_sampling_surface_normal_*, include/pgicp_ssn_ext.h) and ElipsoidsDataPointsFilter
+// (include/pgicp_elipsoids.h).  The three entries run one schedule (launch_box_filter): they differ in the per-box rows they offer and
+// in the planarity drop, which only Elipsoids has.
 //
 // [EXT] libpointmatcher SamplingSurfaceNormalDataPointsFilter as the oracle states it (oracle/icp_oracle.c,
 // orc_sampling_surface_normal): a range of more than knn points is cut at the median of its widest CARRIED side, ordered by
@@ -15,8 +18,9 @@
 //      scan over the 3n marks): every child stays sorted on every axis, as the parent's sort would have left it;
 //   3. a child of at most knn points becomes a box whose member order is its range of the parent's cut-axis list; it is
 //      left alone by the later levels, so that range still holds it at the end;
-//   4. one thread per box fuses it (the oracle's sequential sums in T, jacobi3 in double, the same rank test);
-//   5. the kept points are compacted in index order.
+//   4. one thread per box fuses it (k_box_fuse: the oracle's sequential sums in T, jacobi3 in double, the same rank test; the
+//      shape values, the planarity drop and the assembly of a box's rows are elipsoids_host.hpp's, shared with the host form);
+//   5. the kept points are compacted in index order (k_box_compact), every requested row gathered from the point's box.
 // The arithmetic contract of kernels.hip holds (no contraction); every comparison is T's.
 
 
@@ -153,20 +157,23 @@ __global__ __launch_bounds__(256) void k_ssn_part(int n, const int *__restrict__
     lst_out[flag[q] ? first + left + rb : q - rb] = lst[q];
 }
 
-// one thread per box: extent, mean and scatter sequentially in box order in T, jacobi3 in double, the rank test; the kept
-// points (method 0: each with probability ratio; method 1: the box's first) flagged with their box
-// EXT (pgicp_ssn_ext.h): the rows the kernel used to drop, per fused box -- the three eigenvalues and the three eigenvector
-// columns in ascending order (l, mid, h), and the density of the box around its mean, which takes one more walk over the
-// members (pgicp_density.h's statement: the largest squared distance by strict >, from 0).  EXT = false takes no argument for
-// it (an empty structure) and is the kernel as it was.
-struct SsnNoExt {};
-template <typename T, bool EXT = false>
-__global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int xs, int n, const int *__restrict__ lst, const SsnBox *__restrict__ boxes,
-                                                  int nbox, int method, T ratio, T max_box, unsigned long long seed, T eps,
+// one thread per box: extent, mean and scatter sequentially in box order in T, jacobi3 in double, the maxBoxDim and rank < 2
+// drops; with min_planarity > 0 the planarity drop (elipsoids_host.hpp, shared with the host form), after the rank test and before
+// the draw; then the box's rows to the per-box scratch (assemble_rows, the same header) and the kept points (method 0: each with
+// probability ratio; method 1: the box's first) flagged with their box.
+// ROWS = false is the lean case (normal and mean only, 6 stores a box): no row pointer is passed (an empty structure) and no row
+// store is compiled.  ROWS = true takes BoxRows' six pointers; a null one is a row nobody asked for and is skipped.  The density of
+// the box around its mean takes one more walk over the members (pgicp_density.h's statement: the largest squared distance by
+// strict >, from 0).  The shape values cost three divisions, so they are computed only for the planarity drop or the shape row.
+struct BoxNoRows {};
+template <typename T, bool ROWS>
+__global__ __launch_bounds__(128) void k_box_fuse(const T *__restrict__ X, int xs, int n, const int *__restrict__ lst, const SsnBox *__restrict__ boxes,
+                                                  int nbox, int method, T ratio, T max_box, T min_planarity, unsigned long long seed, T eps,
                                                   int *__restrict__ keep, int *__restrict__ box_of, T *__restrict__ bnrm, T *__restrict__ bmean,
                                                   const int *__restrict__ box_count, int *__restrict__ fused,
-                                                  typename std::conditional<EXT, SsnExtBox<T>, SsnNoExt>::type x = {})
+                                                  typename std::conditional<ROWS, BoxRows<T>, BoxNoRows>::type x = {})
 {
+    namespace eh = pgslam_amd::elipsoids;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nbox || b >= *box_count) return;
     const SsnBox B = boxes[b];
@@ -190,7 +197,8 @@ __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int x
     if (hi[1] - lo[1] > box) box = hi[1] - lo[1];
     if (hi[2] - lo[2] > box) box = hi[2] - lo[2];
     if (box > max_box) return;
-    const T mx = sum[0] / (T)B.count, my = sum[1] / (T)B.count, mz = sum[2] / (T)B.count;
+    const T mean[3] = {sum[0] / (T)B.count, sum[1] / (T)B.count, sum[2] / (T)B.count};
+    const T mx = mean[0], my = mean[1], mz = mean[2];
     T c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
     for (int k = 0; k < B.count; k++) {
         const T *p = X + (long long)member(k) * xs;
@@ -205,26 +213,39 @@ __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int x
     for (int k = 1; k < 3; k++) { if (ev[k] < ev[l]) l = k; if (ev[k] > ev[h]) h = k; }
     if (l == h) return;                                          // (mid would not name an eigenvalue)
     const int mid = 3 - l - h;
-    if (!(ev[h] > 0.0) || !(ev[mid] > 3.0 * (double)eps * ev[h])) return;      // rank < 2: the box is dropped
+    // (eigenvalues and eigenvector entries by selection, pick3: a run-time index would send the arrays to scratch memory)
+    if (!(eh::pick3(ev, h) > 0.0) || !(eh::pick3(ev, mid) > 3.0 * (double)eps * eh::pick3(ev, h))) return;      // rank < 2: the box is dropped
+    eh::Rows<T> rows;
+    rows.normal = bnrm + 3LL * b;
+    rows.mean = bmean + 3LL * b;
+    if constexpr (ROWS) {
+        if (x.beig) rows.eig = x.beig + 3LL * b;
+        if (x.bvec) rows.vec = x.bvec + 9LL * b;
+        if (x.bcov) rows.cov = x.bcov + 9LL * b;
+        if (x.bweight) rows.weight = x.bweight + b;
+        if (x.bshape) rows.shape = x.bshape + 3LL * b;
+    }
+    // a box dropped by its planarity is not fused
+    eh::Shape<T> shape{};
+    if (min_planarity > (T)0 || rows.shape) {
+        shape = eh::shape_of<T>(ev, l, mid, h);
+        if (eh::dropped_by_planarity<T>(shape, min_planarity)) return;
+    }
     atomicAdd(fused, 1);
-    bnrm[3LL * b] = (T)V[0][l]; bnrm[3LL * b + 1] = (T)V[1][l]; bnrm[3LL * b + 2] = (T)V[2][l];
-    bmean[3LL * b] = mx; bmean[3LL * b + 1] = my; bmean[3LL * b + 2] = mz;
-    if constexpr (EXT) {
-        const int col[3] = {l, mid, h};
-        T *be = x.beig + 3LL * b, *bv = x.bvec + 9LL * b;
-        for (int c = 0; c < 3; c++) {
-            be[c] = (T)ev[col[c]];
-            for (int r = 0; r < 3; r++) bv[3 * c + r] = (T)V[r][col[c]];
+    const T scatter[6] = {c00, c01, c02, c11, c12, c22};
+    eh::assemble_rows<T>(B.count, mean, scatter, ev, V, l, mid, h, shape, rows);
+    if constexpr (ROWS) {
+        if (x.bdens) {
+            T r2 = 0;
+            for (int k = 0; k < B.count; k++) {
+                const T *p = X + (long long)member(k) * xs;
+                const T dx = p[0] - mx, dy = p[1] - my, dz = p[2] - mz;
+                const T q = (dx * dx + dy * dy) + dz * dz;
+                if (q > r2) r2 = q;
+            }
+            const T r = sqrt_rn_t(r2);
+            x.bdens[b] = (T)B.count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
         }
-        T r2 = 0;
-        for (int k = 0; k < B.count; k++) {
-            const T *p = X + (long long)member(k) * xs;
-            const T dx = p[0] - mx, dy = p[1] - my, dz = p[2] - mz;
-            const T q = (dx * dx + dy * dy) + dz * dz;
-            if (q > r2) r2 = q;
-        }
-        const T r = sqrt_rn_t(r2);
-        x.bdens[b] = (T)B.count / ((T)((4.0 / 3.0) * 3.14159265358979323846) * ((r * r) * r));
     }
     if (method == 0) {
         for (int k = 0; k < B.count; k++) {
@@ -241,15 +262,15 @@ __global__ __launch_bounds__(128) void k_ssn_fuse(const T *__restrict__ X, int x
 
 // the kept points in index order: coordinates (method 1: the box mean), the box's normal, the index, the descriptors
 // (method 1 with averaging: the box's mean of each row, summed in box order in T)
-// EXT: besides, the box's eigenvalues, eigenvectors and density to each kept point (each output may be null)
-template <typename T, bool EXT = false>
-__global__ __launch_bounds__(256) void k_ssn_compact(const T *__restrict__ X, int xs, int n, const int *__restrict__ lst,
+// ROWS: besides, every requested row of the point's box (each output may be null)
+template <typename T, bool ROWS>
+__global__ __launch_bounds__(256) void k_box_compact(const T *__restrict__ X, int xs, int n, const int *__restrict__ lst,
                                                      const SsnBox *__restrict__ boxes, const int *__restrict__ keep, const int *__restrict__ pos,
                                                      const int *__restrict__ box_of, const T *__restrict__ bnrm, const T *__restrict__ bmean,
                                                      int method, const T *__restrict__ desc, int drows, int average,
                                                      T *__restrict__ out_xyz, int os, T *__restrict__ out_nrm, int ns, T *__restrict__ out_desc,
                                                      int *__restrict__ kept_idx,
-                                                     typename std::conditional<EXT, SsnExtOut<T>, SsnNoExt>::type x = {})
+                                                     typename std::conditional<ROWS, BoxOut<T>, BoxNoRows>::type x = {})
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !keep[i]) return;
@@ -260,10 +281,14 @@ __global__ __launch_bounds__(256) void k_ssn_compact(const T *__restrict__ X, in
     else { const T *p = X + (long long)i * xs; ox[0] = p[0]; ox[1] = p[1]; ox[2] = p[2]; }
     if (out_nrm) { T *on = out_nrm + o * ns; on[0] = bnrm[3LL * b]; on[1] = bnrm[3LL * b + 1]; on[2] = bnrm[3LL * b + 2]; }
     if (kept_idx) kept_idx[o] = i;
-    if constexpr (EXT) {
+    if constexpr (ROWS) {
         if (x.eig) for (int r = 0; r < 3; r++) x.eig[3 * o + r] = x.box.beig[3LL * b + r];
         if (x.eigvec) for (int r = 0; r < 9; r++) x.eigvec[9 * o + r] = x.box.bvec[9LL * b + r];
         if (x.dens) x.dens[o] = x.box.bdens[b];
+        if (x.cov) for (int r = 0; r < 9; r++) x.cov[9 * o + r] = x.box.bcov[9LL * b + r];
+        if (x.weights) x.weights[o] = x.box.bweight[b];
+        if (x.means) for (int r = 0; r < 3; r++) x.means[3 * o + r] = bmean[3LL * b + r];
+        if (x.shapes) for (int r = 0; r < 3; r++) x.shapes[3 * o + r] = x.box.bshape[3LL * b + r];
     }
     if (desc) {
         T *od = out_desc + o * drows;
@@ -302,7 +327,6 @@ __global__ void k_ssn_root_box(int n, SsnBox *__restrict__ boxes, int *__restric
 
 // Steps 1.-3. of one call: the counters and the keep flags cleared, the three lists sorted, the tree cut level by level, the box
 // list made.  Returns the lists the boxes' member ranges index (w.lst[0] or w.lst[1]); `nbox` gets the number of boxes the tree has.
-// (Shared by the SamplingSurfaceNormal launcher below and by k_elipsoids.inc: the same launches in the same order.)
 template <typename T>
 static const int *ssn_build_tree(hipStream_t st, const T *X, int xs, int n, int knn, const SsnScratch &w, int *counters, long long &nbox)
 {
@@ -354,69 +378,42 @@ static const int *ssn_build_tree(hipStream_t st, const T *X, int xs, int n, int 
     return lst;
 }
 
-// Scratch of one call (device): see pgicp_sampling_surface_normal_*.  Returns 0, or -1 when n / knn are out of range.
-// EXT (pgicp_ssn_ext.h): the same schedule with the EXT instantiations of the last two kernels; x names the per-box scratch and
-// the three outputs.  EXT = false launches what launch_sampling_normals always launched (those two launches keep their text and
-// their indentation).
-template <typename T, bool EXT>
-static int ssn_launch(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                      const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                      T *out_desc, int *kept_idx, int *counters /* [0] box slots, [1] boxes fused, [2] not finite, [3] kept */,
-                      typename std::conditional<EXT, SsnExtOut<T>, SsnNoExt>::type x = {})
+// The schedule of one call of any of the three entries: the tree, then the two kernels above.  x.box names the per-box scratch
+// (box_scratch), the other members of x the outputs; with none of them asked for the lean instantiations run.  min_planarity 0 is
+// no planarity drop (the SamplingSurfaceNormal entries).  Returns 0, or -1 when n / knn are out of range.
+template <typename T>
+int launch_box_filter(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, T min_planarity, unsigned long long seed,
+                      const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns, T *out_desc,
+                      int *kept_idx, int *counters /* [0] box slots, [1] boxes fused, [2] not finite, [3] kept */, const BoxOut<T> &x)
 {
     if (n <= 0 || knn < 1 || (long long)n * 3 + 1 > 0x7FFFFFFFLL) return -1;
     long long nbox = 0;
     const int *lst = ssn_build_tree<T>(st, X, xs, n, knn, w, counters, nbox);
-    const dim3 b256(256);
-    auto scan = [&](const int *in, int len, int *out) { launch_exclusive_scan(st, in, len, out, w.bsum); };
     const SsnBox *boxes = (const SsnBox *)w.boxes;
+    const dim3 b256(256), b128(128);
+    const T eps = std::numeric_limits<T>::epsilon();
     // 4. the boxes
-    if constexpr (EXT) {
-        hipLaunchKernelGGL((k_ssn_fuse<T, true>), dim3(cdiv(nbox, 128)), dim3(128), 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (int)nbox, method,
-                           ratio, max_box, seed, std::numeric_limits<T>::epsilon(), w.keep, w.box_of, (T *)w.bnrm, (T *)w.bmean, (const int *)counters, counters + 1, x.box);
-    } else {
-    hipLaunchKernelGGL(k_ssn_fuse<T>, dim3(cdiv(nbox, 128)), dim3(128), 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (int)nbox, method,
-                       ratio, max_box, seed, std::numeric_limits<T>::epsilon(), w.keep, w.box_of, (T *)w.bnrm, (T *)w.bmean, (const int *)counters, counters + 1);
-    }
+    if (x.any())
+        hipLaunchKernelGGL((k_box_fuse<T, true>), dim3(cdiv(nbox, 128)), b128, 0, st, X, xs, n, lst, boxes, (int)nbox, method, ratio, max_box,
+                           min_planarity, seed, eps, w.keep, w.box_of, (T *)w.bnrm, (T *)w.bmean, (const int *)counters, counters + 1, x.box);
+    else
+        hipLaunchKernelGGL((k_box_fuse<T, false>), dim3(cdiv(nbox, 128)), b128, 0, st, X, xs, n, lst, boxes, (int)nbox, method, ratio, max_box,
+                           min_planarity, seed, eps, w.keep, w.box_of, (T *)w.bnrm, (T *)w.bmean, (const int *)counters, counters + 1);
     // 5. the kept points in index order
-    scan(w.keep, n, w.pos);
-    if constexpr (EXT) {
-        hipLaunchKernelGGL((k_ssn_compact<T, true>), dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (const int *)w.keep,
-                           (const int *)w.pos, (const int *)w.box_of, (const T *)w.bnrm, (const T *)w.bmean, method, desc, drows, average, out_xyz, os,
-                           out_nrm, ns, out_desc, kept_idx, x);
-    } else {
-    hipLaunchKernelGGL(k_ssn_compact<T>, dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, (const int *)lst, (const SsnBox *)boxes, (const int *)w.keep,
-                       (const int *)w.pos, (const int *)w.box_of, (const T *)w.bnrm, (const T *)w.bmean, method, desc, drows, average, out_xyz, os,
-                       out_nrm, ns, out_desc, kept_idx);
-    }
+    launch_exclusive_scan(st, w.keep, n, w.pos, w.bsum);
+    if (x.any())
+        hipLaunchKernelGGL((k_box_compact<T, true>), dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, lst, boxes, (const int *)w.keep, (const int *)w.pos,
+                           (const int *)w.box_of, (const T *)w.bnrm, (const T *)w.bmean, method, desc, drows, average, out_xyz, os, out_nrm, ns,
+                           out_desc, kept_idx, x);
+    else
+        hipLaunchKernelGGL((k_box_compact<T, false>), dim3(cdiv(n, 256)), b256, 0, st, X, xs, n, lst, boxes, (const int *)w.keep, (const int *)w.pos,
+                           (const int *)w.box_of, (const T *)w.bnrm, (const T *)w.bmean, method, desc, drows, average, out_xyz, os, out_nrm, ns,
+                           out_desc, kept_idx);
     (void)hipMemcpyAsync(counters + 3, w.pos + n, sizeof(int), hipMemcpyDeviceToDevice, st);
     return 0;
 }
 
-template <typename T>
-int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                            const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                            T *out_desc, int *kept_idx, int *counters)
-{
-    return ssn_launch<T, false>(st, X, xs, n, knn, method, ratio, max_box, seed, desc, drows, average, w, out_xyz, os, out_nrm, ns, out_desc, kept_idx,
-                                counters);
-}
-
-// pgicp_ssn_ext.h: x.box is the per-box scratch (ssn_ext_scratch), x.eig / x.eigvec / x.dens the outputs, each may be null
-template <typename T>
-int launch_sampling_normals_ext(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                                const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                                T *out_desc, int *kept_idx, int *counters, const SsnExtOut<T> &x)
-{
-    return ssn_launch<T, true>(st, X, xs, n, knn, method, ratio, max_box, seed, desc, drows, average, w, out_xyz, os, out_nrm, ns, out_desc, kept_idx,
-                               counters, x);
-}
-
-template int launch_sampling_normals<float>(hipStream_t, const float *, int, int, int, int, float, float, unsigned long long, const float *, int, int,
-                                            const SsnScratch &, float *, int, float *, int, float *, int *, int *);
-template int launch_sampling_normals<double>(hipStream_t, const double *, int, int, int, int, double, double, unsigned long long, const double *, int,
-                                             int, const SsnScratch &, double *, int, double *, int, double *, int *, int *);
-template int launch_sampling_normals_ext<float>(hipStream_t, const float *, int, int, int, int, float, float, unsigned long long, const float *, int, int,
-                                                const SsnScratch &, float *, int, float *, int, float *, int *, int *, const SsnExtOut<float> &);
-template int launch_sampling_normals_ext<double>(hipStream_t, const double *, int, int, int, int, double, double, unsigned long long, const double *, int,
-                                                 int, const SsnScratch &, double *, int, double *, int, double *, int *, int *, const SsnExtOut<double> &);
+template int launch_box_filter<float>(hipStream_t, const float *, int, int, int, int, float, float, float, unsigned long long, const float *, int, int,
+                                      const SsnScratch &, float *, int, float *, int, float *, int *, int *, const BoxOut<float> &);
+template int launch_box_filter<double>(hipStream_t, const double *, int, int, int, int, double, double, double, unsigned long long, const double *, int,
+                                       int, const SsnScratch &, double *, int, double *, int, double *, int *, int *, const BoxOut<double> &);

@@ -200,7 +200,6 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_axisquantile.inc"
 #include "k_launch.inc"
 #include "k_ssn.inc"
-#include "k_elipsoids.inc"
 #include "k_vartrim.inc"
 #include "k_pairsort.inc"
 #include "k_voxel.inc"

@@ -189,60 +189,43 @@ SsnScratch ssn_scratch(Carve &cv, int n)
     w.pos = cv.take<int>(n1);
     return w;
 }
+// The per-box rows beside SsnScratch's bnrm / bmean that the three entries of the box filters offer (pgicp_sampling_surface_normal_*
+// none, include/pgicp_ssn_ext.h the first three, include/pgicp_elipsoids.h all), as a set of bits.  (kBoxMean is an output only: it
+// is gathered from bmean and has no scratch of its own.)
+enum : unsigned { kBoxEig = 1, kBoxVec = 2, kBoxDens = 4, kBoxCov = 8, kBoxWeight = 16, kBoxShape = 32, kBoxMean = 64, kBoxRowsExt = 7, kBoxRowsAll = 127 };
+// BoxRows: what k_box_fuse<T, true> writes per box slot -- 3, 9, 1, 9, 1 and 3 values; a null pointer is a row nobody asked for, and
+// is not written.  BoxOut: what k_box_compact<T, true> copies to each kept point (every output may be null; `means` is gathered
+// from bmean).
 template <typename T>
-int launch_sampling_normals(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                            const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                            T *out_desc, int *kept_idx, int *counters);
-// include/pgicp_ssn_ext.h: what k_ssn_fuse<T, true> writes per box (3, 9 and 1 values a box slot, carved after the call's
-// SsnScratch from the same buffer) and what k_ssn_compact<T, true> copies to each kept point (every output may be null)
+struct BoxRows { T *beig, *bvec, *bdens, *bcov, *bweight, *bshape; };
 template <typename T>
-struct SsnExtBox { T *beig, *bvec, *bdens; };
-template <typename T>
-struct SsnExtOut { T *eig, *eigvec, *dens; SsnExtBox<T> box; };
-template <typename T>
-SsnExtBox<T> ssn_ext_scratch(Carve &cv, int n)
-{
-    const size_t n1 = (size_t)n + 1;
-    SsnExtBox<T> b;
-    b.beig = cv.take<T>(3 * n1);
-    b.bvec = cv.take<T>(9 * n1);
-    b.bdens = cv.take<T>(n1);
-    return b;
-}
-template <typename T>
-int launch_sampling_normals_ext(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, unsigned long long seed,
-                                const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns,
-                                T *out_desc, int *kept_idx, int *counters, const SsnExtOut<T> &x);
-
-// include/pgicp_elipsoids.h (k_elipsoids.inc): the tree, SsnScratch and the counters are SamplingSurfaceNormal's.  ElipBox: what
-// k_elip_fuse<T, true> writes per box slot besides SsnScratch's bnrm / bmean -- 3, 9, 1, 9, 1 and 3 values; a null pointer is a row
-// nobody asked for, and is not written.  ElipOut: what k_elip_compact<T, true> copies to each kept point (every output may be null;
-// `means` is gathered from bmean).  The scratch's size does not depend on what is asked for.
-template <typename T>
-struct ElipBox { T *beig, *bvec, *bdens, *bcov, *bweight, *bshape; };
-template <typename T>
-struct ElipOut {
+struct BoxOut {
     T *eig, *eigvec, *dens, *cov, *weights, *means, *shapes;
-    ElipBox<T> box;
+    BoxRows<T> box;
     bool any() const { return eig || eigvec || dens || cov || weights || means || shapes; }
 };
+// carved after the call's SsnScratch from the same buffer: room for every row the entry offers, whether asked for or not, so the
+// buffer's size depends on the entry and n alone; a pointer only for a row that is asked for
 template <typename T>
-ElipBox<T> elip_scratch(Carve &cv, int n, const ElipOut<T> &want)
+BoxRows<T> box_scratch(Carve &cv, int n, unsigned offered, const BoxOut<T> &want)
 {
     const size_t n1 = (size_t)n + 1;
-    ElipBox<T> b;
-    b.beig = cv.take<T>(3 * n1, want.eig != nullptr);
-    b.bvec = cv.take<T>(9 * n1, want.eigvec != nullptr);
-    b.bdens = cv.take<T>(n1, want.dens != nullptr);
-    b.bcov = cv.take<T>(9 * n1, want.cov != nullptr);
-    b.bweight = cv.take<T>(n1, want.weights != nullptr);
-    b.bshape = cv.take<T>(3 * n1, want.shapes != nullptr);
+    auto row = [&](unsigned bit, size_t width, const T *asked) { return offered & bit ? cv.take<T>(width * n1, asked != nullptr) : nullptr; };
+    BoxRows<T> b;
+    b.beig = row(kBoxEig, 3, want.eig);
+    b.bvec = row(kBoxVec, 9, want.eigvec);
+    b.bdens = row(kBoxDens, 1, want.dens);
+    b.bcov = row(kBoxCov, 9, want.cov);
+    b.bweight = row(kBoxWeight, 1, want.weights);
+    b.bshape = row(kBoxShape, 3, want.shapes);
     return b;
 }
+// The one schedule of the three entries (k_ssn.inc): the tree, then the boxes fused and the kept points compacted.  With no row
+// asked for in x the lean instantiations run.  min_planarity 0: no planarity drop (the SamplingSurfaceNormal entries).
 template <typename T>
-int launch_elipsoids(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, T min_planarity, unsigned long long seed,
-                     const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns, T *out_desc,
-                     int *kept_idx, int *counters, const ElipOut<T> &x);
+int launch_box_filter(hipStream_t st, const T *X, int xs, int n, int knn, int method, T ratio, T max_box, T min_planarity, unsigned long long seed,
+                      const T *desc, int drows, int average, const SsnScratch &w, T *out_xyz, int os, T *out_nrm, int ns, T *out_desc,
+                      int *kept_idx, int *counters, const BoxOut<T> &x);
 
 // The stable LSD radix sort of (64-bit key, index) pairs (k_pairsort.inc), 8 bits a pass, that VoxelGrid, OctreeGrid and NormalSpace
 // share: the two ping-pong buffers, the [digit][tile] counts and their scan, and the scan's block sums.  `other_scan`: the longest

@@ -47,7 +47,6 @@ using namespace pgicp;
 #include "api_icp.inc"                // BatchLayout, batch_begin, one iteration, align_batch, icp_pair
 #include "api_stages.inc"             // match, partial chain, outlier weights, error statistics, transform, local maps, normals
 #include "api_filters_uploads.inc"    // pgicp_filter_cloud*, batched map ABI, last-call diagnostics, map transfer, pgicp_upload_*
-#include "api_sampling.inc"           // pgicp_sampling_surface_normal_* (SamplingSurfaceNormalDataPointsFilter)
 #include "api_voxel.inc"              // pgicp_voxel_grid_* (VoxelGridDataPointsFilter)
 #include "api_density.inc"            // pgicp_surface_densities_*, pgicp_max_density_*, pgicp_normals_max_density_* (pgicp_density.h)
 #include "api_covsample.inc"          // pgicp_covariance_sampling_*, pgicp_covariance_sampling_framed_* (pgicp_covsample.h)
@@ -55,8 +54,7 @@ using namespace pgicp;
 #include "api_normalspace.inc"        // pgicp_normal_space_sampling_* (pgicp_normalspace.h)
 #include "api_normals_ext.inc"        // pgicp_surface_normals_ext_*, pgicp_smooth_normals_* (pgicp_normals_ext.h)
 #include "api_quantile.inc"           // pgicp_axis_quantile_* (pgicp_quantile.h); the list entry runs in launch_filter_cloud
-#include "api_ssn_ext.inc"            // pgicp_sampling_surface_normal_ext_* (pgicp_ssn_ext.h)
-#include "api_elipsoids.inc"          // pgicp_elipsoids_* (pgicp_elipsoids.h)
+#include "api_box.inc"                // pgicp_sampling_surface_normal_*, pgicp_sampling_surface_normal_ext_* (pgicp_ssn_ext.h), pgicp_elipsoids_* (pgicp_elipsoids.h)
 #include "api_sensor_chain.inc"       // pgicp_sensor_chain_* (pgicp_sensor_chain.h)
 
 extern "C" {
@@ -525,16 +523,6 @@ int pgicp_surface_normals_f32(pgicp_ctx *c, const float *xyz, int stride, int n,
 int pgicp_surface_normals_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int mem, int knn, double max_dist,
                               double *out_nrm, int out_stride, double *out_eig, int32_t *out_ids, double *out_d2)
 { return surface_normals<double>(c, xyz, stride, n, mem, knn, max_dist, out_nrm, out_stride, out_eig, out_ids, out_d2); }
-int pgicp_sampling_surface_normal_f32(pgicp_ctx *c, const float *xyz, int stride, int n, int mem, int knn, double ratio, int sampling_method,
-                                      double max_box_dim, uint64_t seed, const float *desc, int drows, int average_descriptors, float *out_xyz,
-                                      int out_stride, float *out_nrm, int nrm_stride, float *out_desc, int32_t *kept_idx, int *n_out, int *n_boxes)
-{ return sampling_surface_normal<float>(c, xyz, stride, n, mem, knn, ratio, sampling_method, max_box_dim, seed, desc, drows, average_descriptors, out_xyz,
-                                        out_stride, out_nrm, nrm_stride, out_desc, kept_idx, n_out, n_boxes); }
-int pgicp_sampling_surface_normal_f64(pgicp_ctx *c, const double *xyz, int stride, int n, int mem, int knn, double ratio, int sampling_method,
-                                      double max_box_dim, uint64_t seed, const double *desc, int drows, int average_descriptors, double *out_xyz,
-                                      int out_stride, double *out_nrm, int nrm_stride, double *out_desc, int32_t *kept_idx, int *n_out, int *n_boxes)
-{ return sampling_surface_normal<double>(c, xyz, stride, n, mem, knn, ratio, sampling_method, max_box_dim, seed, desc, drows, average_descriptors, out_xyz,
-                                         out_stride, out_nrm, nrm_stride, out_desc, kept_idx, n_out, n_boxes); }
 int pgicp_voxel_grid_f32(pgicp_ctx *c, const float *xyz, int stride, int n, int mem, const double v_size[3], int use_centroid, const float *desc,
                          int drows, int average_descriptors, float *out_xyz, int out_stride, float *out_desc, int32_t *kept_idx, int32_t *out_count,
                          int *n_out)

@@ -961,25 +961,43 @@ class Context:
             out += [ids, d2]
         return out[0] if len(out) == 1 else tuple(out)
 
+    ELIPSOIDS_ROWS = dict(normals=3, densities=1, eigen_values=3, eigen_vectors=9, covariance=9, weights=1, means=3, shapes=3)
+    # the box filters' three entries: what each takes after n_boxes, in its order
+    _BOX_ENTRIES = {"sampling_surface_normal": (),
+                    "sampling_surface_normal_ext": ("eigen_values", "eigen_vectors", "densities"),
+                    "elipsoids": ("eigen_values", "eigen_vectors", "densities", "min_planarity", "covariance", "weights", "means", "shapes")}
+
+    def _box_filter(self, entry, xyz, knn, ratio, method, max_box, seed, desc, average, keep, dtype, min_planarity=0.0, mem=None):
+        """One call of an entry of _BOX_ENTRIES: the staging, the outputs (of ELIPSOIDS_ROWS those in `keep`), the call.  Returns
+        dict(xyz, kept_idx, descriptors, boxes, and every row of ELIPSOIDS_ROWS), cut to the kept points; what was not asked for is None."""
+        s = _Staged(xyz, descriptors=desc, dtype=dtype)
+        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
+        if mem is not None and {"host": HOST, "device": DEVICE}[mem] != x.mem:
+            raise ValueError(f"{entry}: mem={mem!r} but xyz lies in {'host' if x.mem == HOST else 'device'} memory")
+        m = max(n, 1)
+        ox, oi = mk((m, 3)), mk((m,), np.int32)
+        od = mk((m, drows)) if d is not None else None
+        rows = {k: (mk((m, w) if w > 1 else (m,)) if k in keep else None) for k, w in self.ELIPSOIDS_ROWS.items()}
+        n_out, boxes = C.c_int(0), C.c_int(0)
+        tail = [C.c_double(min_planarity) if a == "min_planarity" else ptr(rows[a]) for a in self._BOX_ENTRIES[entry]]
+        self._check(s.fn(self.lib, entry)(
+            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
+            C.c_int(method), C.c_double(max_box), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
+            C.c_int(int(bool(average))), ptr(ox), C.c_int(3), ptr(rows["normals"]), C.c_int(3), ptr(od), ptr(oi),
+            C.byref(n_out), C.byref(boxes), *tail))
+        k = n_out.value
+        cut = lambda a: a[:k] if a is not None else None
+        return dict(xyz=ox[:k], kept_idx=oi[:k], descriptors=cut(od), boxes=boxes.value, **{key: cut(a) for key, a in rows.items()})
+
     def sampling_surface_normal(self, xyz, knn=7, ratio=0.5, sampling_method=0, max_box_dim=float("inf"), seed=1, descriptors=None,
                                 average_descriptors=True, dtype=None):
         """SamplingSurfaceNormalDataPointsFilter on the device (pgicp_sampling_surface_normal_*).  numpy in -> numpy out, torch
         CUDA in -> torch CUDA out.  `descriptors`: (n, drows) or None, in the same memory as xyz.  Returns dict(xyz (k,3),
         normals (k,3), kept_idx (k,) int32, descriptors (k,drows) or None, boxes: boxes fused) for the k kept points, in
         ascending input index."""
-        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
-        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
-        m = max(n, 1)
-        ox, on, oi = mk((m, 3)), mk((m, 3)), mk((m,), np.int32)
-        od = mk((m, drows)) if d is not None else None
-        n_out, boxes = C.c_int(0), C.c_int(0)
-        self._check(s.fn(self.lib, "sampling_surface_normal")(
-            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
-            C.c_int(sampling_method), C.c_double(max_box_dim), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
-            C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(on), C.c_int(3), ptr(od), ptr(oi),
-            C.byref(n_out), C.byref(boxes)))
-        k = n_out.value
-        return dict(xyz=ox[:k], normals=on[:k], kept_idx=oi[:k], descriptors=od[:k] if od is not None else None, boxes=boxes.value)
+        r = self._box_filter("sampling_surface_normal", xyz, knn, ratio, sampling_method, max_box_dim, seed, descriptors, average_descriptors,
+                             ("normals",), dtype)
+        return {key: r[key] for key in ("xyz", "normals", "kept_idx", "descriptors", "boxes")}
 
     def sampling_surface_normal_ext(self, xyz, knn=7, ratio=0.5, sampling_method=0, max_box_dim=float("inf"), seed=1, descriptors=None,
                                     average_descriptors=True, want_eigen=False, want_eigen_vectors=False, want_densities=False,
@@ -988,27 +1006,10 @@ class Context:
         include/pgicp_ssn_ext.h).  numpy in -> numpy out, torch CUDA in -> torch CUDA out.  Returns sampling_surface_normal's dict
         and eigen_values (k,3) ascending, eigen_vectors (k,9): three columns in that order, densities (k,) -- the kept point's
         box's; what was not asked for is None."""
-        s = _Staged(xyz, descriptors=descriptors, dtype=dtype)
-        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
-        m = max(n, 1)
-        ox, oi = mk((m, 3)), mk((m,), np.int32)
-        on = mk((m, 3)) if want_normals else None
-        od = mk((m, drows)) if d is not None else None
-        eig = mk((m, 3)) if want_eigen else None
-        vec = mk((m, 9)) if want_eigen_vectors else None
-        dens = mk((m,)) if want_densities else None
-        n_out, boxes = C.c_int(0), C.c_int(0)
-        self._check(s.fn(self.lib, "sampling_surface_normal_ext")(
-            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
-            C.c_int(sampling_method), C.c_double(max_box_dim), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
-            C.c_int(int(bool(average_descriptors))), ptr(ox), C.c_int(3), ptr(on), C.c_int(3), ptr(od), ptr(oi),
-            C.byref(n_out), C.byref(boxes), ptr(eig), ptr(vec), ptr(dens)))
-        k = n_out.value
-        cut = lambda a: a[:k] if a is not None else None
-        return dict(xyz=ox[:k], normals=cut(on), kept_idx=oi[:k], descriptors=cut(od), boxes=boxes.value,
-                    eigen_values=cut(eig), eigen_vectors=cut(vec), densities=cut(dens))
-
-    ELIPSOIDS_ROWS = dict(normals=3, densities=1, eigen_values=3, eigen_vectors=9, covariance=9, weights=1, means=3, shapes=3)
+        want = dict(normals=want_normals, eigen_values=want_eigen, eigen_vectors=want_eigen_vectors, densities=want_densities)
+        r = self._box_filter("sampling_surface_normal_ext", xyz, knn, ratio, sampling_method, max_box_dim, seed, descriptors, average_descriptors,
+                             tuple(k for k, w in want.items() if w), dtype)
+        return {key: r[key] for key in ("xyz", "normals", "kept_idx", "descriptors", "boxes", "eigen_values", "eigen_vectors", "densities")}
 
     def elipsoids(self, xyz, knn=7, ratio=0.5, method=0, max_box=float("inf"), min_planarity=0.0, seed=1, desc=None, average=True,
                   keep=("normals",), mem=None, dtype=None):
@@ -1019,24 +1020,7 @@ class Context:
         unknown = set(keep) - set(self.ELIPSOIDS_ROWS)
         if unknown:
             raise ValueError(f"elipsoids: unknown rows {sorted(unknown)} (known: {sorted(self.ELIPSOIDS_ROWS)})")
-        s = _Staged(xyz, descriptors=desc, dtype=dtype)
-        x, n, d, drows, mk, ptr = s.x, s.n, s.d, s.drows, s.mk, s.ptr
-        if mem is not None and {"host": HOST, "device": DEVICE}[mem] != x.mem:
-            raise ValueError(f"elipsoids: mem={mem!r} but xyz lies in {'host' if x.mem == HOST else 'device'} memory")
-        m = max(n, 1)
-        ox, oi = mk((m, 3)), mk((m,), np.int32)
-        od = mk((m, drows)) if d is not None else None
-        rows = {k: (mk((m, w) if w > 1 else (m,)) if k in keep else None) for k, w in self.ELIPSOIDS_ROWS.items()}
-        n_out, boxes = C.c_int(0), C.c_int(0)
-        self._check(s.fn(self.lib, "elipsoids")(
-            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(ratio),
-            C.c_int(method), C.c_double(max_box), C.c_uint64(int(seed)), ptr(d), C.c_int(drows),
-            C.c_int(int(bool(average))), ptr(ox), C.c_int(3), ptr(rows["normals"]), C.c_int(3), ptr(od), ptr(oi),
-            C.byref(n_out), C.byref(boxes), ptr(rows["eigen_values"]), ptr(rows["eigen_vectors"]), ptr(rows["densities"]),
-            C.c_double(min_planarity), ptr(rows["covariance"]), ptr(rows["weights"]), ptr(rows["means"]), ptr(rows["shapes"])))
-        k = n_out.value
-        cut = lambda a: a[:k] if a is not None else None
-        return dict(xyz=ox[:k], kept_idx=oi[:k], descriptors=cut(od), boxes=boxes.value, **{key: cut(a) for key, a in rows.items()})
+        return self._box_filter("elipsoids", xyz, knn, ratio, method, max_box, seed, desc, average, keep, dtype, min_planarity, mem)
 
     def voxel_grid(self, xyz, v_size=(1.0, 1.0, 1.0), use_centroid=True, descriptors=None, average_descriptors=True, dtype=None):
         """VoxelGridDataPointsFilter on the device (pgicp_voxel_grid_*, statement in include/pgicp.h).  numpy in -> numpy out, torch

@@ -55,9 +55,9 @@ for name, xyz in clouds.items():
     for key in ("xyz", "normals", "kept_idx"):
         sha.update(r[key].cpu().numpy().tobytes())
     kept, boxes = len(r["kept_idx"]), r["boxes"]
-    # bytes the two kernels must move at the least with every row, from shapes: k_ssn_fuse<T, true> reads the members' indices and
+    # bytes the two kernels must move at the least with every row, from shapes: k_box_fuse<T, true> reads the members' indices and
     # coordinates three times (extent and sum, scatter, density) and writes per fused box the normal 3, the mean 3, the eigenvalues 3,
-    # the eigenvectors 9 and the density 1, and per kept point its flag and box; k_ssn_compact<T, true> reads per point the flag and
+    # the eigenvectors 9 and the density 1, and per kept point its flag and box; k_box_compact<T, true> reads per point the flag and
     # the position, per kept point the box, the coordinates 3 and the box's 3 + 13 values, and writes 3 + 3 + 13 values and the index
     res = dict(points=n, kept=kept, boxes=boxes,
                bytes=dict(fuse_all_rows=3 * n * (4 + 3 * s) + boxes * 19 * s + kept * 8,
