@@ -418,7 +418,15 @@ int pgicp_partial_chain_f64(pgicp_ctx *ctx, int map_id, const double *reading, i
  * threshold its previous probe ended with (PGICP_PROBE_CAP_SCALE), as an ICP's later iterations are by their previous one's (a query with nothing inside
  * the cap is resolved lazily, only if the new threshold turns out to need it: a cap that is wrong costs time, never a result --
  * same test).  A reading the source context did not align (another size), a chain with
- * knn > 1, the brute matcher or a SurfaceNormalOutlierFilter: searched unseeded, as pgicp_partial_chain. */
+ * knn > 1, the brute matcher or a SurfaceNormalOutlierFilter: searched unseeded, as pgicp_partial_chain.  So is a source
+ * whose state is no longer what its align call left (pgslam_amd/csrc/seed_source.hpp decides, tests/test_gpu_seeded_sources.py):
+ *   - the map it aligned against has been destroyed or transferred away since -- also when another map, created or adopted
+ *     later, has taken the same id (every map carries a stamp of its context; ids are reused, stamps are not); other maps of
+ *     the source may come and go;
+ *   - the source aligned with knn > 1, or as the other cloud type (f32 / f64), or is this context itself, or has made any
+ *     other ICP / matcher / partial-chain call since;
+ *   - n_seg outside 1 ... 16.
+ * A seed that does not name a point of the source's map is dropped on the device; src_start / dst_start may hold anything. */
 int pgicp_partial_chain_seeded_f32(pgicp_ctx *ctx, int map_id, const float *reading, int stride, int n, int mem, const double *T,
                                    pgicp_ctx *src, int n_seg, const int32_t *src_start, const int32_t *dst_start,
                                    double *weighted_point_used_ratio, double *residual);

@@ -1054,6 +1054,9 @@ protected:
             icp_sequence_.setMap(lm.Cloud());
         }
         rebuilds_++;
+        // (the ICP's correspondences are slots of the map this call has just replaced, and map_segs_ now describes the new one: the
+        //  next probe goes unseeded -- the library would refuse the source by its map's stamp anyway)
+        last_icp_on_device_reading_ = false;
     }
     T OverlapWith(const std::vector<size_t> &comp)                          // ComputeOverlapWith, Localizer.hpp:282-348
     {

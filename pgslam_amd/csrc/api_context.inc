@@ -42,6 +42,7 @@ struct SharedBlock {
 template <typename T>
 struct MapHost {
     bool used = false;
+    unsigned long long stamp = 0;   // pgicp_ctx::map_clock when this context created or adopted the map (seed_source.hpp)
     int m = 0;
     T mean[3] = {0, 0, 0};
     bool has_nrm = false;
@@ -101,9 +102,12 @@ struct pgicp_ctx {
     State<double> f64;
     DevBuf probs, src, partials, sums, sums2, small, stats, bdesc, tmp_a, tmp_b, tmp_c, tmp_d, tmp_e, tmp_f, tmp_r, tmp_w, tmp_p, tmp_n;
     // what problem 0 of the last ALIGN call was (pgicp_partial_chain_seeded reads another context's correspondences): its reading's
-    // size, the slot of its map in the context's table, the cloud type; -1: none
-    int last_n0 = -1, last_map0 = -1, last_elem = 0;
-    template <typename T> bool last_is() const { return last_elem == (int)sizeof(T); }
+    // size, the slot of its map in the context's table, the cloud type, the knn it ran with, that map's stamp; -1: none
+    int last_n0 = -1, last_map0 = -1, last_elem = 0, last_knn = 0;
+    unsigned long long last_stamp0 = 0;
+    // moves with every map create, destroy, transfer in and transfer out (either cloud type); a map keeps the value it was
+    // registered with (MapHost::stamp) -- table entries are reused, stamps are not
+    unsigned long long map_clock = 0;
     DevBuf scan_pos;                // PGICP_SUM_ORDER_SCAN: the inverse of `order` (sorted position of every reading point)
     DevBuf qrow, qtmp, order, qcounts, qblock, qstart, qcursor, slow_list, slow_lb, slow_ring, slow2, active, sel_tables, queue;
     // host-input pipeline (pgicp_upload_*): a copy stream and two upload sets used alternately

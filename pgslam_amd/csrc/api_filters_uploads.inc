@@ -233,7 +233,9 @@ int map_transfer_impl(pgicp_ctx *from, int id, pgicp_ctx *to, int *new_id)
     for (size_t i = 0; i < S.maps.size(); i++) if (!S.maps[i].used) { slot = (int)i; break; }
     if (slot < 0) { S.maps.push_back(MapHost<T>()); slot = (int)S.maps.size() - 1; }
     S.maps[slot] = *src;
+    S.maps[slot].stamp = ++to->map_clock;
     *src = MapHost<T>();                           // ownership of the device block moves with the record
+    ++from->map_clock;
     *new_id = slot | id_tag<T>();
     return sync_maps_table<T>(to);
 }

@@ -29,6 +29,7 @@ struct BatchLayout {
 // grid), pre-transformed and seeded in ONE kernel (k_borrow_order) where the sort is seven launches.
 struct BorrowSpec {
     const int *order_a, *slot_a; const void *pts_a; SeedSegs sg; const int *slot_of_b; int m_b;
+    int first_a, m_a;           // the source map's slots: [first_a, first_a + m_a) of pts_a
     // out: the problem starts with a search cap (ProblemDev::rlimit) taken from the threshold the context's previous call of this
     // kind ended with -- matcher mode 3: seeds from outside AND the capped, lazily exact search of an ICP's later iterations
     mutable bool capped = false;
@@ -192,7 +193,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
         // coherent for every iteration
         if (borrow && P == 1 && !L.normals)
             launch_borrow_order<T>(c->stream, c->probs.as<ProblemDev>(), src_dev, borrow->order_a, borrow->slot_a, (const typename Vec4<T>::type *)borrow->pts_a,
-                                   pr[0].n, borrow->sg, borrow->slot_of_b, borrow->m_b, S.rd_sorted.template as<T>(), c->order.as<int>(), S.slot.template as<int>());
+                                   borrow->first_a, borrow->m_a, pr[0].n, borrow->sg, borrow->slot_of_b, borrow->m_b, S.rd_sorted.template as<T>(), c->order.as<int>(), S.slot.template as<int>());
         else
         launch_query_sort<T>(c->stream, c->probs.as<ProblemDev>(), src_dev, S.d_maps.template as<MapDev<T>>(),
                              S.rd_pre.template as<typename Vec4<T>::type>(), S.rd_sorted.template as<T>(), c->qrow.as<int>(), c->qtmp.as<unsigned long long>(),
@@ -644,7 +645,9 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         if (res_ratio) res_ratio[p] = ok ? rs[27] / ((double)pr[p].n * L.knn) : 0.0;
         if (residual) residual[p] = ok ? rs[29] : std::numeric_limits<double>::infinity();
     }
-    c->last_n0 = pr[0].n; c->last_map0 = map_index<T>(c, pr[0].map_id); c->last_elem = (int)sizeof(T);      // (pgicp_partial_chain_seeded may read problem 0's correspondences)
+    // (pgicp_partial_chain_seeded may read problem 0's correspondences: knn slots per point, of the map that carries this stamp)
+    c->last_n0 = pr[0].n; c->last_map0 = map_index<T>(c, pr[0].map_id); c->last_elem = (int)sizeof(T); c->last_knn = L.knn;
+    c->last_stamp0 = c->last_map0 >= 0 ? S.maps[c->last_map0].stamp : 0;
     if (host_timing) {
         const auto ht3 = std::chrono::steady_clock::now();
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

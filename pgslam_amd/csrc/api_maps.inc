@@ -120,6 +120,7 @@ void free_map(pgicp_ctx *c, MapHost<T> &m)
         m.block->p = nullptr;
     }
     m = MapHost<T>();
+    if (c) ++c->map_clock;          // (pgicp_ctx_destroy frees its maps with no context: the block goes straight back to the device)
 }
 
 // one reference cloud of a batched map creation
@@ -344,6 +345,7 @@ int map_create_batch(pgicp_ctx *c, int n, const MapSrc<T> *src, int mem, int cen
         for (size_t i = 0; i < S.maps.size(); i++) if (!S.maps[i].used) { id = (int)i; break; }
         if (id < 0) { S.maps.push_back(MapHost<T>()); id = (int)S.maps.size() - 1; }
         S.maps[id] = Ms[k];
+        S.maps[id].stamp = ++c->map_clock;
         map_ids[k] = id | id_tag<T>();
     }
     return sync_maps_table<T>(c);

@@ -105,16 +105,23 @@ int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ra
     // all of it is one kernel instead of the reading sort.  Mode 2 of the matcher: seeds are read, the pass has no history.
     BorrowSpec bs;
     bool borrow = false;
-    if (seed && P == 1 && std::max(1, c->prm.knn) == 1 && c->prm.matcher == PGICP_MATCHER_GRID && !(c->prm.normal_max_angle > 0.0) &&
-        c->gd_mode == PGICP_DESC_FILTER_OFF && seed->src && seed->src != c &&
-        seed->src->device == c->device && seed->n_seg > 0 && seed->n_seg <= 16 && seed->src->last_n0 == pr[0].n && seed->src->template last_is<T>()) {
+    // Whether the source's state is still what it claims to be is seed_source_ok's to say (seed_source.hpp), and nobody else's.
+    if (seed && seed->src) {
         pgicp_ctx *a = seed->src;
         State<T> &SA = state<T>(a);
         MapHost<T> *MB = get_map<T>(c, pr[0].map_id);
-        const MapHost<T> *MA = a->last_map0 >= 0 && a->last_map0 < (int)SA.maps.size() && SA.maps[a->last_map0].used ? &SA.maps[a->last_map0] : nullptr;
-        if (MA && MB) {
+        const MapHost<T> *MA = a->last_map0 >= 0 && a->last_map0 < (int)SA.maps.size() ? &SA.maps[a->last_map0] : nullptr;
+        SeedSource q;
+        q.src_n = a->last_n0; q.src_elem = a->last_elem; q.src_knn = a->last_knn; q.src_map = a->last_map0; q.src_device = a->device;
+        q.src_stamp = a->last_stamp0;
+        q.n = pr[0].n; q.elem = (int)sizeof(T); q.device = c->device; q.n_seg = seed->n_seg; q.src_is_self = a == c;
+        q.problems = P; q.knn = std::max(1, c->prm.knn); q.grid_matcher = c->prm.matcher == PGICP_MATCHER_GRID;
+        q.normals_filter = c->prm.normal_max_angle > 0.0; q.desc_filter = c->gd_mode != PGICP_DESC_FILTER_OFF;
+        q.map_used = MA && MA->used; q.map_stamp = MA ? MA->stamp : 0;
+        if (seed_source_ok(q) && MB) {
             if (!MB->slot_of_made) { launch_slot_of<T>(c->stream, MB->pts, MB->first, MB->m, MB->slot_of); MB->slot_of_made = true; }
             bs.order_a = a->order.as<int>(); bs.slot_a = SA.slot.template as<int>(); bs.pts_a = MA->pts;
+            bs.first_a = MA->first; bs.m_a = MA->m;
             bs.sg.n = seed->n_seg;
             for (int k = 0; k <= seed->n_seg; k++) bs.sg.src[k] = seed->src_start[k];
             for (int k = 0; k < seed->n_seg; k++) bs.sg.dst[k] = seed->dst_start[k];

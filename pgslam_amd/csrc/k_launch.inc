@@ -192,9 +192,9 @@ void launch_knn(hipStream_t st, int matcher, const ProblemDev *probs, const MapD
 
 template <typename T>
 void launch_borrow_order(hipStream_t st, const ProblemDev *probs, const SrcDesc *src, const int *order_a, const int *slot_a, const typename Vec4<T>::type *pts_a,
-                         int n, const SeedSegs &sg, const int *slot_of_b, int m_b, T *rd_sorted, int *order_b, int *slot_b)
+                         int first_a, int m_a, int n, const SeedSegs &sg, const int *slot_of_b, int m_b, T *rd_sorted, int *order_b, int *slot_b)
 {
-    hipLaunchKernelGGL(k_borrow_order<T>, dim3(cdiv(n, 256)), dim3(256), 0, st, probs, src, order_a, slot_a, pts_a, n, sg, slot_of_b, m_b, rd_sorted, order_b, slot_b);
+    hipLaunchKernelGGL(k_borrow_order<T>, dim3(cdiv(n, 256)), dim3(256), 0, st, probs, src, order_a, slot_a, pts_a, first_a, m_a, n, sg, slot_of_b, m_b, rd_sorted, order_b, slot_b);
 }
 
 template <typename T>
@@ -565,7 +565,7 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     template void launch_slot_of<T>(hipStream_t, const typename Vec4<T>::type *, int, int, int *);                       \
     template void launch_gd_max<T>(hipStream_t, ProblemDev *, const MapDev<T> *, const int *, int, int, const int *);     \
     template void launch_map_values<T>(hipStream_t, const typename Vec4<T>::type *, int, int, const T *, int, T *, int *); \
-    template void launch_borrow_order<T>(hipStream_t, const ProblemDev *, const SrcDesc *, const int *, const int *, const typename Vec4<T>::type *, int, const SeedSegs &, \
+    template void launch_borrow_order<T>(hipStream_t, const ProblemDev *, const SrcDesc *, const int *, const int *, const typename Vec4<T>::type *, int, int, int, const SeedSegs &, \
                                          const int *, int, T *, int *, int *);                                            \
     template int launch_surface_normals<T>(hipStream_t, const MapDev<T> *, int, int, int, T, T, T *, int, T *, int *, T *); \
     template int launch_surface_normals_ext<T>(hipStream_t, const MapDev<T> *, int, int, int, T, T, T *, int, T *, int *, T *, T *, const NormalsExtOut<T> &); \

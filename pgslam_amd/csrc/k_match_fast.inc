@@ -94,7 +94,7 @@ __device__ __forceinline__ void finish_query(const MapDev<T> &M, const GridDesc<
 // its own pre-transform (the arithmetic of k_qbin: apply_T in T) and seeds it.
 template <typename T>
 __global__ __launch_bounds__(256) void k_borrow_order(const ProblemDev *__restrict__ probs, const SrcDesc *__restrict__ src, const int *__restrict__ order_a,
-                                                       const int *__restrict__ slot_a, const typename Vec4<T>::type *__restrict__ pts_a, int n, SeedSegs sg,
+                                                       const int *__restrict__ slot_a, const typename Vec4<T>::type *__restrict__ pts_a, int first_a, int m_a, int n, SeedSegs sg,
                                                        const int *__restrict__ slot_of_b, int m_b, T *__restrict__ rd_sorted, int *__restrict__ order_b,
                                                        int *__restrict__ slot_b)
 {
@@ -111,12 +111,15 @@ __global__ __launch_bounds__(256) void k_borrow_order(const ProblemDev *__restri
     order_b[P.off + j] = i;
     const int s = slot_a[j];
     int out = -1;
-    if (s >= 0) {
+    // (a seed outside the source map's slots [first_a, first_a + m_a) is dropped -- "none" and "not located" among them; the host
+    //  refuses a source whose map has changed, seed_source.hpp: this keeps the read inside the block whatever slot_a holds)
+    if ((unsigned)s - (unsigned)first_a < (unsigned)m_a) {
         const int ia = Bits<T>::unpack_idx(pts_a[s].w);
         for (int k = 0; k < sg.n; ++k)
             if (ia >= sg.src[k] && ia < sg.src[k + 1]) {
-                const int ib = sg.dst[k] < 0 ? -1 : ia - sg.src[k] + sg.dst[k];
-                if (ib >= 0 && ib < m_b) out = slot_of_b[ib];
+                // (compared before it is added, without sign: no src_start / dst_start of the caller's leads outside slot_of_b)
+                const unsigned off = (unsigned)ia - (unsigned)sg.src[k];
+                if (sg.dst[k] >= 0 && sg.dst[k] < m_b && off < (unsigned)(m_b - sg.dst[k])) out = slot_of_b[sg.dst[k] + (int)off];
                 break;
             }
     }

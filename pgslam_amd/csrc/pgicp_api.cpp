@@ -19,6 +19,7 @@
 #include "pgicp_elipsoids.h"
 #include "pgicp_sensor_chain.h"
 #include "kernels.hpp"
+#include "seed_source.hpp"
 
 #include <algorithm>
 #include <atomic>
