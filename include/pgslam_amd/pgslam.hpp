@@ -318,7 +318,9 @@ public:
         }
         double Tm[16], ratio = 0, residual = 0;
         pgslam_amd::to_row_major16(T_world_robot, Tm);
+        temp_icp.matcher->takeRadii(reading);               // (KDTreeVarDistMatcher: the reading's radius row goes with the call)
         temp_icp.pushParams();
+        temp_icp.matcher->armRadii(reading);
         PM::check(temp_icp.ctx, pgslam_amd::Abi<T>::partial(temp_icp.ctx, temp_icp.matcher->mapId, reading.xyzPtr(), reading.xyzStride(),
                                                            (int)reading.getNbPoints(), Tm, &ratio, &residual));
         return (T)ratio;
@@ -329,7 +331,8 @@ public:
     {
         if (!temp_icp_) throw std::logic_error("ComputeOverlapAgainstPrepared: no reference prepared");
         typename PM::ICP &temp_icp = *temp_icp_;
-        if (!reading || !temp_icp.deviceReadingEquivalent()) return ComputeOverlapAgainstPrepared(*reading.filtered, T_world_robot);
+        // (a matcher with per-point radii reads a descriptor of the reading: the host cloud goes the usual, unseeded way)
+        if (!reading || !temp_icp.deviceReadingEquivalent() || temp_icp.matcher->perPointRadii()) return ComputeOverlapAgainstPrepared(*reading.filtered, T_world_robot);
         double Tm[16], ratio = 0, residual = 0;
         pgslam_amd::to_row_major16(T_world_robot, Tm);
         temp_icp.pushParams();
@@ -344,7 +347,7 @@ public:
     {
         if (!temp_icp_) throw std::logic_error("ComputeOverlapAgainstPrepared: no reference prepared");
         typename PM::ICP &temp_icp = *temp_icp_;
-        if (!reading || !temp_icp.deviceReadingEquivalent() || !icp_ctx || src_start.size() != dst_start.size() + 1)
+        if (!reading || !temp_icp.deviceReadingEquivalent() || temp_icp.matcher->perPointRadii() || !icp_ctx || src_start.size() != dst_start.size() + 1)
             return ComputeOverlapAgainstPrepared(reading, T_world_robot);
         double Tm[16], ratio = 0, residual = 0;
         pgslam_amd::to_row_major16(T_world_robot, Tm);
@@ -596,7 +599,9 @@ public:
         }
         double Tm[16], ratio = 0, residual = 0;
         pgslam_amd::to_row_major16(T_refkf_kf, Tm);
+        temp_icp.matcher->takeRadii(input_cloud);
         temp_icp.pushParams();
+        temp_icp.matcher->armRadii(input_cloud);
         PM::check(temp_icp.ctx, pgslam_amd::Abi<T>::partial(temp_icp.ctx, temp_icp.matcher->mapId, input_cloud.xyzPtr(), input_cloud.xyzStride(),
                                                            (int)input_cloud.getNbPoints(), Tm, &ratio, &residual));
         return (T)residual;
@@ -716,6 +721,9 @@ public:
                 noise_strides[k] = (int)rd.descriptors.rows(); noise_n[k] = (int)rd.getNbPoints();
                 noisy = true;
             }
+        // (a matcher with per-point radii takes one row per reading and one max_dist per row: pair by pair, never silently without)
+        if (chain_.matcher && chain_.matcher->perPointRadii())
+            throw std::runtime_error("LoopClosureBatch: KDTreeVarDistMatcher reads a radius row of every reading: process the pair with PairLoopCloser");
         chain_.pushParams(with_nrm == P && P > 0 && chain_.hasNormalFilter());
         for (int k = 0; k < P; k++) {
             const Candidate &c = queue_[mine[k]];
@@ -792,6 +800,9 @@ private:
         // whatever throws below (a partially failed map_create_batch, pushParams, PM::check): the maps made so far go back to the pool
         MapGuard guard{ctx, maps};
         PM::check(ctx, pgslam_amd::Abi<T>::map_create_batch_dev(ctx, P, xyz.data(), xs.data(), nrm.data(), ns.data(), ms.data(), 1, maps.data()));
+        // (a matcher with per-point radii takes one row per reading and one max_dist per row: pair by pair, never silently without)
+        if (chain_.matcher && chain_.matcher->perPointRadii())
+            throw std::runtime_error("LoopClosureBatch: KDTreeVarDistMatcher reads a radius row of every reading: process the pair with PairLoopCloser");
         chain_.pushParams();
         for (int k = 0; k < P; k++) {
             const Candidate &c = queue_[mine[k]];

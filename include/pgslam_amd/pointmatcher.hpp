@@ -30,6 +30,7 @@
 
 #include "../pgicp.h"
 #include "../pgicp_noise.h"
+#include "../pgicp_vardist.h"
 #include "../pgicp_density.h"
 #include "../pgicp_covsample.h"
 #include "covsample_host.hpp"
@@ -208,6 +209,7 @@ template <typename T> struct Abi {
     static int local_map_dev(pgicp_ctx *c, int k, const T *const *x, const T *const *n, const int *sx, const int *sn, const int *cnt, const double *Ts, T *ox, int os, T *on, int ons) { return pick<T>(pgicp_build_local_map_f32, pgicp_build_local_map_f64)(c, k, x, n, sx, sn, cnt, Ts, ox, os, on, ons, PGICP_DEVICE); }
     static int map_create_dev(pgicp_ctx *c, const T *x, int xs, const T *n, int ns, int m, int center, int *id) { return pick<T>(pgicp_map_create_f32, pgicp_map_create_f64)(c, x, xs, n, ns, m, PGICP_DEVICE, center, id); }
     static int transform_dev(pgicp_ctx *c, const double *T16, const T *in, int is, T *out, int os, int n, int rotate_only) { return pick<T>(pgicp_transform_f32, pgicp_transform_f64)(c, T16, in, is, out, os, n, rotate_only, PGICP_DEVICE); }
+    static int arm_radii(pgicp_ctx *c, int k, const T *const *rows, const int *strides, const int *n) { return pick<T>(pgicp_arm_reading_radii_f32, pgicp_arm_reading_radii_f64)(c, k, rows, strides, n, PGICP_HOST); }
     static int arm_noise(pgicp_ctx *c, int k, const T *const *rows, const int *strides, const int *n) { return pick<T>(pgicp_arm_reading_noise_f32, pgicp_arm_reading_noise_f64)(c, k, rows, strides, n, PGICP_HOST); }
     static int set_values(pgicp_ctx *c, int id, const T *v, int stride) { return pick<T>(pgicp_map_set_values_f32, pgicp_map_set_values_f64)(c, id, v, stride, PGICP_HOST); }
     static int map_create_batch_dev(pgicp_ctx *c, int k, const T *const *x, const int *xs, const T *const *n, const int *ns, const int *m, int center, int *ids) { return pick<T>(pgicp_map_create_batch_f32, pgicp_map_create_batch_f64)(c, k, x, xs, n, ns, m, PGICP_DEVICE, center, ids); }
@@ -1948,9 +1950,60 @@ struct PointMatcher {
             if (mapId < 0) throw std::runtime_error("Matcher::findClosests: init() was not called");
             const int n = (int)filteredReading.getNbPoints();
             Matches m(knn < 1 ? 1 : knn, n);                  // knn x N, column-major: [point][neighbour], as the ABI writes them
+            takeRadii(filteredReading);
             chain->pushParams();
+            armRadii(filteredReading);
             check(chain->ctx, A::match(chain->ctx, mapId, filteredReading.xyzPtr(), filteredReading.xyzStride(), n, m.ids.data(), m.dists.data()));
             return m;
+        }
+        //! A matcher with one search radius per reading point (KDTreeVarDistMatcher).  Every call that matches a host reading goes
+        //! takeRadii(reading) -- the row is looked at and its largest value becomes maxDist --, pushParams(), armRadii(reading) --
+        //! the row is handed to the next matching call of the context --, then the call.  Nothing for KDTreeMatcher.
+        virtual bool perPointRadii() const { return false; }
+        virtual void takeRadii(const DataPoints &) {}
+        virtual void armRadii(const DataPoints &) const {}
+        //! a reading that lives in device memory carries coordinates only: refused by a matcher that reads a descriptor of it
+        virtual void refuseDeviceReading() const {}
+    };
+    //! [EXT] KDTreeVarDistMatcher{knn, epsilon, searchType, maxDistField} (Matchers/KDTree.cpp's second matcher): every reading point
+    //! has its own search radius, the one-row descriptor `maxDistField` of the reading (default "maxSearchDist") after the reading
+    //! filters, which carry descriptor rows along.  The statement is include/pgicp_vardist.h's: the neighbours of point i are the knn
+    //! nearest among those with d2 <= r_i * r_i (the product in T); a negative or NaN radius is refused, +inf cuts nothing.  The
+    //! context's max_dist is the row's largest value (+inf if any is).  It has no maxDist parameter (upstream has none).
+    struct KDTreeVarDistMatcher : Matcher {
+        std::string maxDistField = "maxSearchDist";
+        explicit KDTreeVarDistMatcher(ICPChainBase *c) : Matcher(c) {}
+        bool perPointRadii() const override { return true; }
+        //! the row of `reading`: throws, naming the field, when the descriptor is missing or is not one row
+        int row(const DataPoints &reading) const
+        {
+            if (!reading.descriptorExists(maxDistField))
+                throw std::runtime_error("KDTreeVarDistMatcher: the reading has no descriptor " + maxDistField);
+            if (reading.getDescriptorDimension(maxDistField) != 1)
+                throw std::runtime_error("KDTreeVarDistMatcher: descriptor " + maxDistField + " must have one row, it has " +
+                                         std::to_string(reading.getDescriptorDimension(maxDistField)));
+            return (int)reading.getDescriptorStartingRow(maxDistField);
+        }
+        void takeRadii(const DataPoints &reading) override
+        {
+            const int r = row(reading);
+            T largest = T(0);
+            for (int j = 0; j < (int)reading.getNbPoints(); j++) {
+                const T v = reading.descriptors(r, j);
+                if (v > largest) largest = v;             // (+inf: the largest; a NaN is left to the consuming call, which refuses it)
+            }
+            this->maxDist = largest;
+        }
+        void armRadii(const DataPoints &reading) const override
+        {
+            const T *rowp = reading.descriptors.data() + row(reading);
+            const int stride = (int)reading.descriptors.rows(), n = (int)reading.getNbPoints();
+            check(this->chain->ctx, A::arm_radii(this->chain->ctx, 1, &rowp, &stride, &n));
+        }
+        void refuseDeviceReading() const override
+        {
+            throw std::runtime_error("KDTreeVarDistMatcher: the reading is a device cloud, which carries no descriptor " + maxDistField +
+                                     "; pass the host cloud");
         }
     };
 
@@ -2323,9 +2376,19 @@ struct PointMatcher {
             }
             if (y.has("referenceDataPointsFilters")) referenceDataPointsFilters.load(y.sections.at("referenceDataPointsFilters"));
             matcher = std::make_shared<Matcher>(this);
-            if (y.has("matcher") && !y.sections.at("matcher").empty()) {
+            if (y.has("matcher") && !y.sections.at("matcher").empty() && y.sections.at("matcher")[0].name == "KDTreeVarDistMatcher") {
+                auto vd = std::make_shared<KDTreeVarDistMatcher>(this);
+                for (auto &kv : y.sections.at("matcher")[0].params) {
+                    if (kv.first == "knn") vd->knn = (int)to_double(kv.second, "knn");
+                    else if (kv.first == "epsilon") vd->epsilon = (T)to_double(kv.second, "epsilon");
+                    else if (kv.first == "searchType") {}      // both search types return the same neighbours here
+                    else if (kv.first == "maxDistField") vd->maxDistField = kv.second;
+                    else throw std::runtime_error("KDTreeVarDistMatcher: unknown parameter " + kv.first);
+                }
+                matcher = vd;
+            } else if (y.has("matcher") && !y.sections.at("matcher").empty()) {
                 const auto &m = y.sections.at("matcher")[0];
-                if (m.name != "KDTreeMatcher") throw std::runtime_error("loadFromYaml: unsupported matcher " + m.name);
+                if (m.name != "KDTreeMatcher") throw std::runtime_error("loadFromYaml: unsupported matcher " + m.name + " (KDTreeMatcher, KDTreeVarDistMatcher)");
                 for (auto &kv : m.params) {
                     if (kv.first == "knn") matcher->knn = (int)to_double(kv.second, "knn");
                     else if (kv.first == "epsilon") matcher->epsilon = (T)to_double(kv.second, "epsilon");
@@ -2603,6 +2666,7 @@ struct PointMatcher {
             // given the host cloud (refused, never run without the filter -- ADVICE round 4)
             if (hasNormalFilter() && r.filtered && r.filtered->normalsPtr() != nullptr)
                 throw std::logic_error("ICP: a SurfaceNormalOutlierFilter needs the reading's normals; pass the host cloud, not a device reading");
+            matcher->refuseDeviceReading();
             prefilteredReadingPtsCount = (unsigned)r.points();
             double Ti[16], To[16];
             pgslam_amd::to_row_major16(T_init, Ti);
@@ -2643,7 +2707,9 @@ struct PointMatcher {
             bool normalFilter = false;
             for (auto &f : outlierFilters) normalFilter = normalFilter || std::dynamic_pointer_cast<SurfaceNormalOutlierFilter>(f) != nullptr;
             const bool withNormals = normalFilter && reading.normalsPtr() != nullptr;
+            matcher->takeRadii(reading);
             pushParams(withNormals);
+            matcher->armRadii(reading);
             const bool noisy = armSensorNoise(reading);
             const int rc = withNormals ? A::align_nrm(ctx, matcher->mapId, reading.xyzPtr(), reading.xyzStride(), (int)reading.getNbPoints(),
                                                       reading.normalsPtr(), reading.normalsStride(), Ti, To, &st)

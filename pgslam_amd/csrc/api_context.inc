@@ -145,18 +145,30 @@ struct pgicp_ctx {
     // (packed, one problem after the other; off[p]: where problem p's start, -1: it has none) and the next ICP call consumes
     // them (api_noise.inc); every buffer here is allocated by an arm call or an armed ICP call only.  last_*: what
     // pgicp_last_noise_overlap answers with -- last_P < 0: the last ICP call was not armed.
-    struct Noise {
-        bool armed = false, bad = false;    // bad: a value was negative or not finite
+    // (ArmedRows: one value per reading point, armed for the next call -- what the noise rows and KDTreeVarDistMatcher's radii share)
+    struct ArmedRows {
+        bool armed = false, bad = false;    // bad: a value was refused (noise: negative or not finite; radii: negative or a NaN)
         int elem = 0;                       // sizeof(T) of the armed values
         std::vector<long long> off;
         std::vector<int> n;
-        DevBuf vals, off_dev, dist, out;    // off_dev: `off` on the device, then the staging kernel's flag; dist: sqrt(d2) per pair
-                                            // (-1: not kept); out: {S, nb} per problem, then the counts
+        DevBuf vals, off_dev;               // off_dev: `off` on the device, then the staging kernel's flag
+    };
+    struct Noise : ArmedRows {
+        DevBuf dist, out;                   // dist: sqrt(d2) per pair (-1: not kept); out: {S, nb} per problem, then the counts
         int last_P = -1;
         std::vector<double> last_overlap;
         std::vector<int> last_nb;
         std::vector<char> last_ok;
     } noise;
+    // KDTreeVarDistMatcher's radii (include/pgicp_vardist.h, api_vardist.inc).  pgicp_arm_reading_radii copies the rows as the noise
+    // rows are copied; the next matching call consumes them: `on` while that call runs -- its iterations cut the matcher's pairs
+    // into slot_cut / d2_cut (laid out as State::slot / ::d2) and everything downstream reads those (pair_slots / pair_d2);
+    // cut_live: the last call that matched was such a call (pgicp_debug_last_matches reads the cut pairs then).  Every buffer here
+    // is allocated by an arm call or an armed call only.
+    struct VarDist : ArmedRows {
+        bool on = false, cut_live = false;
+        DevBuf slot_cut, d2_cut;
+    } vd;
     int last_icp_P = 0;             // problems of the last ICP call: the last-call diagnostics check their `problem` against it
     int fset_next = 0;
     int up_next = 0;

@@ -211,7 +211,8 @@ int debug_last_matches(pgicp_ctx *c, int problem, int32_t *ids, T *dist2)
     HIPC(c, c->tmp_b.ensure(sizeof(T) * np));
     // `order` holds positions in the batch-wide sorted arrays: point the kernel at this problem's slice
     launch_unpermute<T>(c->stream, S.d_maps.template as<MapDev<T>>(), D.map, c->order.as<int>() + D.off,
-                        S.slot.template as<int>() + D.off * D.knn, S.d2.template as<T>() + D.off * D.knn, D.n, D.knn, c->tmp_a.as<int>(), c->tmp_b.as<T>());
+                        (c->vd.cut_live ? c->vd.slot_cut.as<int>() : S.slot.template as<int>()) + D.off * D.knn,
+                        (c->vd.cut_live ? c->vd.d2_cut.as<T>() : S.d2.template as<T>()) + D.off * D.knn, D.n, D.knn, c->tmp_a.as<int>(), c->tmp_b.as<T>());     // (pgicp_vardist.h: an armed call's pairs are the cut ones)
     XFER(c, d2h(c, ids, c->tmp_a.p, sizeof(int) * np));
     XFER(c, d2h(c, dist2, c->tmp_b.p, sizeof(T) * np));
     HIPC(c, stream_sync(c));

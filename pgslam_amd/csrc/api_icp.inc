@@ -111,6 +111,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
     }
     HIPC(c, S.slot.ensure(sizeof(int) * (size_t)L.total * L.knn));
     HIPC(c, S.d2.ensure(sizeof(T) * (size_t)L.total * L.knn));
+    { const int vst = vardist_begin<T>(c, (size_t)L.total * L.knn); if (vst) return vst; }
     if (L.normals) {
         HIPC(c, S.nrm_pre.ensure(sizeof(typename Vec4<T>::type) * (size_t)L.total));
         HIPC(c, S.nrm_sorted.ensure(sizeof(T) * 3 * (size_t)L.total));
@@ -228,9 +229,8 @@ static int probe_rings(const BatchLayout &L)
 template <typename T>
 void var_trim_enqueue(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, int nA)
 {
-    State<T> &S = state<T>(c);
     char *keys = (char *)c->vt_keys.p;
-    launch_var_trim<T>(c->stream, c->probs.as<ProblemDev>(), S.d2.template as<T>(), c->active.as<int>(), nA, keys,
+    launch_var_trim<T>(c->stream, c->probs.as<ProblemDev>(), pair_d2<T>(c), c->active.as<int>(), nA, keys,
                        keys + sizeof(T) * (size_t)L.total * L.knn, ch.vt_min, ch.vt_max, ch.vt_lambda);
 }
 
@@ -249,6 +249,12 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
     const MapDev<T> *maps = S.d_maps.template as<MapDev<T>>();
     ProblemDev *probs = c->probs.as<ProblemDev>();
     const T *rd_nrm = L.normals ? S.nrm_sorted.template as<T>() : nullptr;
+    // KDTreeVarDistMatcher's radii armed (pgicp_vardist.h): the matcher resolves every pair exactly under maxDist into its own
+    // arrays, which seed its next pass and stay as it left them; k_vardist_cut copies the pairs within their point's radius into
+    // the cut arrays, and everything behind the matcher reads those (`slot` / `d2` below)
+    const bool vardist = c->vd.on;
+    const int *slot = pair_slots<T>(c);
+    const T *d2 = pair_d2<T>(c);
     if (L.knn > 1) {
         // KDTreeMatcher.knn > 1: the top-K matcher finds every pair exactly (no queue, no lazy resolution), one selection
         // over the knn * N distances, the minimiser over the knn * N pairs
@@ -258,17 +264,18 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
         }
         {
             ProfScope ps(c, PGICP_PROF_TRIM, act_units, act_probs);
+            if (vardist) vardist_cut_enqueue<T>(c, nA, L.max_pairs());
             if (ch.var_trim) {
                 var_trim_enqueue<T>(c, L, ch, nA);
-                launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_pairs(), 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
+                launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_pairs(), 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
             } else {
-                launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_pairs(), 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, use_seed);
+                launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_pairs(), 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, use_seed);
             }
-            if (ch.gd_mode == PGICP_DESC_FILTER_SOFT) launch_gd_max<T>(c->stream, probs, maps, S.slot.template as<int>(), nA, L.max_pairs(), active);
+            if (ch.gd_mode == PGICP_DESC_FILTER_SOFT) launch_gd_max<T>(c->stream, probs, maps, slot, nA, L.max_pairs(), active);
         }
         {
             ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);
-            launch_reduce<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), rd_nrm, S.slot.template as<int>(), S.d2.template as<T>(),
+            launch_reduce<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), rd_nrm, slot, d2,
                              c->partials.as<double>(), nA, L.max_pairs(), active, ch);
         }
         if (with_solve) {
@@ -298,18 +305,19 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
         //  A cheaper counter clear would spare one selection an iteration there; the TrimmedDist path is left as it is)
         const bool grid = c->prm.matcher == PGICP_MATCHER_GRID;
         launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 0, active, c->sel_tables.as<int>(), c->qtmp.p,
-                              grid ? (int *)c->queue.p : nullptr, (ch.robust.fct != 0 || ch.var_trim) ? 0 : (use_seed == 1 || c->sel_guess_first));      // (every selection but a run's first starts from the last one's result,
+                              grid ? (int *)c->queue.p : nullptr, (ch.robust.fct != 0 || ch.var_trim || vardist) ? 0 : (use_seed == 1 || c->sel_guess_first));      // (every selection but a run's first starts from the last one's result,
                                                                                           // ProblemDev::qraw; a run's first from the previous call's, ::qhint, if there is one)
         c->seg_clean = grid ? 1 : 0;
     }
     const bool robust = ch.robust.fct != 0;
     // RobustOutlierFilter: nothing is trimmed -- the threshold the lazy path resolves queued queries up to is +inf from here on;
     // VarTrimmedDistOutlierFilter: its ratio is chosen over every distance -- the same
-    if (robust || ch.var_trim) launch_robust_open(c->stream, probs, active, nA);
+    // KDTreeVarDistMatcher's radii: the cut needs every pair under maxDist -- the same
+    if (robust || ch.var_trim || vardist) launch_robust_open(c->stream, probs, active, nA);
     // GenericDescriptorOutlierFilter, soft mode: its maximum covers every pair with a neighbour -- the same, and (no Robust /
     // VarTrimmed filter to set it) the second selection below must then restore the iteration's threshold
     const bool gd_soft = ch.gd_mode == PGICP_DESC_FILTER_SOFT;
-    if (gd_soft && !robust && !ch.var_trim && c->prm.matcher == PGICP_MATCHER_GRID) launch_gd_open(c->stream, probs, active, nA);
+    if (gd_soft && !robust && !ch.var_trim && !vardist && c->prm.matcher == PGICP_MATCHER_GRID) launch_gd_open(c->stream, probs, active, nA);
     if (c->prm.matcher == PGICP_MATCHER_GRID) {
         // lazy resolution: only queued queries whose lower bound is within the threshold just
         // selected (an upper bound of the final one) are searched exactly; then the threshold
@@ -333,27 +341,38 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
             }
         }
         ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        if (!robust && !ch.var_trim) launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 1, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 1);
+        if (!robust && !ch.var_trim && !vardist) launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 1, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 1);
+    }
+    if (vardist) {
+        // every pair is exact now: the cut, then -- no Robust or VarTrimmed filter to do it below -- the quantile filter's selection
+        // over the cut distances (a first selection without a guess, as RobustOutlierFilter's own), and the search cap lifted again
+        // for the next matcher pass: a threshold over cut distances says nothing about the search
+        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
+        vardist_cut_enqueue<T>(c, nA, L.max_n);
+        if (!robust && !ch.var_trim) {
+            launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_n, 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
+            launch_vardist_reset(c->stream, probs, active, nA);
+        }
     }
     if (ch.var_trim) {
         // every distance is exact now: the ratio of this iteration, then the selection at that ratio
         ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
         var_trim_enqueue<T>(c, L, ch, nA);
-        launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
+        launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_n, 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
     }
     if (robust) {
         // the scale of this iteration from the (now exact) distances: median, absolute deviations, their median
         ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        launch_robust_scale<T>(c->stream, probs, S.d2.template as<T>(), c->robust_dev.as<T>(), ch, nA, L.max_n, active, c->sel_tables.as<int>(), c->qtmp.p);
+        launch_robust_scale<T>(c->stream, probs, d2, c->robust_dev.as<T>(), ch, nA, L.max_n, active, c->sel_tables.as<int>(), c->qtmp.p);
     }
     if (gd_soft) {
         // every pair is exact now: the soft maximum of this iteration
         ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        launch_gd_max<T>(c->stream, probs, maps, S.slot.template as<int>(), nA, L.max_n, active);
+        launch_gd_max<T>(c->stream, probs, maps, slot, nA, L.max_n, active);
     }
     {
         ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);
-        launch_reduce<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), rd_nrm, S.slot.template as<int>(), S.d2.template as<T>(),
+        launch_reduce<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), rd_nrm, slot, d2,
                          c->partials.as<double>(), nA, L.max_n, active, ch);
     }
     if (with_solve) {
@@ -397,7 +416,10 @@ void one_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, bo
         const void *bufs[] = {c->probs.p, S.d_maps.p, S.rd_sorted.p, S.slot.p, S.d2.p, S.none_r.p, c->small.p, c->slow_list.p, c->slow_lb.p,
                               c->slow_ring.p, c->slow2.p, c->active.p, c->queue.p, c->sel_tables.p, c->qtmp.p, c->partials.p, c->h_flag, c->stamp_dev,
                               c->robust_dev.p, L.normals ? S.nrm_sorted.p : nullptr, c->vt_on ? c->vt_keys.p : nullptr,
-                              (const void *)(size_t)(c->vt_on ? L.total : 0)};     // (VarTrimmed: the second key list starts L.total pairs in)
+                              (const void *)(size_t)(c->vt_on ? L.total : 0),     // (VarTrimmed: the second key list starts L.total pairs in)
+                              // (armed radii: the cut's arrays, rows and the reading order it gathers them through)
+                              c->vd.on ? c->vd.slot_cut.p : nullptr, c->vd.on ? c->vd.d2_cut.p : nullptr, c->vd.on ? c->vd.vals.p : nullptr,
+                              c->vd.on ? c->vd.off_dev.p : nullptr, c->vd.on ? c->order.p : nullptr};
         mix(bufs, sizeof bufs);
         pgicp_ctx::IterGraph *g = nullptr;
         for (auto &e : c->iter_graphs) if (e.exec && e.key == key) { g = &e; break; }
@@ -493,8 +515,10 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
                 double *res_ratio = nullptr, int *res_status = nullptr)
 {
     const bool noisy = noise_take(c);            // (pgicp_arm_reading_noise: one-shot, consumed here whatever follows)
+    VarDistCall radii(c);                        // (pgicp_arm_reading_radii: the same)
     if (!c || P <= 0 || !pr || !T_out) return fail(c, PGICP_ERR_ARG, "pgicp_align_batch: bad argument");
     if (noisy) { const int nst = noise_check<T>(c, P, pr); if (nst) return nst; }
+    { const int rst = radii.template check<T>(P, pr); if (rst) return rst; }
     HIPC(c, hipSetDevice(c->device));
     State<T> &S = state<T>(c);
     const pgicp_params &prm = c->prm;
@@ -582,7 +606,7 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         HIPC(c, N.dist.ensure(sizeof(T) * (size_t)L.total * L.knn));
         HIPC(c, hipMemsetAsync((char *)N.out.p + cnt_off, 0, sizeof(int) * (size_t)P, c->stream));
         launch_noise_overlap<T>(c->stream, c->probs.as<ProblemDev>(), S.d_maps.template as<MapDev<T>>(), L.normals ? S.nrm_sorted.template as<T>() : nullptr,
-                                S.slot.template as<int>(), S.d2.template as<T>(), c->order.as<int>(), N.vals.template as<T>(),
+                                pair_slots<T>(c), pair_d2<T>(c), c->order.as<int>(), N.vals.template as<T>(),
                                 N.off_dev.as<long long>(), N.dist.template as<T>(), c->partials.as<double>(), N.out.as<double>(),
                                 (int *)((char *)N.out.p + cnt_off), P, L.max_pairs(), ch);
         nres.resize(cnt_off + sizeof(int) * (size_t)P);
@@ -592,7 +616,7 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
     if (with_cov) {
         ProfScope ps(c, PGICP_PROF_COV, L.total, P);
         launch_cov<T>(c->stream, c->probs.as<ProblemDev>(), S.d_maps.template as<MapDev<T>>(), S.rd_sorted.template as<T>(),
-                      L.normals ? S.nrm_sorted.template as<T>() : nullptr, S.slot.template as<int>(), S.d2.template as<T>(),
+                      L.normals ? S.nrm_sorted.template as<T>() : nullptr, pair_slots<T>(c), pair_d2<T>(c),
                       c->partials.as<double>(), c->sums.as<double>(), P, L.max_pairs(), ch);
     } else HIPC(c, hipMemsetAsync(c->sums.p, 0, sizeof(double) * (size_t)P * kCovTerms, c->stream));
     std::vector<double> cs((size_t)P * kCovTerms);
@@ -707,7 +731,7 @@ int icp_pair(pgicp_ctx *c, const T *reading, int rd_stride, int n, const T *ref_
 {
     int id = -1;
     int st = map_create<T>(c, ref_xyz, ref_stride, ref_nrm, nrm_stride, m, mem, 1, &id);
-    if (st) { (void)noise_take(c); return st; }
+    if (st) { (void)noise_take(c); VarDistCall radii(c); return st; }
     pgicp_problem pr;
     std::memset(&pr, 0, sizeof pr);
     pr.map_id = id; pr.reading = reading; pr.stride = rd_stride; pr.n = n; pr.mem = mem;

@@ -44,18 +44,21 @@ int simple_sensor_noise(pgicp_ctx *c, const T *xyz, int stride, int n, int mem, 
     return PGICP_OK;
 }
 
+// One value per reading point of every problem, copied into the context for the next call to consume: the noise rows here, and
+// KDTreeVarDistMatcher's radii (api_vardist.inc).  `what`: the entry point's name for the messages; `inf_ok`: +inf is a value (a
+// radius that cuts nothing) -- otherwise a value must be finite; neither takes a negative value or a NaN.  `stage`: the kernel that
+// copies a device row and raises the flag at a refused value.
 template <typename T>
-int arm_reading_noise(pgicp_ctx *c, int P, const T *const *noise, const int *stride, const int *n, int mem)
+int arm_rows(pgicp_ctx *c, pgicp_ctx::ArmedRows &N, const char *what, bool inf_ok, void (*stage)(hipStream_t, const T *, int, int, T *, int *),
+             int P, const T *const *rows, const int *stride, const int *n, int mem)
 {
-    if (!c) return PGICP_ERR_ARG;
-    pgicp_ctx::Noise &N = c->noise;
     N.armed = false;
-    if (P <= 0 || P > 65535 || !noise || !stride || !n || (mem != PGICP_HOST && mem != PGICP_DEVICE))
-        return fail(c, PGICP_ERR_ARG, "pgicp_arm_reading_noise: bad argument");
+    if (P <= 0 || P > 65535 || !rows || !stride || !n || (mem != PGICP_HOST && mem != PGICP_DEVICE))
+        return fail(c, PGICP_ERR_ARG, std::string(what) + ": bad argument");
     size_t total = 0;
     for (int p = 0; p < P; p++) {
-        if (!noise[p]) continue;
-        if (stride[p] < 1 || n[p] <= 0) return fail(c, PGICP_ERR_ARG, "pgicp_arm_reading_noise: bad stride or size of problem " + std::to_string(p));
+        if (!rows[p]) continue;
+        if (stride[p] < 1 || n[p] <= 0) return fail(c, PGICP_ERR_ARG, std::string(what) + ": bad stride or size of problem " + std::to_string(p));
         total += (size_t)n[p];
     }
     HIPC(c, hipSetDevice(c->device));
@@ -68,17 +71,17 @@ int arm_reading_noise(pgicp_ctx *c, int P, const T *const *noise, const int *str
     HIPC(c, N.off_dev.ensure(flag_off + sizeof(int)));
     HIPC(c, N.vals.ensure(sizeof(T) * std::max<size_t>(total, 1)));
     long long off = 0;
-    for (int p = 0; p < P; p++) if (noise[p]) { N.off[p] = off; N.n[p] = n[p]; off += n[p]; }
+    for (int p = 0; p < P; p++) if (rows[p]) { N.off[p] = off; N.n[p] = n[p]; off += n[p]; }
     XFER(c, h2d(c, N.off_dev.p, N.off.data(), flag_off));
     if (mem == PGICP_HOST) {
         // packed and looked at on the host, one copy for the batch
         std::vector<T> packed(total);
         size_t k = 0;
         for (int p = 0; p < P; p++) {
-            if (!noise[p]) continue;
+            if (!rows[p]) continue;
             for (int i = 0; i < n[p]; i++) {
-                const T v = noise[p][(size_t)i * stride[p]];
-                if (!(v >= (T)0) || !std::isfinite(v)) N.bad = true;
+                const T v = rows[p][(size_t)i * stride[p]];
+                if (!(v >= (T)0) || (!inf_ok && !std::isfinite(v))) N.bad = true;
                 packed[k++] = v;
             }
         }
@@ -89,9 +92,9 @@ int arm_reading_noise(pgicp_ctx *c, int P, const T *const *noise, const int *str
         int *flag = (int *)((char *)N.off_dev.p + flag_off);
         HIPC(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
         for (int p = 0; p < P; p++) {
-            if (!noise[p]) continue;
-            uu.touch(noise[p]);
-            launch_noise_stage<T>(c->stream, noise[p], stride[p], n[p], N.vals.template as<T>() + N.off[p], flag);
+            if (!rows[p]) continue;
+            uu.touch(rows[p]);
+            stage(c->stream, rows[p], stride[p], n[p], N.vals.template as<T>() + N.off[p], flag);
         }
         int bad = 0;
         XFER(c, d2h(c, &bad, flag, sizeof(int)));
@@ -102,18 +105,29 @@ int arm_reading_noise(pgicp_ctx *c, int P, const T *const *noise, const int *str
     N.armed = true;
     return PGICP_OK;
 }
+template <typename T>
+int arm_reading_noise(pgicp_ctx *c, int P, const T *const *noise, const int *stride, const int *n, int mem)
+{
+    if (!c) return PGICP_ERR_ARG;
+    return arm_rows<T>(c, c->noise, "pgicp_arm_reading_noise", false, launch_noise_stage<T>, P, noise, stride, n, mem);
+}
 
 // The consuming call's look at what was armed (before it does any work): the batch's shape and element type, the values
+// (`what`: "sensor noise" / "reading radii", for the messages)
+template <typename T>
+int rows_check(pgicp_ctx *c, const pgicp_ctx::ArmedRows &N, const std::string &what, const char *bad, int P, const pgicp_problem *pr)
+{
+    if (N.elem != (int)sizeof(T)) return fail(c, PGICP_ERR_ARG, what + ": armed with another element type than the call's");
+    if ((int)N.off.size() != P)
+        return fail(c, PGICP_ERR_ARG, what + ": armed for " + std::to_string(N.off.size()) + " problems, the call has " + std::to_string(P));
+    for (int p = 0; p < P; p++)
+        if (N.off[p] >= 0 && N.n[p] != pr[p].n)
+            return fail(c, PGICP_ERR_ARG, what + ": " + std::to_string(N.n[p]) + " values armed for problem " + std::to_string(p) + ", its reading has " + std::to_string(pr[p].n) + " points");
+    if (N.bad) return fail(c, PGICP_ERR_ARG, what + ": " + bad);
+    return PGICP_OK;
+}
 template <typename T>
 int noise_check(pgicp_ctx *c, int P, const pgicp_problem *pr)
 {
-    const pgicp_ctx::Noise &N = c->noise;
-    if (N.elem != (int)sizeof(T)) return fail(c, PGICP_ERR_ARG, "sensor noise: armed with another element type than the ICP call's");
-    if ((int)N.off.size() != P)
-        return fail(c, PGICP_ERR_ARG, "sensor noise: armed for " + std::to_string(N.off.size()) + " problems, the ICP call has " + std::to_string(P));
-    for (int p = 0; p < P; p++)
-        if (N.off[p] >= 0 && N.n[p] != pr[p].n)
-            return fail(c, PGICP_ERR_ARG, "sensor noise: " + std::to_string(N.n[p]) + " values armed for problem " + std::to_string(p) + ", its reading has " + std::to_string(pr[p].n) + " points");
-    if (N.bad) return fail(c, PGICP_ERR_ARG, "sensor noise: a value is negative or not finite");
-    return PGICP_OK;
+    return rows_check<T>(c, c->noise, "sensor noise", "a value is negative or not finite", P, pr);
 }

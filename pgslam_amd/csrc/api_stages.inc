@@ -33,6 +33,7 @@ int run_partial(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, i
         if (launch_knn_topk<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(), S.d2.template as<T>(), ch, 1, n,
                                c->active.as<int>()) != 0)
             return fail(c, PGICP_ERR_ARG, "KDTreeMatcher.knn exceeds PGICP_MAX_KNN");
+        if (c->vd.on) vardist_cut_enqueue<T>(c, 1, L.max_pairs());
         return PGICP_OK;
     }
     {
@@ -48,13 +49,22 @@ int run_partial(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, i
                                S.d2.template as<T>(), ch, c->small.as<int>() + 16, c->slow_list.as<int2>(), c->slow_lb.as<T>(),
                                c->slow2.as<int>(), 1, S.none_r.template as<T>());
     }
+    if (c->vd.on) vardist_cut_enqueue<T>(c, 1, L.max_pairs());      // (pgicp_vardist.h: what the call returns is cut as an iteration's pairs are)
     return PGICP_OK;
 }
 
 template <typename T>
 int match(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, int mem, const double *Tm, int32_t *ids, T *dist2)
 {
+    VarDistCall radii(c);                        // (pgicp_arm_reading_radii: one-shot, consumed here whatever follows)
     if (!c || !reading || n <= 0 || !ids || !dist2) return fail(c, PGICP_ERR_ARG, "pgicp_match: bad argument");
+    {
+        pgicp_problem one;
+        std::memset(&one, 0, sizeof one);
+        one.n = n;
+        const int rst = radii.template check<T>(1, &one);
+        if (rst) return rst;
+    }
     HIPC(c, hipSetDevice(c->device));
     BatchLayout L;
     std::vector<ProblemDev> hp;
@@ -65,7 +75,7 @@ int match(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, int mem
     HIPC(c, c->tmp_a.ensure(sizeof(int) * np));
     HIPC(c, c->tmp_b.ensure(sizeof(T) * np));
     launch_unpermute<T>(c->stream, S.d_maps.template as<MapDev<T>>(), map_index<T>(c, map_id), c->order.as<int>(),
-                        S.slot.template as<int>(), S.d2.template as<T>(), n, L.knn, c->tmp_a.as<int>(), c->tmp_b.as<T>());
+                        pair_slots<T>(c), pair_d2<T>(c), n, L.knn, c->tmp_a.as<int>(), c->tmp_b.as<T>());
     if (mem == PGICP_DEVICE) {
         HIPC(c, hipMemcpyAsync(ids, c->tmp_a.p, sizeof(int) * np, hipMemcpyDeviceToDevice, c->stream));
         HIPC(c, hipMemcpyAsync(dist2, c->tmp_b.p, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
@@ -88,7 +98,11 @@ struct SeedSpec {
 template <typename T>
 int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ratio, double *residual, int *status, const SeedSpec *seed = nullptr)
 {
+    // (pgicp_arm_reading_radii: one-shot, consumed here whatever follows -- but a seeded probe refuses and keeps the arm)
+    if (c && seed && c->vd.armed) return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain_seeded: reading radii are armed (pgicp_arm_reading_radii): the seeded probe takes none");
+    VarDistCall radii(c);
     if (!c || P <= 0 || !pr) return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain: bad argument");
+    { const int rst = radii.template check<T>(P, pr); if (rst) return rst; }
     HIPC(c, hipSetDevice(c->device));
     for (int p = 0; p < P; p++) {
         MapHost<T> *M = get_map<T>(c, pr[p].map_id);
@@ -170,7 +184,7 @@ template <typename T>
 int partial_chain(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, int mem, const double *Tm, double *ratio,
                   double *residual)
 {
-    if (!c || !reading || n <= 0) return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain: bad argument");
+    if (!c || !reading || n <= 0) { VarDistCall radii(c); return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain: bad argument"); }
     pgicp_problem pr;
     std::memset(&pr, 0, sizeof pr);
     pr.map_id = map_id; pr.reading = reading; pr.stride = stride; pr.n = n; pr.mem = mem;
@@ -191,7 +205,7 @@ int partial_chain_seeded(pgicp_ctx *c, int map_id, const T *reading, int stride,
     mat4_identity(pr.T_init);
     if (Tm) std::memcpy(pr.T_init, Tm, sizeof pr.T_init);
     const SeedSpec sp{src, n_seg, src_start, dst_start};
-    return partial_chain_batch<T>(c, 1, &pr, ratio, residual, nullptr, src ? &sp : nullptr);
+    return partial_chain_batch<T>(c, 1, &pr, ratio, residual, nullptr, &sp);
 }
 
 template <typename T>

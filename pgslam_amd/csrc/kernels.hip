@@ -204,6 +204,7 @@ __device__ __forceinline__ long long pairs_off(const ProblemDev &P) { return P.o
 #include "k_pairsort.inc"
 #include "k_voxel.inc"
 #include "k_noise.inc"
+#include "k_vardist.inc"
 #include "k_density.inc"
 #include "k_sensor_chain.inc"
 #include "k_covsample.inc"

@@ -93,6 +93,14 @@ template <typename T>
 void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, const T *rd_nrm, const int *slot, const T *d2,
                           const int *order, const T *noise, const long long *noise_off, T *dist, double *partials, double *out, int *count,
                           int P, int max_pairs, const ChainDev<T> &ch);
+// KDTreeVarDistMatcher's per-point radii (k_vardist.inc, include/pgicp_vardist.h): staging a device row; the cut of the matcher's
+// exact pairs into a second pair of arrays; the uncapped next pass after a quantile selection over cut distances
+template <typename T>
+void launch_vardist_stage(hipStream_t st, const T *src, int stride, int n, T *dst, int *flag);
+template <typename T>
+void launch_vardist_cut(hipStream_t st, const ProblemDev *probs, const int *active, int n_active, int max_pairs, const int *slot, const T *d2,
+                        const int *order, const T *radii, const long long *radii_off, int *slot_cut, T *d2_cut);
+void launch_vardist_reset(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
 void launch_robust_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
 void launch_gd_open(hipStream_t st, ProblemDev *probs, const int *active, int n_active);
 template <typename T>

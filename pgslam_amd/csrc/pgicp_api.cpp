@@ -6,6 +6,7 @@
 // There is no CPU compute path here: every stage runs on the GPU.
 #include "pgicp.h"
 #include "pgicp_noise.h"
+#include "pgicp_vardist.h"
 #include "pgicp_density.h"
 #include "pgicp_covsample.h"
 #include "pgslam_amd/covsample_host.hpp"
@@ -45,6 +46,7 @@ using namespace pgicp;
 #include "api_context.inc"            // context, allocation accounting, fail() / HIPC / XFER, the pinned bounce buffer, the profile
 #include "api_maps.inc"               // the device table of maps, the block pool, map_create_batch (the index build)
 #include "api_noise.inc"              // pgicp_simple_sensor_noise_*, pgicp_arm_reading_noise_*, the armed ICP call's reduction (pgicp_noise.h)
+#include "api_vardist.inc"            // pgicp_arm_reading_radii_*, the armed call's look at them, the cut (pgicp_vardist.h)
 #include "api_icp.inc"                // BatchLayout, batch_begin, one iteration, align_batch, icp_pair
 #include "api_stages.inc"             // match, partial chain, outlier weights, error statistics, transform, local maps, normals
 #include "api_filters_uploads.inc"    // pgicp_filter_cloud*, batched map ABI, last-call diagnostics, map transfer, pgicp_upload_*
@@ -181,6 +183,7 @@ void pgicp_ctx_destroy(pgicp_ctx *c)
     }
     c->dpf_work.release(); c->dpf_io.release(); c->dpf_stat.release();
     c->noise.vals.release(); c->noise.off_dev.release(); c->noise.dist.release(); c->noise.out.release();
+    c->vd.vals.release(); c->vd.off_dev.release(); c->vd.slot_cut.release(); c->vd.d2_cut.release();
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (auto &m : c->f32.maps) free_map<float>(nullptr, m);
     for (auto &m : c->f64.maps) free_map<double>(nullptr, m);
@@ -396,14 +399,14 @@ static pgicp_problem one_problem(int map_id, const void *rd, int stride, int n, 
 int pgicp_align_f32(pgicp_ctx *c, int map_id, const float *rd, int stride, int n, int mem, const double T_init[16],
                     double T_out[16], pgicp_stats *stats)
 {
-    if (!T_init) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null"); }
+    if (!T_init) { (void)noise_take(c); VarDistCall radii(c); return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null"); }
     pgicp_problem p = one_problem(map_id, rd, stride, n, mem, T_init);
     return align_batch<float>(c, 1, &p, T_out, stats);
 }
 int pgicp_align_f64(pgicp_ctx *c, int map_id, const double *rd, int stride, int n, int mem, const double T_init[16],
                     double T_out[16], pgicp_stats *stats)
 {
-    if (!T_init) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null"); }
+    if (!T_init) { (void)noise_take(c); VarDistCall radii(c); return fail(c, PGICP_ERR_ARG, "pgicp_align: T_init is null"); }
     pgicp_problem p = one_problem(map_id, rd, stride, n, mem, T_init);
     return align_batch<double>(c, 1, &p, T_out, stats);
 }
@@ -415,13 +418,13 @@ int pgicp_align_batch_f64(pgicp_ctx *c, int P, const pgicp_problem *pr, double *
 int pgicp_align_residual_batch_f32(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgicp_stats *stats, double *residual,
                                    double *ratio, int *status)
 {
-    if (!residual) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null"); }
+    if (!residual) { (void)noise_take(c); VarDistCall radii(c); return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null"); }
     return align_batch<float>(c, P, pr, T_out, stats, residual, ratio, status);
 }
 int pgicp_align_residual_batch_f64(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgicp_stats *stats, double *residual,
                                    double *ratio, int *status)
 {
-    if (!residual) { (void)noise_take(c); return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null"); }
+    if (!residual) { (void)noise_take(c); VarDistCall radii(c); return fail(c, PGICP_ERR_ARG, "pgicp_align_residual_batch: residual is null"); }
     return align_batch<double>(c, P, pr, T_out, stats, residual, ratio, status);
 }
 
@@ -699,6 +702,10 @@ int pgicp_arm_reading_noise_f32(pgicp_ctx *c, int P, const float *const *noise, 
 { return arm_reading_noise<float>(c, P, noise, stride, n, mem); }
 int pgicp_arm_reading_noise_f64(pgicp_ctx *c, int P, const double *const *noise, const int *stride, const int *n, int mem)
 { return arm_reading_noise<double>(c, P, noise, stride, n, mem); }
+int pgicp_arm_reading_radii_f32(pgicp_ctx *c, int P, const float *const *radii, const int *stride, const int *n, int mem)
+{ return arm_reading_radii<float>(c, P, radii, stride, n, mem); }
+int pgicp_arm_reading_radii_f64(pgicp_ctx *c, int P, const double *const *radii, const int *stride, const int *n, int mem)
+{ return arm_reading_radii<double>(c, P, radii, stride, n, mem); }
 int pgicp_last_noise_overlap(pgicp_ctx *c, int problem, double *overlap, int *n_elements)
 {
     if (!c) return PGICP_ERR_ARG;

@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "pgicp_voxel_grid_f32", "pgicp_voxel_grid_f64",
 ]
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
+# every symbol the companion header include/pgicp_vardist.h declares (checked by tests/test_var_dist_host.py)
+VARDIST_SYMBOLS = ("pgicp_arm_reading_radii_f32", "pgicp_arm_reading_radii_f64")
 # every symbol the companion header include/pgicp_noise.h declares (checked by tests/test_noise_overlap_host.py)
 NOISE_SYMBOLS = (
     "pgicp_simple_sensor_noise_f32", "pgicp_simple_sensor_noise_f64",
@@ -675,6 +677,16 @@ class Context:
         align_residual_batch / icp_pair call (one-shot).  noises: one entry per problem -- a 1-D numpy array (any positive
         stride: a row of a descriptor matrix), a 1-D torch CUDA tensor, or None (that problem has no noise); all in host
         memory or all on the device.  dtype: the element type of the ICP call."""
+        self._arm_rows("arm_reading_noise", noises, dtype)
+
+    def arm_reading_radii(self, radii, dtype):
+        """pgicp_arm_reading_radii_* (include/pgicp_vardist.h): KDTreeVarDistMatcher's search radius of every point of every
+        reading of the NEXT align / align_batch / align_residual_batch / icp_pair / match / partial_chain / partial_chain_batch
+        call (one-shot).  radii: one entry per problem, shaped as arm_reading_noise's rows (None: that problem has none);
+        +inf is a radius.  dtype: the element type of the consuming call."""
+        self._arm_rows("arm_reading_radii", radii, dtype)
+
+    def _arm_rows(self, what, noises, dtype):
         dtype = np.dtype(dtype)
         P = len(noises)
         ptrs, strides, counts, keep, mems = [], [], [], [], set()
@@ -684,17 +696,17 @@ class Context:
                 continue
             if _is_torch(v) and v.is_cuda:
                 if v.dim() != 1 or v.stride(0) < 1 or np.dtype(str(v.dtype).replace("torch.", "")) != dtype:
-                    raise ValueError("arm_reading_noise: a 1-D tensor of the call's dtype with a positive stride is needed")
+                    raise ValueError(what + ": a 1-D tensor of the call's dtype with a positive stride is needed")
                 ptrs.append(v.data_ptr()), strides.append(v.stride(0)), counts.append(v.shape[0]), mems.add(DEVICE)
             else:
                 v = np.asarray(v.cpu() if _is_torch(v) else v).astype(dtype, copy=False)
                 if v.ndim != 1 or v.strides[0] <= 0 or v.strides[0] % v.itemsize != 0:
-                    raise ValueError("arm_reading_noise: values must be 1-D with a positive stride of whole elements")
+                    raise ValueError(what + ": values must be 1-D with a positive stride of whole elements")
                 ptrs.append(v.ctypes.data), strides.append(v.strides[0] // v.itemsize), counts.append(v.shape[0]), mems.add(HOST)
             keep.append(v)
         if len(mems) > 1:
-            raise ValueError("arm_reading_noise: the rows must all be in host memory or all on the device")
-        fn = getattr(self.lib, "pgicp_arm_reading_noise" + self._sfx(dtype))
+            raise ValueError(what + ": the rows must all be in host memory or all on the device")
+        fn = getattr(self.lib, "pgicp_" + what + self._sfx(dtype))
         self._check(fn(self.h, C.c_int(P), (C.c_void_p * max(P, 1))(*ptrs), (C.c_int * max(P, 1))(*strides),
                        (C.c_int * max(P, 1))(*counts), C.c_int(mems.pop() if mems else HOST)))
         del keep
@@ -714,11 +726,13 @@ class Context:
             st["overlap_noise"], st["n_elements"] = ov, nb
 
     # ---- full ICP -----------------------------------------------------------
-    def align(self, map_id, reading, T_init, dtype=None, normals=None, noise=None):
+    def align(self, map_id, reading, T_init, dtype=None, normals=None, noise=None, radii=None):
         """normals: the reading's `normals` descriptor (a SurfaceNormalOutlierFilter in the chain needs it); noise: its
-        `simpleSensorNoise` row -- the stats then carry overlap_noise (getOverlap()'s sensor-noise branch) and n_elements"""
+        `simpleSensorNoise` row -- the stats then carry overlap_noise (getOverlap()'s sensor-noise branch) and n_elements;
+        radii: KDTreeVarDistMatcher's search radius of every reading point (arm_reading_radii)"""
         if normals is not None:
-            T, st = self.align_batch(map_id, [reading], [T_init], dtype=dtype, normals=[normals], noises=None if noise is None else [noise])
+            T, st = self.align_batch(map_id, [reading], [T_init], dtype=dtype, normals=[normals], noises=None if noise is None else [noise],
+                                     radiis=None if radii is None else [radii])
             return T[0], st[0]
         r = _Buf(reading, dtype)
         T_out = (C.c_double * 16)()
@@ -726,6 +740,8 @@ class Context:
         fn = getattr(self.lib, "pgicp_align" + self._sfx(r.dtype))
         if noise is not None:
             self.arm_reading_noise([noise], r.dtype)
+        if radii is not None:
+            self.arm_reading_radii([radii], r.dtype)
         self._check(fn(self.h, C.c_int(map_id), C.c_void_p(r.ptr), C.c_int(r.stride), C.c_int(r.n), C.c_int(r.mem),
                        _T16(T_init), T_out, C.byref(st)))
         sd = st.as_dict()
@@ -733,22 +749,25 @@ class Context:
             self._noise_into([sd], [noise])
         return np.array(T_out[:]).reshape(4, 4), sd
 
-    def align_residual_batch(self, map_ids, readings, T_inits, dtype=None, normals=None, raw_stats=False, noises=None):
+    def align_residual_batch(self, map_ids, readings, T_inits, dtype=None, normals=None, raw_stats=False, noises=None, radiis=None):
         """pgicp_align_residual_batch: the ICPs of a batch of loop-closure candidates and, fused, the residual check of every
         result (LoopCloser.hpp:98, 343-365).  Returns (T (P,4,4), stats, residual (P,), ratio (P,), status (P,)); never raises
         for a failed candidate (its residual is +inf)."""
         return self.align_batch(map_ids, readings, T_inits, dtype=dtype, raise_on_error=False, normals=normals, _residual=True, _raw_stats=raw_stats,
-                                noises=noises)
+                                noises=noises, radiis=radiis)
 
     def align_batch(self, map_ids, readings, T_inits, dtype=None, raise_on_error=True, normals=None, _residual=False, _raw_stats=False,
-                    noises=None):
+                    noises=None, radiis=None):
         """`_raw_stats`: the pgicp_stats records come back as ONE numpy record array (fields as in include/pgicp.h) instead of a
         list of dicts -- a batch of 512 loop-closure candidates does not need 512 dictionaries to fill 512 edge records.
         `noises`: one `simpleSensorNoise` row per reading (or None for a reading without): the stats dicts then carry
-        overlap_noise and n_elements (with `_raw_stats`: read them with last_noise_overlap(p))."""
+        overlap_noise and n_elements (with `_raw_stats`: read them with last_noise_overlap(p)).
+        `radiis`: one row of search radii per reading (or None for a reading without), as arm_reading_radii takes them."""
         P = len(readings)
         if noises is not None and len(noises) != P:
             raise ValueError("align_batch: one noise row (or None) per reading is needed")
+        if radiis is not None and len(radiis) != P:
+            raise ValueError("align_batch: one row of radii (or None) per reading is needed")
         if isinstance(map_ids, int):
             map_ids = [map_ids] * P
         bufs = _bufs(readings, dtype)
@@ -770,6 +789,8 @@ class Context:
         sa = np.zeros(P, dtype=_STATS_DTYPE)
         if noises is not None:
             self.arm_reading_noise(noises, bufs[0].dtype)
+        if radiis is not None:
+            self.arm_reading_radii(radiis, bufs[0].dtype)
         if _residual:
             res, ratio, rst = np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)
             fn = getattr(self.lib, "pgicp_align_residual_batch" + self._sfx(bufs[0].dtype))
@@ -796,7 +817,7 @@ class Context:
             return T_out, stats, res, ratio, rst
         return T_out, stats
 
-    def icp_pair(self, reading, ref_xyz, ref_nrm, T_init, dtype=None, noise=None):
+    def icp_pair(self, reading, ref_xyz, ref_nrm, T_init, dtype=None, noise=None, radii=None):
         r = _Buf(reading, dtype)
         x = _Buf(ref_xyz, r.dtype)
         nb = _Buf(ref_nrm, r.dtype)
@@ -806,6 +827,8 @@ class Context:
         fn = getattr(self.lib, "pgicp_icp_pair" + self._sfx(r.dtype))
         if noise is not None:
             self.arm_reading_noise([noise], r.dtype)
+        if radii is not None:
+            self.arm_reading_radii([radii], r.dtype)
         self._check(fn(self.h, C.c_void_p(r.ptr), C.c_int(r.stride), C.c_int(r.n), C.c_void_p(x.ptr), C.c_int(x.stride),
                        C.c_void_p(nb.ptr), C.c_int(nb.stride), C.c_int(x.n), C.c_int(r.mem), _T16(T_init), T_out,
                        C.byref(st)))
@@ -815,9 +838,12 @@ class Context:
         return np.array(T_out[:]).reshape(4, 4), sd
 
     # ---- stages -----------------------------------------------------------
-    def match(self, map_id, reading, T=None, dtype=None):
+    def match(self, map_id, reading, T=None, dtype=None, radii=None):
+        """radii: KDTreeVarDistMatcher's search radius of every reading point (arm_reading_radii)"""
         r = _Buf(reading, dtype)
         fn = getattr(self.lib, "pgicp_match" + self._sfx(r.dtype))
+        if radii is not None:
+            self.arm_reading_radii([radii], r.dtype)
         Tp = _T16(T) if T is not None else None
         k = max(1, int(self.params.knn))
         shape = (r.n,) if k == 1 else (r.n, k)              # knn entries per reading point
@@ -857,10 +883,12 @@ class Context:
                        C.c_void_p(ids.ctypes.data), C.c_void_p(w.ctypes.data), C.byref(ratio), C.byref(resid), sys_))
         return ratio.value, resid.value, np.array(sys_[:])
 
-    def partial_chain(self, map_id, reading, T=None, dtype=None):
+    def partial_chain(self, map_id, reading, T=None, dtype=None, radii=None):
         r = _Buf(reading, dtype)
         ratio, resid = C.c_double(0), C.c_double(0)
         fn = getattr(self.lib, "pgicp_partial_chain" + self._sfx(r.dtype))
+        if radii is not None:
+            self.arm_reading_radii([radii], r.dtype)
         self._check(fn(self.h, C.c_int(map_id), C.c_void_p(r.ptr), C.c_int(r.stride), C.c_int(r.n), C.c_int(r.mem),
                        _T16(T) if T is not None else None, C.byref(ratio), C.byref(resid)))
         return ratio.value, resid.value
@@ -880,9 +908,12 @@ class Context:
                        C.c_void_p(ss.ctypes.data), C.c_void_p(ds.ctypes.data), C.byref(ratio), C.byref(resid)))
         return ratio.value, resid.value
 
-    def partial_chain_batch(self, map_ids, readings, Ts, dtype=None, raise_on_error=True):
-        """(weightedPointUsedRatio, residual, status) arrays of a batch of (map, reading, T) in one device pass."""
+    def partial_chain_batch(self, map_ids, readings, Ts, dtype=None, raise_on_error=True, radiis=None):
+        """(weightedPointUsedRatio, residual, status) arrays of a batch of (map, reading, T) in one device pass.
+        radiis: one row of search radii per reading (or None for a reading without), as arm_reading_radii takes them."""
         P = len(readings)
+        if radiis is not None and len(radiis) != P:
+            raise ValueError("partial_chain_batch: one row of radii (or None) per reading is needed")
         bufs = [_Buf(r, dtype) for r in readings]
         pa = np.zeros(P, dtype=_PROBLEM_DTYPE)              # (numpy views of the records: see align_batch)
         pa["map_id"] = map_ids
@@ -893,6 +924,8 @@ class Context:
         pa["T_init"] = np.asarray(Ts, dtype=np.float64).reshape(P, 16)
         ratio, resid, status = np.zeros(P, dtype=np.float64), np.zeros(P, dtype=np.float64), np.zeros(P, dtype=np.int32)
         fn = getattr(self.lib, "pgicp_partial_chain_batch" + self._sfx(bufs[0].dtype))
+        if radiis is not None:
+            self.arm_reading_radii(radiis, bufs[0].dtype)
         rc = fn(self.h, C.c_int(P), C.c_void_p(pa.ctypes.data), C.c_void_p(ratio.ctypes.data), C.c_void_p(resid.ctypes.data),
                 C.c_void_p(status.ctypes.data))
         if raise_on_error or rc not in (OK, ERR_NO_MATCH):
