@@ -162,7 +162,7 @@ struct pgicp_ctx {
     } noise;
     // KDTreeVarDistMatcher's radii (include/pgicp_vardist.h, api_vardist.inc).  pgicp_arm_reading_radii copies the rows as the noise
     // rows are copied; the next matching call consumes them: `on` while that call runs -- its iterations cut the matcher's pairs
-    // into slot_cut / d2_cut (laid out as State::slot / ::d2) and everything downstream reads those (pair_slots / pair_d2);
+    // into slot_cut / d2_cut (laid out as State::slot / ::d2) and everything downstream reads those (IterBufs::pair_slot / ::pair_d2);
     // cut_live: the last call that matched was such a call (pgicp_debug_last_matches reads the cut pairs then).  Every buffer here
     // is allocated by an arm call or an armed call only.
     struct VarDist : ArmedRows {

@@ -5,6 +5,28 @@ void translation(const double *t3, double sign, double *T)
     T[3] = sign * t3[0]; T[7] = sign * t3[1]; T[11] = sign * t3[2];
 }
 
+// one reading against one map as a problem record (`T`: its first guess; none: the identity)
+static pgicp_problem one_problem(int map_id, const void *reading, int stride, int n, int mem, const double *T)
+{
+    pgicp_problem pr;
+    std::memset(&pr, 0, sizeof pr);
+    pr.map_id = map_id; pr.reading = reading; pr.stride = stride; pr.n = n; pr.mem = mem;
+    mat4_identity(pr.T_init);
+    if (T) std::memcpy(pr.T_init, T, sizeof pr.T_init);
+    return pr;
+}
+
+// A problem's pre-transform: its first guess, centred on the map's mean (`Tref`, optional: the transform back)
+template <typename T>
+void centred_pre(const MapHost<T> *M, const double *T_init, double *Tpre, double *Tref = nullptr)
+{
+    const double mean[3] = {(double)M->mean[0], (double)M->mean[1], (double)M->mean[2]};
+    double Tm_inv[16];
+    translation(mean, -1.0, Tm_inv);
+    if (Tref) translation(mean, +1.0, Tref);
+    mat4_mul(Tm_inv, T_init, Tpre);
+}
+
 struct BatchLayout {
     int P = 0;
     int max_n = 0;
@@ -225,167 +247,212 @@ static int probe_rings(const BatchLayout &L)
     return v > 0 ? v : L.rings_unseeded;
 }
 
-// VarTrimmedDistOutlierFilter: every active problem's ratio of this iteration into ProblemDev::vt_ratio (k_vartrim.inc)
+// Every device and pinned address the launches of an iteration name, and nothing else.  enqueue_iteration and its stages take their
+// addresses from this record only and one_iteration mixes the whole record into the key of a captured iteration: a buffer enters the
+// iteration by entering this record, so the key cannot fall behind the launches.  Plain data, zeroed with memset before it is filled
+// (padding hashes the same); built behind batch_begin, and again wherever a buffer it names may have been re-`ensure`d.
+// The seeding invariant (DESIGN.md, KDTreeVarDistMatcher): `slot` / `d2` / `none_r` are the matcher's own -- they seed its next pass
+// and are never written by the cut.  Everything behind the matcher reads `pair_slot` / `pair_d2`: the cut arrays when radii are armed.
 template <typename T>
-void var_trim_enqueue(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, int nA)
+struct IterBufs {
+    ProblemDev *probs; const MapDev<T> *maps; const T *rd, *rd_nrm; T *none_r;
+    int *slot; T *d2;                                   // the matcher's own
+    const int *pair_slot; const T *pair_d2;             // what the consumers read
+    int *active, *small, *qcount;                       // qcount: the queue counters (small + 16)
+    int2 *slow_list; T *slow_lb; int *slow_ring, *slow2; void *queue;
+    int *sel_tables; void *qtmp; double *partials; T *robust_dev;
+    void *vt_keys_a, *vt_keys_b;                        // VarTrimmed: the sort's two key lists
+    const int *order; const T *radii; const long long *radii_off; int *slot_cut; T *d2_cut;     // armed radii: the cut (order: the tail's too)
+    int *h_flag, *stamp_dev;
+};
+template <typename T>
+IterBufs<T> iter_bufs(pgicp_ctx *c, const BatchLayout &L)
 {
-    char *keys = (char *)c->vt_keys.p;
-    launch_var_trim<T>(c->stream, c->probs.as<ProblemDev>(), pair_d2<T>(c), c->active.as<int>(), nA, keys,
-                       keys + sizeof(T) * (size_t)L.total * L.knn, ch.vt_min, ch.vt_max, ch.vt_lambda);
+    State<T> &S = state<T>(c);
+    IterBufs<T> B;
+    std::memset(&B, 0, sizeof B);
+    B.probs = c->probs.as<ProblemDev>(); B.maps = S.d_maps.template as<MapDev<T>>(); B.rd = S.rd_sorted.template as<T>();
+    if (L.normals) B.rd_nrm = S.nrm_sorted.template as<T>();
+    B.none_r = S.none_r.template as<T>(); B.slot = S.slot.template as<int>(); B.d2 = S.d2.template as<T>();
+    B.pair_slot = B.slot; B.pair_d2 = B.d2;
+    B.active = c->active.as<int>(); B.small = c->small.as<int>(); B.qcount = B.small + 16;
+    B.slow_list = c->slow_list.as<int2>(); B.slow_lb = c->slow_lb.as<T>(); B.slow_ring = c->slow_ring.as<int>(); B.slow2 = c->slow2.as<int>();
+    B.queue = c->queue.p; B.sel_tables = c->sel_tables.as<int>(); B.qtmp = c->qtmp.p; B.partials = c->partials.as<double>();
+    if (c->prm.robust_fct != PGICP_ROBUST_NONE) B.robust_dev = c->robust_dev.as<T>();
+    if (c->vt_on) { B.vt_keys_a = c->vt_keys.p; B.vt_keys_b = (char *)c->vt_keys.p + sizeof(T) * (size_t)L.total * L.knn; }
+    B.order = c->order.as<int>();
+    if (c->vd.on) {
+        B.radii = c->vd.vals.template as<T>(); B.radii_off = c->vd.off_dev.as<long long>();
+        B.pair_slot = B.slot_cut = c->vd.slot_cut.as<int>(); B.pair_d2 = B.d2_cut = c->vd.d2_cut.as<T>();
+    }
+    B.h_flag = c->h_flag; B.stamp_dev = c->stamp_dev;
+    return B;
 }
 
+// The host-side switches of an iteration, computed once a call; the whole record is part of a captured iteration's key.
+struct IterPlan {
+    int topk, grid;     // KDTreeMatcher.knn > 1: the top-K matcher finds every pair exactly (no queue, no lazy resolution); the grid matcher (else brute force)
+    int vardist;        // KDTreeVarDistMatcher's radii armed (pgicp_vardist.h): the cut behind the matcher
+    int robust, gd_soft;        // RobustOutlierFilter; GenericDescriptorOutlierFilter, soft mode
+    int exact_all;      // this iteration must resolve every pair exactly
+    int n_pairs;        // pairs a problem has at most: what everything behind the matcher is launched over
+    int fold_solve;     // one problem: the solve kernel also does the bookkeeping of k_compact_active (one launch less per iteration)
+};
+template <typename T>
+IterPlan iter_plan(const pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch)
+{
+    IterPlan pl;
+    std::memset(&pl, 0, sizeof pl);
+    const bool robust = ch.robust.fct != 0, vardist = c->vd.on;
+    pl.topk = L.knn > 1; pl.grid = c->prm.matcher == PGICP_MATCHER_GRID; pl.vardist = vardist; pl.robust = robust;
+    // RobustOutlierFilter: nothing is trimmed -- the threshold the lazy path resolves queued queries up to is +inf;
+    // VarTrimmedDistOutlierFilter: its ratio is chosen over every distance; armed radii: the cut needs every pair under maxDist
+    pl.exact_all = robust || ch.var_trim || vardist;
+    pl.gd_soft = ch.gd_mode == PGICP_DESC_FILTER_SOFT;
+    pl.n_pairs = pl.topk ? L.max_pairs() : L.max_n; pl.fold_solve = L.P == 1 && !pl.topk;
+    return pl;
+}
+
+// KDTreeVarDistMatcher's cut, behind a matcher pass that resolved every pair of the active problems exactly
+template <typename T>
+void cut_pairs(pgicp_ctx *c, const IterBufs<T> &B, int nA, int n_pairs)
+{
+    launch_vardist_cut<T>(c->stream, B.probs, B.active, nA, n_pairs, B.slot, B.d2, B.order, B.radii, B.radii_off, B.slot_cut, B.d2_cut);
+}
+
+// the queue a fast pass left: the medium pass (`med`), then the wave-per-query pass
+template <typename T>
+void resolve_queue(pgicp_ctx *c, const ChainDev<T> &ch, const IterBufs<T> &B, bool med, int use_seed, int exact_all)
+{
+    if (med) launch_knn_med<T>(c->stream, B.probs, B.maps, B.rd, B.slot, B.d2, ch, B.qcount, B.slow_list, B.slow_lb, B.slow_ring, B.slow2,
+                               c->med_rings, (use_seed == 1 || use_seed == 3) ? 1 : 0, B.none_r);
+    launch_knn_slow<T>(c->stream, B.probs, B.maps, B.rd, B.slot, B.d2, ch, B.qcount, B.slow_list, B.slow_lb, B.slow2, exact_all, B.none_r);
+}
+
+// The matcher stage: the top-K launch, or the fast pass, the first selection, the opens, the medium and slow resolution and the
+// re-selection.  `stage`: see enqueue_iteration.  Returns launch_knn_topk's status (0 otherwise).
+// `partial` (run_partial: the matcher's public output, no outlier filter behind it): the fast pass clears the queue counters itself
+// and leaves them for pgicp_debug_counters, every queued query is resolved exactly at once (no medium pass), nothing is selected.
+// use_seed: 0 no correspondences to start from, 1 the previous iteration's (with its threshold as search cap and its proven-empty
+// radii), 2 seeds from outside (pgicp_partial_chain_seeded): candidates only, no history, 3 the same with a search cap from
+// the threshold of the context's previous call (BorrowSpec::capped)
+template <typename T>
+int matcher_stage(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, const IterBufs<T> &B, const IterPlan &pl, int nA,
+                  long long units, long long problems, int use_seed, int stage, bool partial = false)
+{
+    if (pl.topk) {
+        ProfScope ps(c, PGICP_PROF_KNN_GRID, units, problems);
+        return launch_knn_topk<T>(c->stream, B.probs, B.maps, B.rd, B.slot, B.d2, ch, nA, L.max_n, B.active);
+    }
+    if (stage != 2) {
+        ProfScope ps(c, pl.grid ? PGICP_PROF_KNN_GRID : PGICP_PROF_KNN_BRUTE, units, problems);
+        if (!partial && use_seed != 1 && pl.grid) ps.also(PGICP_PROF_KNN_GRID_UNSEEDED);
+        launch_knn<T>(c->stream, pl.grid ? PGICP_MATCHER_GRID : PGICP_MATCHER_BRUTE, B.probs, B.maps, B.rd, B.slot, B.d2, ch, nA, L.max_n, use_seed,
+                      B.qcount, B.slow_list, B.slow_lb, B.slow_ring, use_seed == 1 ? L.rings_seeded : use_seed == 3 ? probe_rings(L) : L.rings_unseeded,
+                      B.active, B.none_r, L.P, B.queue, (partial || !c->seg_clean) ? 1 : 0, L.table_kinds);
+        c->counters_clean = 0;                 // (partial, pgicp_debug_counters: this pass's queue counters, not the copy batch_begin cleared)
+        if (partial) {
+            c->seg_clean = 0;
+            if (pl.grid) resolve_queue<T>(c, ch, B, false, use_seed, 1);
+            return 0;
+        }
+    }
+    if (stage == 1) return 0;
+    {
+        ProfScope ps(c, PGICP_PROF_TRIM, units, problems);
+        // (with the grid matcher this selection also clears the matcher's segmented queue counters for the next iteration; under
+        //  VarTrimmed that -- and far_mode -- is all it is for: k_robust_open and the second == 2 selection overwrite its threshold.
+        //  A cheaper counter clear would spare one selection an iteration there; the TrimmedDist path is left as it is)
+        // (every selection but a run's first starts from the last one's result, ProblemDev::qraw; a run's first from the previous
+        //  call's, ::qhint, if there is one)
+        launch_trim_select<T>(c->stream, B.probs, B.d2, ch, nA, L.max_n, 0, B.active, B.sel_tables, B.qtmp, pl.grid ? (int *)B.queue : nullptr,
+                              pl.exact_all ? 0 : (use_seed == 1 || c->sel_guess_first));
+        c->seg_clean = pl.grid ? 1 : 0;
+    }
+    if (pl.exact_all) launch_robust_open(c->stream, B.probs, B.active, nA);
+    // GenericDescriptorOutlierFilter, soft mode: its maximum covers every pair with a neighbour -- the same, and (no Robust /
+    // VarTrimmed filter to set it) the second selection below must then restore the iteration's threshold
+    if (pl.gd_soft && !pl.exact_all && pl.grid) launch_gd_open(c->stream, B.probs, B.active, nA);
+    if (!pl.grid) return 0;
+    // lazy resolution: only queued queries whose lower bound is within the threshold just selected (an upper bound of the final
+    // one) are searched exactly; then the threshold is re-selected if anything changed.  Kept pairs / threshold / n_finite stay exact.
+    {
+        ProfScope ps(c, PGICP_PROF_KNN_SLOW, units, problems);
+        resolve_queue<T>(c, ch, B, true, use_seed, 0);
+        static const bool each_pass = std::getenv("PGICP_PHASE_EACH_PASS") != nullptr;     // diagnostics builds only
+        if (each_pass) {
+            unsigned long long ph[48];
+            (void)stream_sync(c);
+            (void)knn_xcc_report(use_seed, 1);
+            if (knn_phase_read(ph, 1) == 0)
+                std::fprintf(stderr, "    pass (seeded %d): wave-per-query kernel entries=%llu, longest wave %llu, longest entry %llu cycles; per entry: walk %.0f\n",
+                             use_seed, ph[46], ph[44], ph[45], (double)ph[36] / (double)std::max<unsigned long long>(1ULL, ph[46]));
+        }
+    }
+    ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
+    if (!pl.exact_all) launch_trim_select<T>(c->stream, B.probs, B.d2, ch, nA, L.max_n, 1, B.active, B.sel_tables, B.qtmp, nullptr, 1);
+    return 0;
+}
+
+// Everything behind the matcher, for both matchers: the armed-radii cut, the VarTrimmed ratio and selection, the robust scale, the
+// soft descriptor maximum, the reduce and the solve.  Every pair is exact here.
+// One ProfScope is one counted entry of profile(): the top-K path has ONE PGICP_PROF_TRIM scope round the parts before the reduce (its
+// only selection is among them, with the iteration's units); the grid path one for each part that runs, without units.
+template <typename T>
+void pairs_stage(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, const IterBufs<T> &B, const IterPlan &pl, int nA,
+                 long long units, long long problems, int use_seed, bool with_solve)
+{
+    auto select = [&](int second, int guess) {
+        launch_trim_select<T>(c->stream, B.probs, B.pair_d2, ch, nA, pl.n_pairs, second, B.active, B.sel_tables, B.qtmp, nullptr, guess);
+    };
+    auto part = [&](bool on, auto body) {
+        if (!on) return;
+        if (pl.topk) { body(); return; }
+        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
+        body();
+    };
+    {
+        std::optional<ProfScope> all;
+        if (pl.topk) all.emplace(c, PGICP_PROF_TRIM, units, problems);
+        part(pl.vardist, [&] {
+            cut_pairs<T>(c, B, nA, pl.n_pairs);
+            // the grid path, no Robust or VarTrimmed filter to do it below: the quantile filter's selection over the cut distances (a
+            // first selection without a guess, as RobustOutlierFilter's own), and the search cap lifted again for the next matcher
+            // pass: a threshold over cut distances says nothing about the search
+            if (!pl.topk && !pl.robust && !ch.var_trim) { select(0, 0); launch_vardist_reset(c->stream, B.probs, B.active, nA); }
+        });
+        part(ch.var_trim, [&] {                 // the ratio of this iteration, then the selection at that ratio
+            launch_var_trim<T>(c->stream, B.probs, B.pair_d2, B.active, nA, B.vt_keys_a, B.vt_keys_b, ch.vt_min, ch.vt_max, ch.vt_lambda);
+            select(2, 0);
+        });
+        part(pl.topk && !ch.var_trim, [&] { select(0, use_seed); });     // (top-K: the iteration's one selection, over the knn * N distances)
+        // the scale of this iteration from the distances: median, absolute deviations, their median
+        part(pl.robust, [&] { launch_robust_scale<T>(c->stream, B.probs, B.pair_d2, B.robust_dev, ch, nA, pl.n_pairs, B.active, B.sel_tables, B.qtmp); });
+        part(pl.gd_soft, [&] { launch_gd_max<T>(c->stream, B.probs, B.maps, B.pair_slot, nA, pl.n_pairs, B.active); });      // the soft maximum of this iteration
+    }
+    {
+        ProfScope ps(c, PGICP_PROF_REDUCE, units, problems);
+        launch_reduce<T>(c->stream, B.probs, B.maps, B.rd, B.rd_nrm, B.pair_slot, B.pair_d2, B.partials, nA, pl.n_pairs, B.active, ch);
+    }
+    if (!with_solve) return;
+    ProfScope ps(c, PGICP_PROF_SOLVE, units, problems);
+    const bool fold = pl.fold_solve;
+    launch_solve<T>(c->stream, B.probs, B.partials, ch, B.small, nA, pl.n_pairs, B.active, fold ? B.h_flag : nullptr, fold ? B.stamp_dev : nullptr,
+                    fold ? B.qcount : nullptr);
+    if (!fold) launch_compact_active(c->stream, B.probs, L.P, B.active, B.h_flag, B.stamp_dev, B.qcount);
+}
+
+// One iteration of the problems still iterating: `active` lists them first (k_compact_active), act_probs of them.
 // `stage`: 0 the whole iteration; 1 only its matcher pass (fast kernel + queue compaction); 2 everything but that pass -- the
 // driver of a single problem enqueues the NEXT iteration's matcher pass before it knows whether there is a next iteration
 // (align_batch: every kernel leaves at once for a problem that is done), so that the device does not wait for the host's
 // look at the convergence flag: a round trip per iteration, and at one problem per launch the matcher pass is all latency.
 template <typename T>
-void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, bool with_solve, long long act_units,
-                       long long act_probs, int use_seed, int stage = 0)
+void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, const IterBufs<T> &B, const IterPlan &pl, bool with_solve,
+                       long long act_units, long long act_probs, int use_seed, int stage = 0)
 {
-    // only the problems still iterating are launched: `active` lists them first (k_compact_active)
-    const int nA = (int)act_probs;
-    const int *active = c->active.as<int>();
-    State<T> &S = state<T>(c);
-    const MapDev<T> *maps = S.d_maps.template as<MapDev<T>>();
-    ProblemDev *probs = c->probs.as<ProblemDev>();
-    const T *rd_nrm = L.normals ? S.nrm_sorted.template as<T>() : nullptr;
-    // KDTreeVarDistMatcher's radii armed (pgicp_vardist.h): the matcher resolves every pair exactly under maxDist into its own
-    // arrays, which seed its next pass and stay as it left them; k_vardist_cut copies the pairs within their point's radius into
-    // the cut arrays, and everything behind the matcher reads those (`slot` / `d2` below)
-    const bool vardist = c->vd.on;
-    const int *slot = pair_slots<T>(c);
-    const T *d2 = pair_d2<T>(c);
-    if (L.knn > 1) {
-        // KDTreeMatcher.knn > 1: the top-K matcher finds every pair exactly (no queue, no lazy resolution), one selection
-        // over the knn * N distances, the minimiser over the knn * N pairs
-        {
-            ProfScope ps(c, PGICP_PROF_KNN_GRID, act_units, act_probs);
-            (void)launch_knn_topk<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(), S.d2.template as<T>(), ch, nA, L.max_n, active);
-        }
-        {
-            ProfScope ps(c, PGICP_PROF_TRIM, act_units, act_probs);
-            if (vardist) vardist_cut_enqueue<T>(c, nA, L.max_pairs());
-            if (ch.var_trim) {
-                var_trim_enqueue<T>(c, L, ch, nA);
-                launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_pairs(), 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
-            } else {
-                launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_pairs(), 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, use_seed);
-            }
-            if (ch.gd_mode == PGICP_DESC_FILTER_SOFT) launch_gd_max<T>(c->stream, probs, maps, slot, nA, L.max_pairs(), active);
-        }
-        {
-            ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);
-            launch_reduce<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), rd_nrm, slot, d2,
-                             c->partials.as<double>(), nA, L.max_pairs(), active, ch);
-        }
-        if (with_solve) {
-            ProfScope ps(c, PGICP_PROF_SOLVE, act_units, act_probs);
-            launch_solve<T>(c->stream, probs, c->partials.as<double>(), ch, c->small.as<int>(), nA, L.max_pairs(), active, nullptr, nullptr, nullptr);
-            launch_compact_active(c->stream, probs, L.P, c->active.as<int>(), c->h_flag, c->stamp_dev, c->small.as<int>() + 16);
-        }
-        return;
-    }
-    if (stage != 2) {
-        ProfScope ps(c, c->prm.matcher == PGICP_MATCHER_BRUTE ? PGICP_PROF_KNN_BRUTE : PGICP_PROF_KNN_GRID, act_units, act_probs);
-        // use_seed: 0 no correspondences to start from, 1 the previous iteration's (with its threshold as search cap and its proven-empty
-        // radii), 2 seeds from outside (pgicp_partial_chain_seeded): candidates only, no history, 3 the same with a search cap from
-        // the threshold of the context's previous call (BorrowSpec::capped)
-        if (use_seed != 1 && c->prm.matcher == PGICP_MATCHER_GRID) ps.also(PGICP_PROF_KNN_GRID_UNSEEDED);
-        launch_knn<T>(c->stream, c->prm.matcher, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(),
-                      S.d2.template as<T>(), ch, nA, L.max_n, use_seed, c->small.as<int>() + 16, c->slow_list.as<int2>(),
-                      c->slow_lb.as<T>(), c->slow_ring.as<int>(), use_seed == 1 ? L.rings_seeded : use_seed == 3 ? probe_rings(L) : L.rings_unseeded, active, S.none_r.template as<T>(),
-                      L.P, c->queue.p, c->seg_clean ? 0 : 1, L.table_kinds);
-        c->counters_clean = 0;
-    }
-    if (stage == 1) return;
-    {
-        ProfScope ps(c, PGICP_PROF_TRIM, act_units, act_probs);
-        // (with the grid matcher this selection also clears the matcher's segmented queue counters for the next iteration; under
-        //  VarTrimmed that -- and far_mode -- is all it is for: k_robust_open and the second == 2 selection overwrite its threshold.
-        //  A cheaper counter clear would spare one selection an iteration there; the TrimmedDist path is left as it is)
-        const bool grid = c->prm.matcher == PGICP_MATCHER_GRID;
-        launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 0, active, c->sel_tables.as<int>(), c->qtmp.p,
-                              grid ? (int *)c->queue.p : nullptr, (ch.robust.fct != 0 || ch.var_trim || vardist) ? 0 : (use_seed == 1 || c->sel_guess_first));      // (every selection but a run's first starts from the last one's result,
-                                                                                          // ProblemDev::qraw; a run's first from the previous call's, ::qhint, if there is one)
-        c->seg_clean = grid ? 1 : 0;
-    }
-    const bool robust = ch.robust.fct != 0;
-    // RobustOutlierFilter: nothing is trimmed -- the threshold the lazy path resolves queued queries up to is +inf from here on;
-    // VarTrimmedDistOutlierFilter: its ratio is chosen over every distance -- the same
-    // KDTreeVarDistMatcher's radii: the cut needs every pair under maxDist -- the same
-    if (robust || ch.var_trim || vardist) launch_robust_open(c->stream, probs, active, nA);
-    // GenericDescriptorOutlierFilter, soft mode: its maximum covers every pair with a neighbour -- the same, and (no Robust /
-    // VarTrimmed filter to set it) the second selection below must then restore the iteration's threshold
-    const bool gd_soft = ch.gd_mode == PGICP_DESC_FILTER_SOFT;
-    if (gd_soft && !robust && !ch.var_trim && !vardist && c->prm.matcher == PGICP_MATCHER_GRID) launch_gd_open(c->stream, probs, active, nA);
-    if (c->prm.matcher == PGICP_MATCHER_GRID) {
-        // lazy resolution: only queued queries whose lower bound is within the threshold just
-        // selected (an upper bound of the final one) are searched exactly; then the threshold
-        // is re-selected if anything changed.  Kept pairs / threshold / n_finite stay exact.
-        {
-            ProfScope ps(c, PGICP_PROF_KNN_SLOW, act_units, act_probs);
-            launch_knn_med<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(), S.d2.template as<T>(),
-                              ch, c->small.as<int>() + 16, c->slow_list.as<int2>(), c->slow_lb.as<T>(), c->slow_ring.as<int>(),
-                              c->slow2.as<int>(), c->med_rings, (use_seed == 1 || use_seed == 3) ? 1 : 0, S.none_r.template as<T>());
-            launch_knn_slow<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(),
-                               S.d2.template as<T>(), ch, c->small.as<int>() + 16, c->slow_list.as<int2>(), c->slow_lb.as<T>(),
-                               c->slow2.as<int>(), 0, S.none_r.template as<T>());
-            static const bool each_pass = std::getenv("PGICP_PHASE_EACH_PASS") != nullptr;     // diagnostics builds only
-            if (each_pass) {
-                unsigned long long ph[48];
-                (void)stream_sync(c);
-                (void)knn_xcc_report(use_seed, 1);
-                if (knn_phase_read(ph, 1) == 0)
-                    std::fprintf(stderr, "    pass (seeded %d): wave-per-query kernel entries=%llu, longest wave %llu, longest entry %llu cycles; per entry: walk %.0f\n",
-                                 use_seed, ph[46], ph[44], ph[45], (double)ph[36] / (double)std::max<unsigned long long>(1ULL, ph[46]));
-            }
-        }
-        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        if (!robust && !ch.var_trim && !vardist) launch_trim_select<T>(c->stream, probs, S.d2.template as<T>(), ch, nA, L.max_n, 1, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 1);
-    }
-    if (vardist) {
-        // every pair is exact now: the cut, then -- no Robust or VarTrimmed filter to do it below -- the quantile filter's selection
-        // over the cut distances (a first selection without a guess, as RobustOutlierFilter's own), and the search cap lifted again
-        // for the next matcher pass: a threshold over cut distances says nothing about the search
-        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        vardist_cut_enqueue<T>(c, nA, L.max_n);
-        if (!robust && !ch.var_trim) {
-            launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_n, 0, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
-            launch_vardist_reset(c->stream, probs, active, nA);
-        }
-    }
-    if (ch.var_trim) {
-        // every distance is exact now: the ratio of this iteration, then the selection at that ratio
-        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        var_trim_enqueue<T>(c, L, ch, nA);
-        launch_trim_select<T>(c->stream, probs, d2, ch, nA, L.max_n, 2, active, c->sel_tables.as<int>(), c->qtmp.p, nullptr, 0);
-    }
-    if (robust) {
-        // the scale of this iteration from the (now exact) distances: median, absolute deviations, their median
-        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        launch_robust_scale<T>(c->stream, probs, d2, c->robust_dev.as<T>(), ch, nA, L.max_n, active, c->sel_tables.as<int>(), c->qtmp.p);
-    }
-    if (gd_soft) {
-        // every pair is exact now: the soft maximum of this iteration
-        ProfScope ps(c, PGICP_PROF_TRIM, 0, 0);
-        launch_gd_max<T>(c->stream, probs, maps, slot, nA, L.max_n, active);
-    }
-    {
-        ProfScope ps(c, PGICP_PROF_REDUCE, act_units, act_probs);
-        launch_reduce<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), rd_nrm, slot, d2,
-                         c->partials.as<double>(), nA, L.max_n, active, ch);
-    }
-    if (with_solve) {
-        ProfScope ps(c, PGICP_PROF_SOLVE, act_units, act_probs);
-        if (L.P == 1) {
-            // one problem: the solve kernel also does the bookkeeping of k_compact_active (one launch less per iteration)
-            launch_solve<T>(c->stream, probs, c->partials.as<double>(), ch, c->small.as<int>(), nA, L.max_n, active, c->h_flag, c->stamp_dev,
-                            c->small.as<int>() + 16);
-        } else {
-            launch_solve<T>(c->stream, probs, c->partials.as<double>(), ch, c->small.as<int>(), nA, L.max_n, active, nullptr, nullptr, nullptr);
-            launch_compact_active(c->stream, probs, L.P, c->active.as<int>(), c->h_flag, c->stamp_dev, c->small.as<int>() + 16);
-        }
-    }
+    (void)matcher_stage<T>(c, L, ch, B, pl, (int)act_probs, act_units, act_probs, use_seed, stage);
+    if (stage != 1) pairs_stage<T>(c, L, ch, B, pl, (int)act_probs, act_units, act_probs, use_seed, with_solve);
 }
 
 // One ICP iteration.  For a batch of a few problems (a streamed scan, a SLAM front end) -- a chain of ten small launches --
@@ -396,31 +463,24 @@ void enqueue_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch
 // the GPU what ten launches cost there, and the workloads are not bound by launching (GPU 52 % busy in the SLAM run; the
 // rest is host logic between ICP calls).
 template <typename T>
-void one_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, bool with_solve, long long act_units,
-                   long long act_probs, int use_seed, int stage = 0)
+void one_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, const IterBufs<T> &B, const IterPlan &pl, bool with_solve,
+                   long long act_units, long long act_probs, int use_seed, int stage = 0)
 {
-    State<T> &S = state<T>(c);
-    if (stage == 1) { enqueue_iteration<T>(c, L, ch, with_solve, act_units, act_probs, use_seed, 1); return; }     // (the matcher pass ahead of its iteration)
+    if (stage == 1) { enqueue_iteration<T>(c, L, ch, B, pl, with_solve, act_units, act_probs, use_seed, 1); return; }     // (the matcher pass ahead of its iteration)
     const bool want_graph = stage == 0 && L.P <= c->graph_max_problems && !c->prof_on && c->graph_failures < 3;
     bool done = false;
     if (want_graph) {
-        // FNV-1a over the argument values: shapes, switches, chain parameters, and every buffer the launches name
+        // FNV-1a over the argument values: shapes, chain parameters, the plan's switches, and the record of every address the launches name
         unsigned long long key = 1469598103934665603ULL;
         auto mix = [&key](const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t i = 0; i < n; i++) { key ^= b[i]; key *= 1099511628211ULL; } };
         // (sel_guess_first decides the `guess` argument of the iteration's first selection launch: the hinted and the
         //  unhinted first iteration are different graphs)
-        const int shape[13] = {(int)sizeof(T), L.P, (int)act_probs, L.max_n, use_seed, with_solve ? 1 : 0, c->med_rings, L.rings_seeded,
-                               L.rings_unseeded, c->prm.matcher, c->seg_clean, c->sel_guess_first, c->sel_hints_on};
+        const int shape[14] = {(int)sizeof(T), L.P, (int)act_probs, L.max_n, use_seed, with_solve ? 1 : 0, c->med_rings, L.rings_seeded,
+                               L.rings_unseeded, c->prm.matcher, c->seg_clean, c->sel_guess_first, c->sel_hints_on, L.table_kinds};
         mix(shape, sizeof shape);
         mix(&ch, sizeof ch);
-        const void *bufs[] = {c->probs.p, S.d_maps.p, S.rd_sorted.p, S.slot.p, S.d2.p, S.none_r.p, c->small.p, c->slow_list.p, c->slow_lb.p,
-                              c->slow_ring.p, c->slow2.p, c->active.p, c->queue.p, c->sel_tables.p, c->qtmp.p, c->partials.p, c->h_flag, c->stamp_dev,
-                              c->robust_dev.p, L.normals ? S.nrm_sorted.p : nullptr, c->vt_on ? c->vt_keys.p : nullptr,
-                              (const void *)(size_t)(c->vt_on ? L.total : 0),     // (VarTrimmed: the second key list starts L.total pairs in)
-                              // (armed radii: the cut's arrays, rows and the reading order it gathers them through)
-                              c->vd.on ? c->vd.slot_cut.p : nullptr, c->vd.on ? c->vd.d2_cut.p : nullptr, c->vd.on ? c->vd.vals.p : nullptr,
-                              c->vd.on ? c->vd.off_dev.p : nullptr, c->vd.on ? c->order.p : nullptr};
-        mix(bufs, sizeof bufs);
+        mix(&pl, sizeof pl);
+        mix(&B, sizeof B);
         pgicp_ctx::IterGraph *g = nullptr;
         for (auto &e : c->iter_graphs) if (e.exec && e.key == key) { g = &e; break; }
         if (!g) {
@@ -428,7 +488,7 @@ void one_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, bo
             hipGraphExec_t exec = nullptr;
             bool ok = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
             if (ok) {
-                enqueue_iteration<T>(c, L, ch, with_solve, act_units, act_probs, use_seed);
+                enqueue_iteration<T>(c, L, ch, B, pl, with_solve, act_units, act_probs, use_seed);
                 ok = hipStreamEndCapture(c->stream, &graph) == hipSuccess && graph != nullptr;
             }
             if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
@@ -453,9 +513,9 @@ void one_iteration(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, bo
             else { (void)hipGetLastError(); c->graph_failures++; }
         }
     }
-    if (!done) enqueue_iteration<T>(c, L, ch, with_solve, act_units, act_probs, use_seed, stage);
+    if (!done) enqueue_iteration<T>(c, L, ch, B, pl, with_solve, act_units, act_probs, use_seed, stage);
     c->counters_clean = with_solve ? 1 : 0;      // k_compact_active clears the matcher's queue counters
-    c->seg_clean = c->prm.matcher == PGICP_MATCHER_GRID ? 1 : 0;     // (a replayed graph did not pass through enqueue_iteration)
+    c->seg_clean = pl.grid ? 1 : 0;    // (a replayed graph did not pass through enqueue_iteration)
     if (with_solve) ++c->flag_stamp;
 }
 
@@ -465,19 +525,26 @@ static bool hints_cover_first(const std::vector<ProblemDev> &hp)
     for (const ProblemDev &D : hp) if (!(D.qhint[0][0] > 0.0)) return false;
     return !hp.empty();
 }
-// what this call's selections found becomes the next call's hints (problem by problem; a call with another number of problems starts over)
-static void hints_store(pgicp_ctx *c, int kind, const std::vector<ProblemDev> &hp)
+// The end of a batched call: the problem records into pinned memory, the wait for the stream, the records into `hp`.  `behind`: what
+// the call still enqueues between the copy and the wait (align_batch's residual pass overwrites what the stats report).  Then
+// what this call's selections found becomes the next call's hints of its kind (problem by problem; a call with another number of
+// problems starts over), and pgicp_last_var_trim_ratio's answers the tuned ratio of every problem's last iteration (the chain has no
+// VarTrimmed filter: none).
+template <typename F = int (*)()>
+int batch_download(pgicp_ctx *c, int P, std::vector<ProblemDev> &hp, int hint_kind, F behind = [] { return (int)PGICP_OK; })
 {
-    std::vector<pgicp_ctx::SelHint> &H = c->sel_hints[kind];
+    { const int pst = pinned_ensure(c, &c->h_down, &c->h_down_cap, sizeof(ProblemDev) * (size_t)P); if (pst) return pst; }
+    HIPC(c, hipMemcpyAsync(c->h_down, c->probs.p, sizeof(ProblemDev) * P, hipMemcpyDeviceToHost, c->stream));
+    XFER(c, behind());
+    HIPC(c, stream_sync(c));
+    HIPC(c, hipGetLastError());
+    std::memcpy(hp.data(), c->h_down, sizeof(ProblemDev) * (size_t)P);
+    std::vector<pgicp_ctx::SelHint> &H = c->sel_hints[hint_kind];
     H.resize(hp.size());
     for (size_t p = 0; p < hp.size(); p++) std::memcpy(H[p].q, hp[p].qrec, sizeof H[p].q);
-}
-
-// pgicp_last_var_trim_ratio: the tuned ratio of every problem's last iteration (the chain has no VarTrimmed filter: none)
-static void var_trim_record(pgicp_ctx *c, const std::vector<ProblemDev> &hp)
-{
     c->vt_last.clear();
     if (c->vt_on) for (const ProblemDev &D : hp) c->vt_last.push_back(D.vt_ratio);
+    return PGICP_OK;
 }
 
 // number of finished problems after the iteration just enqueued (its k_compact_active carries c->flag_stamp)
@@ -533,20 +600,15 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
     }
     static const bool host_timing = std::getenv("PGICP_HOST_TIMING") != nullptr;      // diagnostics
     const auto ht0 = std::chrono::steady_clock::now();
-    int st = batch_begin<T>(c, P, pr, [&](int p, double *Tpre) {
-        MapHost<T> *M = get_map<T>(c, pr[p].map_id);
-        double mean[3] = {(double)M->mean[0], (double)M->mean[1], (double)M->mean[2]};
-        double Tm_inv[16];
-        translation(mean, -1.0, Tm_inv);
-        translation(mean, +1.0, Tref[p].data());
-        mat4_mul(Tm_inv, pr[p].T_init, Tpre);
-    }, L, hp, 0);
+    int st = batch_begin<T>(c, P, pr, [&](int p, double *Tpre) { centred_pre(get_map<T>(c, pr[p].map_id), pr[p].T_init, Tpre, Tref[p].data()); }, L, hp, 0);
     if (st) return st;
+    const IterBufs<T> B = iter_bufs<T>(c, L);
     const bool hint_first = hints_cover_first(hp);
     long long total_m = 0;                       // (profile only) reference points over the batch's problems
     if (c->prof_on) for (int p = 0; p < P; p++) total_m += get_map<T>(c, pr[p].map_id)->m;
     const auto ht1 = std::chrono::steady_clock::now();
     const ChainDev<T> ch = chain_of<T>(c, prm);
+    const IterPlan pl = iter_plan(c, L, ch);
     const int every = std::max(1, prm.check_every);
     // active-problem accounting for the profile: exact when check_every == 1 and all
     // readings have the same size (the benchmark's case), an upper bound otherwise
@@ -567,13 +629,13 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         c->prof_next_m = total_m * act_p / P;
         if (!(ahead && ahead_mode == 2)) {
             c->sel_guess_first = it == 0 && hint_first ? 1 : 0;
-            one_iteration<T>(c, L, ch, true, L.total * act_p / P, act_p, it > 0 ? 1 : 0, ahead ? 2 : 0);
+            one_iteration<T>(c, L, ch, B, pl, true, L.total * act_p / P, act_p, it > 0 ? 1 : 0, ahead ? 2 : 0);
             c->sel_guess_first = 0;
         }
         ahead = false;
         if (ahead_mode && it + 1 < prm.max_iters) {
             if (c->prof_on) { std::lock_guard<std::mutex> lock(c->prof_m); ahead_events = c->prof_events.size(); }
-            one_iteration<T>(c, L, ch, true, L.total, 1, 1, ahead_mode == 1 ? 1 : 0);
+            one_iteration<T>(c, L, ch, B, pl, true, L.total, 1, 1, ahead_mode == 1 ? 1 : 0);
             ahead = true;
         }
         if ((it + 1) % every == 0 || it + 1 == prm.max_iters) {
@@ -605,9 +667,8 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         HIPC(c, N.out.ensure(cnt_off + sizeof(int) * (size_t)P));
         HIPC(c, N.dist.ensure(sizeof(T) * (size_t)L.total * L.knn));
         HIPC(c, hipMemsetAsync((char *)N.out.p + cnt_off, 0, sizeof(int) * (size_t)P, c->stream));
-        launch_noise_overlap<T>(c->stream, c->probs.as<ProblemDev>(), S.d_maps.template as<MapDev<T>>(), L.normals ? S.nrm_sorted.template as<T>() : nullptr,
-                                pair_slots<T>(c), pair_d2<T>(c), c->order.as<int>(), N.vals.template as<T>(),
-                                N.off_dev.as<long long>(), N.dist.template as<T>(), c->partials.as<double>(), N.out.as<double>(),
+        launch_noise_overlap<T>(c->stream, B.probs, B.maps, B.rd_nrm, B.pair_slot, B.pair_d2, B.order, N.vals.template as<T>(),
+                                N.off_dev.as<long long>(), N.dist.template as<T>(), B.partials, N.out.as<double>(),
                                 (int *)((char *)N.out.p + cnt_off), P, L.max_pairs(), ch);
         nres.resize(cnt_off + sizeof(int) * (size_t)P);
         XFER(c, d2h(c, nres.data(), N.out.p, nres.size()));
@@ -615,35 +676,27 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
     const bool with_cov = prm.error_minimizer != PGICP_MINIMIZER_POINT_TO_POINT;      // (PointToPoint: the base class's zeros; its WithCov form: the same Censi estimate)
     if (with_cov) {
         ProfScope ps(c, PGICP_PROF_COV, L.total, P);
-        launch_cov<T>(c->stream, c->probs.as<ProblemDev>(), S.d_maps.template as<MapDev<T>>(), S.rd_sorted.template as<T>(),
-                      L.normals ? S.nrm_sorted.template as<T>() : nullptr, pair_slots<T>(c), pair_d2<T>(c),
-                      c->partials.as<double>(), c->sums.as<double>(), P, L.max_pairs(), ch);
+        launch_cov<T>(c->stream, B.probs, B.maps, B.rd, B.rd_nrm, B.pair_slot, B.pair_d2, B.partials, c->sums.as<double>(), P, L.max_pairs(), ch);
     } else HIPC(c, hipMemsetAsync(c->sums.p, 0, sizeof(double) * (size_t)P * kCovTerms, c->stream));
-    std::vector<double> cs((size_t)P * kCovTerms);
-    { const int pst = pinned_ensure(c, &c->h_down, &c->h_down_cap, sizeof(ProblemDev) * (size_t)P); if (pst) return pst; }
-    HIPC(c, hipMemcpyAsync(c->h_down, c->probs.p, sizeof(ProblemDev) * P, hipMemcpyDeviceToHost, c->stream));
-    XFER(c, d2h(c, cs.data(), c->sums.p, sizeof(double) * cs.size()));
-    std::vector<double> rsys;
-    if (residual || res_ratio || res_status) {
+    std::vector<double> cs((size_t)P * kCovTerms), rsys;
+    st = batch_download(c, P, hp, 0, [&]() -> int {
+        XFER(c, d2h(c, cs.data(), c->sums.p, sizeof(double) * cs.size()));
+        if (!residual && !res_ratio && !res_status) return PGICP_OK;
         // The residual check of the result: one more pass of the chain WITHOUT a solve, with the final transform (it is in
         // ProblemDev::Tcur) -- transform, match, outlier weights, error elements.  The pass is SEEDED with the last
         // iteration's correspondences, which the final increment (below the convergence thresholds) hardly moves: as a
         // separate, unseeded chain it cost a fifth of a loop-closure batch.  Seeds are candidates only: the matches are exact.
-        launch_reopen(c->stream, c->probs.as<ProblemDev>(), P);
-        XFER(c, h2d(c, c->active.p, c->h_ident.data(), sizeof(int) * P));
+        launch_reopen(c->stream, B.probs, P);
+        XFER(c, h2d(c, B.active, c->h_ident.data(), sizeof(int) * P));
         c->prof_next_m = total_m;
-        one_iteration<T>(c, L, ch, false, L.total, P, 1);
+        one_iteration<T>(c, L, ch, B, pl, false, L.total, P, 1);
         HIPC(c, c->sums2.ensure(sizeof(double) * (size_t)P * kSys));
-        launch_sum_partials(c->stream, c->partials.as<double>(), reduce_blocks(L.max_pairs()), kSys, c->probs.as<ProblemDev>(), 0,
-                            c->sums2.as<double>(), P);
+        launch_sum_partials(c->stream, B.partials, reduce_blocks(L.max_pairs()), kSys, B.probs, 0, c->sums2.as<double>(), P);
         rsys.resize((size_t)P * kSys);
         XFER(c, d2h(c, rsys.data(), c->sums2.p, sizeof(double) * rsys.size()));
-    }
-    HIPC(c, stream_sync(c));
-    HIPC(c, hipGetLastError());
-    std::memcpy(hp.data(), c->h_down, sizeof(ProblemDev) * (size_t)P);
-    hints_store(c, 0, hp);
-    var_trim_record(c, hp);
+        return PGICP_OK;
+    });
+    if (st) return st;
     if (noisy) {
         pgicp_ctx::Noise &N = c->noise;
         N.last_P = P;
@@ -692,25 +745,12 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
             double t1[16];
             mat4_mul(D.T_iter, D.Tpre, t1);
             mat4_mul(Tref[p].data(), t1, To);
-            double H[36], G[36], Hi[36], tmp[36];
+            double H[36], G[36], Hi[36];
             sys_to_full(cs.data() + (size_t)p * kCovTerms, H);
             sys_to_full(cs.data() + (size_t)p * kCovTerms + 21, G);
             if (!with_cov) { /* zeros */ }
-            else if (inverse6(H, Hi)) {
-                const double s2 = prm.sensor_std_dev * prm.sensor_std_dev;
-                for (int i = 0; i < 6; i++)
-                    for (int j = 0; j < 6; j++) {
-                        double a = 0.0;
-                        for (int k = 0; k < 6; k++) a += Hi[i * 6 + k] * G[k * 6 + j];
-                        tmp[i * 6 + j] = a;
-                    }
-                for (int i = 0; i < 6; i++)
-                    for (int j = 0; j < 6; j++) {
-                        double a = 0.0;
-                        for (int k = 0; k < 6; k++) a += tmp[i * 6 + k] * Hi[k * 6 + j];
-                        s.cov[i * 6 + j] = s2 * a;
-                    }
-            } else
+            else if (inverse6(H, Hi)) sandwich6(Hi, G, prm.sensor_std_dev * prm.sensor_std_dev, s.cov);
+            else
                 for (int i = 0; i < 6; i++) s.cov[i * 6 + i] = std::numeric_limits<double>::max();
         } else {
             mat4_identity(To);
@@ -732,10 +772,7 @@ int icp_pair(pgicp_ctx *c, const T *reading, int rd_stride, int n, const T *ref_
     int id = -1;
     int st = map_create<T>(c, ref_xyz, ref_stride, ref_nrm, nrm_stride, m, mem, 1, &id);
     if (st) { (void)noise_take(c); VarDistCall radii(c); return st; }
-    pgicp_problem pr;
-    std::memset(&pr, 0, sizeof pr);
-    pr.map_id = id; pr.reading = reading; pr.stride = rd_stride; pr.n = n; pr.mem = mem;
-    std::memcpy(pr.T_init, T_init, sizeof pr.T_init);
+    const pgicp_problem pr = one_problem(id, reading, rd_stride, n, mem, T_init);
     st = align_batch<T>(c, 1, &pr, T_out, stats);
     (void)stream_sync(c);
     if (MapHost<T> *mh = get_map<T>(c, id)) free_map(c, *mh);

@@ -1,55 +1,28 @@
 // api_stages.inc -- part of pgicp_api.cpp (one translation unit): stage-level entry points: matcher, partial chain, outlier weights, error statistics, transform, local-map assembly, surface normals.
 // matcher-only / partial chain on one problem
+// (out: the layout, the problem record and the iteration's buffer record of the one problem -- B.pair_slot / B.pair_d2 hold the pairs)
 template <typename T>
 int run_partial(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, int mem, const double *Tmove,
-                BatchLayout &L, std::vector<ProblemDev> &hp)
+                BatchLayout &L, std::vector<ProblemDev> &hp, IterBufs<T> &B)
 {
     MapHost<T> *M = get_map<T>(c, map_id);
     if (!M) return fail(c, PGICP_ERR_ARG, "pgicp: unknown map id");
-    pgicp_problem pr;
-    std::memset(&pr, 0, sizeof pr);
-    pr.map_id = map_id; pr.reading = reading; pr.stride = stride; pr.n = n; pr.mem = mem;
-    mat4_identity(pr.T_init);
-    if (Tmove) std::memcpy(pr.T_init, Tmove, sizeof pr.T_init);
+    const pgicp_problem pr = one_problem(map_id, reading, stride, n, mem, Tmove);
     // (the matcher alone: no outlier filter runs here, so a SurfaceNormalOutlierFilter's normals are not asked for)
     struct NoNormals { pgicp_ctx *c; double a; ~NoNormals() { c->prm.normal_max_angle = a; } } restore{c, c->prm.normal_max_angle};
     c->prm.normal_max_angle = 0.0;
     // (matching alone: the GenericDescriptor filter weighs pairs, it does not need the map's values here)
     struct NoDesc { pgicp_ctx *c; int m; ~NoDesc() { c->gd_mode = m; } } restore_gd{c, c->gd_mode};
     c->gd_mode = PGICP_DESC_FILTER_OFF;
-    int st = batch_begin<T>(c, 1, &pr, [&](int, double *Tpre) {
-        double mean[3] = {(double)M->mean[0], (double)M->mean[1], (double)M->mean[2]};
-        double Tm_inv[16];
-        translation(mean, -1.0, Tm_inv);
-        mat4_mul(Tm_inv, pr.T_init, Tpre);
-    }, L, hp);
+    int st = batch_begin<T>(c, 1, &pr, [&](int, double *Tpre) { centred_pre(M, pr.T_init, Tpre); }, L, hp);
     if (st) return st;
-    State<T> &S = state<T>(c);
+    B = iter_bufs<T>(c, L);
     const ChainDev<T> ch = chain_of<T>(c, c->prm);
-    const MapDev<T> *maps = S.d_maps.template as<MapDev<T>>();
-    ProblemDev *probs = c->probs.as<ProblemDev>();
-    if (L.knn > 1) {
-        ProfScope ps(c, PGICP_PROF_KNN_GRID, n);
-        if (launch_knn_topk<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(), S.d2.template as<T>(), ch, 1, n,
-                               c->active.as<int>()) != 0)
-            return fail(c, PGICP_ERR_ARG, "KDTreeMatcher.knn exceeds PGICP_MAX_KNN");
-        if (c->vd.on) vardist_cut_enqueue<T>(c, 1, L.max_pairs());
-        return PGICP_OK;
-    }
-    {
-        ProfScope ps(c, c->prm.matcher == PGICP_MATCHER_BRUTE ? PGICP_PROF_KNN_BRUTE : PGICP_PROF_KNN_GRID, n);
-        launch_knn<T>(c->stream, c->prm.matcher, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(),
-                      S.d2.template as<T>(), ch, 1, n, 0, c->small.as<int>() + 16, c->slow_list.as<int2>(), c->slow_lb.as<T>(),
-                      c->slow_ring.as<int>(), L.rings_unseeded, c->active.as<int>(), S.none_r.template as<T>(), 1, c->queue.p, 1, L.table_kinds);
-        c->seg_clean = 0;
-        c->counters_clean = 0;                 // (pgicp_debug_counters: this pass's queue counters, not the copy batch_begin cleared)
-        // public matcher output / partial chain: resolve every queued query exactly
-        if (c->prm.matcher == PGICP_MATCHER_GRID)
-            launch_knn_slow<T>(c->stream, probs, maps, S.rd_sorted.template as<T>(), S.slot.template as<int>(),
-                               S.d2.template as<T>(), ch, c->small.as<int>() + 16, c->slow_list.as<int2>(), c->slow_lb.as<T>(),
-                               c->slow2.as<int>(), 1, S.none_r.template as<T>());
-    }
-    if (c->vd.on) vardist_cut_enqueue<T>(c, 1, L.max_pairs());      // (pgicp_vardist.h: what the call returns is cut as an iteration's pairs are)
+    const IterPlan pl = iter_plan(c, L, ch);
+    // the matcher stage as the public matcher output / a partial chain needs it: unseeded, every queued query resolved exactly
+    if (matcher_stage<T>(c, L, ch, B, pl, 1, n, 1, 0, 0, true) != 0) return fail(c, PGICP_ERR_ARG, "KDTreeMatcher.knn exceeds PGICP_MAX_KNN");
+    // (pgicp_vardist.h: what the call returns is cut as an iteration's pairs are)
+    if (pl.vardist) cut_pairs<T>(c, B, 1, L.max_pairs());
     return PGICP_OK;
 }
 
@@ -59,23 +32,20 @@ int match(pgicp_ctx *c, int map_id, const T *reading, int stride, int n, int mem
     VarDistCall radii(c);                        // (pgicp_arm_reading_radii: one-shot, consumed here whatever follows)
     if (!c || !reading || n <= 0 || !ids || !dist2) return fail(c, PGICP_ERR_ARG, "pgicp_match: bad argument");
     {
-        pgicp_problem one;
-        std::memset(&one, 0, sizeof one);
-        one.n = n;
+        const pgicp_problem one = one_problem(-1, reading, stride, n, mem, Tm);
         const int rst = radii.template check<T>(1, &one);
         if (rst) return rst;
     }
     HIPC(c, hipSetDevice(c->device));
     BatchLayout L;
     std::vector<ProblemDev> hp;
-    int st = run_partial<T>(c, map_id, reading, stride, n, mem, Tm, L, hp);
+    IterBufs<T> B;
+    int st = run_partial<T>(c, map_id, reading, stride, n, mem, Tm, L, hp, B);
     if (st) return st;
-    State<T> &S = state<T>(c);
     const size_t np = (size_t)n * L.knn;                     // knn entries per reading point
     HIPC(c, c->tmp_a.ensure(sizeof(int) * np));
     HIPC(c, c->tmp_b.ensure(sizeof(T) * np));
-    launch_unpermute<T>(c->stream, S.d_maps.template as<MapDev<T>>(), map_index<T>(c, map_id), c->order.as<int>(),
-                        pair_slots<T>(c), pair_d2<T>(c), n, L.knn, c->tmp_a.as<int>(), c->tmp_b.as<T>());
+    launch_unpermute<T>(c->stream, B.maps, map_index<T>(c, map_id), B.order, B.pair_slot, B.pair_d2, n, L.knn, c->tmp_a.as<int>(), c->tmp_b.as<T>());
     if (mem == PGICP_DEVICE) {
         HIPC(c, hipMemcpyAsync(ids, c->tmp_a.p, sizeof(int) * np, hipMemcpyDeviceToDevice, c->stream));
         HIPC(c, hipMemcpyAsync(dist2, c->tmp_b.p, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
@@ -143,30 +113,19 @@ int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ra
             borrow = true;
         }
     }
-    int st = batch_begin<T>(c, P, pr, [&](int p, double *Tpre) {
-        MapHost<T> *M = get_map<T>(c, pr[p].map_id);
-        double mean[3] = {(double)M->mean[0], (double)M->mean[1], (double)M->mean[2]};
-        double Tm_inv[16];
-        translation(mean, -1.0, Tm_inv);
-        mat4_mul(Tm_inv, pr[p].T_init, Tpre);
-    }, L, hp, 1, borrow ? &bs : nullptr);
+    int st = batch_begin<T>(c, P, pr, [&](int p, double *Tpre) { centred_pre(get_map<T>(c, pr[p].map_id), pr[p].T_init, Tpre); }, L, hp, 1,
+                            borrow ? &bs : nullptr);
     if (st) return st;
+    const IterBufs<T> B = iter_bufs<T>(c, L);
     const ChainDev<T> ch = chain_of<T>(c, c->prm);
     const int mode = borrow ? (bs.capped ? 3 : 2) : 0;
     c->sel_guess_first = hints_cover_first(hp) ? 1 : 0;
-    one_iteration<T>(c, L, ch, false, L.total, P, mode);
+    one_iteration<T>(c, L, ch, B, iter_plan(c, L, ch), false, L.total, P, mode);
     c->sel_guess_first = 0;
-    launch_sum_partials(c->stream, c->partials.as<double>(), reduce_blocks(L.max_pairs()), kSys, c->probs.as<ProblemDev>(), 0,
-                        c->sums.as<double>(), P);
+    launch_sum_partials(c->stream, B.partials, reduce_blocks(L.max_pairs()), kSys, B.probs, 0, c->sums.as<double>(), P);
     std::vector<double> sys((size_t)P * kSys);
     XFER(c, d2h(c, sys.data(), c->sums.p, sizeof(double) * sys.size()));
-    { const int pst = pinned_ensure(c, &c->h_down, &c->h_down_cap, sizeof(ProblemDev) * (size_t)P); if (pst) return pst; }
-    HIPC(c, hipMemcpyAsync(c->h_down, c->probs.p, sizeof(ProblemDev) * P, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, stream_sync(c));
-    HIPC(c, hipGetLastError());
-    std::memcpy(hp.data(), c->h_down, sizeof(ProblemDev) * (size_t)P);
-    hints_store(c, 1, hp);
-    var_trim_record(c, hp);
+    XFER(c, batch_download(c, P, hp, 1));
     int worst = PGICP_OK;
     for (int p = 0; p < P; p++) {
         const double *s = sys.data() + (size_t)p * kSys;
@@ -185,11 +144,7 @@ int partial_chain(pgicp_ctx *c, int map_id, const T *reading, int stride, int n,
                   double *residual)
 {
     if (!c || !reading || n <= 0) { VarDistCall radii(c); return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain: bad argument"); }
-    pgicp_problem pr;
-    std::memset(&pr, 0, sizeof pr);
-    pr.map_id = map_id; pr.reading = reading; pr.stride = stride; pr.n = n; pr.mem = mem;
-    mat4_identity(pr.T_init);
-    if (Tm) std::memcpy(pr.T_init, Tm, sizeof pr.T_init);
+    const pgicp_problem pr = one_problem(map_id, reading, stride, n, mem, Tm);
     return partial_chain_batch<T>(c, 1, &pr, ratio, residual, nullptr);
 }
 
@@ -199,11 +154,7 @@ int partial_chain_seeded(pgicp_ctx *c, int map_id, const T *reading, int stride,
 {
     if (!c || !reading || n <= 0) return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain_seeded: bad argument");
     if (src && (n_seg < 0 || (n_seg > 0 && (!src_start || !dst_start)))) return fail(c, PGICP_ERR_ARG, "pgicp_partial_chain_seeded: bad segments");
-    pgicp_problem pr;
-    std::memset(&pr, 0, sizeof pr);
-    pr.map_id = map_id; pr.reading = reading; pr.stride = stride; pr.n = n; pr.mem = mem;
-    mat4_identity(pr.T_init);
-    if (Tm) std::memcpy(pr.T_init, Tm, sizeof pr.T_init);
+    const pgicp_problem pr = one_problem(map_id, reading, stride, n, mem, Tm);
     const SeedSpec sp{src, n_seg, src_start, dst_start};
     return partial_chain_batch<T>(c, 1, &pr, ratio, residual, nullptr, &sp);
 }

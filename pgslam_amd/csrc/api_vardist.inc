@@ -31,11 +31,8 @@ struct VarDistCall {
     }
 };
 
-// the per-pair arrays everything downstream of the matcher reads in this call: the cut pairs of an armed call, else the matcher's own
-template <typename T> int *pair_slots(pgicp_ctx *c) { return c->vd.on ? c->vd.slot_cut.as<int>() : state<T>(c).slot.template as<int>(); }
-template <typename T> T *pair_d2(pgicp_ctx *c) { return c->vd.on ? c->vd.d2_cut.as<T>() : state<T>(c).d2.template as<T>(); }
-
-// batch_begin of an armed call: room for the cut pairs (`pairs`: points x knn over the batch)
+// batch_begin of an armed call: room for the cut pairs (`pairs`: points x knn over the batch).  The call's IterBufs (api_icp.inc) then
+// names them as the pairs everything behind the matcher reads, and cut_pairs fills them.
 template <typename T>
 int vardist_begin(pgicp_ctx *c, size_t pairs)
 {
@@ -44,14 +41,4 @@ int vardist_begin(pgicp_ctx *c, size_t pairs)
     HIPC(c, c->vd.slot_cut.ensure(sizeof(int) * pairs));
     HIPC(c, c->vd.d2_cut.ensure(sizeof(T) * pairs));
     return PGICP_OK;
-}
-
-// the cut, behind a matcher pass that resolved every pair of the active problems exactly
-template <typename T>
-void vardist_cut_enqueue(pgicp_ctx *c, int n_active, int max_pairs)
-{
-    State<T> &S = state<T>(c);
-    launch_vardist_cut<T>(c->stream, c->probs.as<ProblemDev>(), c->active.as<int>(), n_active, max_pairs, S.slot.template as<int>(),
-                          S.d2.template as<T>(), c->order.as<int>(), c->vd.vals.template as<T>(), c->vd.off_dev.as<long long>(),
-                          c->vd.slot_cut.as<int>(), c->vd.d2_cut.as<T>());
 }

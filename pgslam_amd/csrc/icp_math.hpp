@@ -437,4 +437,22 @@ PGICP_HD bool inverse6(const double *H, double *Hi)
     return true;
 }
 
+// out = s * Hi G Hi (6x6, row-major): the Censi covariance estimate's sandwich, (Hi G) first, every sum in ascending k
+PGICP_HD void sandwich6(const double *Hi, const double *G, double s, double *out)
+{
+    double tmp[36];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double a = 0.0;
+            for (int k = 0; k < 6; k++) a += Hi[i * 6 + k] * G[k * 6 + j];
+            tmp[i * 6 + j] = a;
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double a = 0.0;
+            for (int k = 0; k < 6; k++) a += tmp[i * 6 + k] * Hi[k * 6 + j];
+            out[i * 6 + j] = s * a;
+        }
+}
+
 }  // namespace pgicp

@@ -37,6 +37,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 using namespace pgicp;
@@ -385,15 +386,6 @@ int pgicp_map_size(pgicp_ctx *c, int id, int *m)
     if (MapHost<float> *h = get_map<float>(c, id)) { *m = h->m; return PGICP_OK; }
     if (MapHost<double> *h = get_map<double>(c, id)) { *m = h->m; return PGICP_OK; }
     return fail(c, PGICP_ERR_ARG, "pgicp_map_size: unknown map id");
-}
-
-static pgicp_problem one_problem(int map_id, const void *rd, int stride, int n, int mem, const double *T)
-{
-    pgicp_problem p;
-    std::memset(&p, 0, sizeof p);
-    p.map_id = map_id; p.reading = rd; p.stride = stride; p.n = n; p.mem = mem;
-    if (T) std::memcpy(p.T_init, T, sizeof p.T_init); else mat4_identity(p.T_init);
-    return p;
 }
 
 int pgicp_align_f32(pgicp_ctx *c, int map_id, const float *rd, int stride, int n, int mem, const double T_init[16],
