@@ -45,6 +45,8 @@
 #include "elipsoids_host.hpp"
 #include "../pgicp_sensor_chain.h"
 #include "sensor_chain_host.hpp"
+#include "../pgicp_descriptor_filters.h"
+#include "descriptor_filters_host.hpp"
 #include "axis_quantile_host.hpp"
 #include "matrix.hpp"
 #include "yaml_lite.hpp"
@@ -193,6 +195,9 @@ template <typename T> struct Abi {
     static int sensor_chain(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, int kn, int ke, int kd, int ns, const pgicp_chain_stage *st, const T *d, int dr,
                             T *ox, T *on, T *oe, T *odn, T *oobs, T *onoise, T *od, int32_t *idx, int *n_out)
     { return pick<T>(pgicp_sensor_chain_f32, pgicp_sensor_chain_f64)(c, x, xs, n, PGICP_HOST, knn, md, kn, ke, kd, ns, st, d, dr, ox, on, 3, oe, odn, oobs, onoise, od, idx, n_out); }
+    static int sensor_chain_ext(pgicp_ctx *c, const T *x, int xs, int n, int knn, double md, int kn, int ke, int kd, int ns, const pgicp_chain_stage *st, const T *d, int dr,
+                                const pgicp_chain_out &o, int *n_out)
+    { return pick<T>(pgicp_sensor_chain_ext_f32, pgicp_sensor_chain_ext_f64)(c, x, xs, n, PGICP_HOST, knn, md, kn, ke, kd, ns, st, d, dr, &o, n_out); }
     static int covariance_sampling(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, int tn, int32_t *idx, int *n_out, pgicp_cov_frame *fr)
     { return pick<T>(pgicp_covariance_sampling_f32, pgicp_covariance_sampling_f64)(c, x, xs, nr, ns, n, PGICP_HOST, nb, tn, nullptr, 0, nullptr, nullptr, 3, nullptr, idx, n_out, fr); }
     static int normal_space(pgicp_ctx *c, const T *x, int xs, const T *nr, int ns, int n, int nb, double eps, unsigned long long seed, int32_t *idx, int *n_out)
@@ -256,6 +261,8 @@ struct PointMatcher {
             bool contains(const std::string &t) const { for (auto &l : *this) if (l.text == t) return true; return false; }
             size_t totalDim() const { size_t d = 0; for (auto &l : *this) d += l.span; return d; }
         };
+        //! [EXT] DataPoints::InvalidField: a filter asks for a descriptor the cloud does not carry, or carries in another shape
+        struct InvalidField : std::runtime_error { explicit InvalidField(const std::string &m) : std::runtime_error(m) {} };
         Matrix features;          //!< (dim+1) x N homogeneous coordinates, column major: one point = 4 contiguous values
         Labels featureLabels;
         Matrix descriptors;       //!< D x N
@@ -423,6 +430,8 @@ struct PointMatcher {
         //! the filter as an entry of pgicp_filter_cloud's list (the device pass keeps the points this host version keeps);
         //! false: the filter has no device form (it adds descriptors, or needs neighbours)
         virtual bool deviceSpec(pgicp_filter &) const { return false; }
+        //! the same for a filter whose entry depends on the cloud it is about to see (a descriptor's row)
+        virtual bool deviceSpec(pgicp_filter &f, const DataPoints &) const { return deviceSpec(f); }
         //! called once after a device pass that stood in for inPlaceFilter (filters whose parameters evolve from cloud to cloud)
         virtual void afterDevicePass() {}
     };
@@ -1506,6 +1515,75 @@ struct PointMatcher {
             c.setDescriptor("simpleSensorNoise", noise);
         }
     };
+    //! the row of descriptor `name`, which must exist with `span` rows: DataPoints::InvalidField otherwise, worded as upstream words it
+    static int descriptorRowOf(const DataPoints &c, const std::string &name, int span, const char *filter)
+    {
+        if (!c.descriptorExists(name)) throw typename DataPoints::InvalidField(std::string(filter) + ": Error, cannot find " + name + " in descriptors.");
+        if (c.getDescriptorDimension(name) != span)
+            throw typename DataPoints::InvalidField(std::string(filter) + ": Error, descriptor " + name + " must have " + std::to_string(span) + (span == 1 ? " row." : " rows."));
+        return c.getDescriptorStartingRow(name);
+    }
+    //! [EXT] IncidenceAngleDataPointsFilter (DataPointsFilters/IncidenceAngle.cpp, restated as recalled in
+    //! include/pgicp_descriptor_filters.h): adds the one-row descriptor `incidenceAngles`, the angle between a point's normal and its
+    //! observation direction -- descriptor_filters_host.hpp's incidence_angle, which the device stage calls too.  Needs `normals` and
+    //! `observationDirections`, 3 rows each.  Elementwise: alone it runs on the host, inside a sensor-chain run on the device.
+    struct IncidenceAngleDataPointsFilter : DataPointsFilter {
+        void inPlaceFilter(DataPoints &c) override
+        {
+            const int rn = descriptorRowOf(c, "normals", 3, "IncidenceAngleDataPointsFilter"), ro = descriptorRowOf(c, "observationDirections", 3, "IncidenceAngleDataPointsFilter");
+            const int n = (int)c.features.cols();
+            Matrix a(1, n);
+            for (int j = 0; j < n; j++) {
+                const T nv[3] = {c.descriptors(rn, j), c.descriptors(rn + 1, j), c.descriptors(rn + 2, j)};
+                const T ov[3] = {c.descriptors(ro, j), c.descriptors(ro + 1, j), c.descriptors(ro + 2, j)};
+                a(0, j) = pgslam_amd::descriptor_filters::incidence_angle<T>(nv, ov);
+            }
+            c.setDescriptor("incidenceAngles", a);
+        }
+    };
+    //! [EXT] SphericalityDataPointsFilter{keepUnstructureness, keepStructureness} (DataPointsFilters/Sphericality.cpp, restated as
+    //! recalled): from `eigValues` (3 rows) the one-row descriptors `sphericality` and, when asked for, `unstructureness` and
+    //! `structureness`, appended in that order -- descriptor_filters_host.hpp's sphericality
+    struct SphericalityDataPointsFilter : DataPointsFilter {
+        bool keepUnstructureness, keepStructureness;
+        explicit SphericalityDataPointsFilter(bool ku = false, bool ks = false) : keepUnstructureness(ku), keepStructureness(ks) {}
+        void inPlaceFilter(DataPoints &c) override
+        {
+            const int re = descriptorRowOf(c, "eigValues", 3, "SphericalityDataPointsFilter");
+            const int n = (int)c.features.cols();
+            Matrix sph(1, n), uns(1, n), str(1, n);
+            for (int j = 0; j < n; j++) {
+                const T e[3] = {c.descriptors(re, j), c.descriptors(re + 1, j), c.descriptors(re + 2, j)};
+                pgslam_amd::descriptor_filters::sphericality<T>(e, sph(0, j), uns(0, j), str(0, j));
+            }
+            c.setDescriptor("sphericality", sph);
+            if (keepUnstructureness) c.setDescriptor("unstructureness", uns);
+            if (keepStructureness) c.setDescriptor("structureness", str);
+        }
+    };
+    //! [EXT] CutAtDescriptorThresholdDataPointsFilter{descName, useLargerThan, threshold} (DataPointsFilters/CutAtDescriptorThreshold.cpp,
+    //! restated as recalled): drops the points whose one-row descriptor `descName` lies above the threshold (useLargerThan) or below
+    //! it -- descriptor_filters_host.hpp's cut_keep; a NaN is never kept.  Order is kept; features and descriptors travel.  On the
+    //! device it is an entry of pgicp_filter_cloud's list (its row is the cloud's, so the spec needs the cloud) and a stage of a
+    //! sensor-chain run.
+    struct CutAtDescriptorThresholdDataPointsFilter : DataPointsFilter {
+        std::string descName; bool useLargerThan; T threshold;
+        CutAtDescriptorThresholdDataPointsFilter(const std::string &name, bool larger, T thr) : descName(name), useLargerThan(larger), threshold(thr) {}
+        void inPlaceFilter(DataPoints &c) override
+        {
+            const int r = descriptorRowOf(c, descName, 1, "CutAtDescriptorThresholdDataPointsFilter");
+            compactColumns(c, [&](int j) { return pgslam_amd::descriptor_filters::cut_keep<T>(c.descriptors(r, j), threshold, useLargerThan); });
+        }
+        //! (no descriptor of that name and one row, or no cloud to look at: no device form -- the host path runs, and throws)
+        using DataPointsFilter::deviceSpec;
+        bool deviceSpec(pgicp_filter &f, const DataPoints &c) const override
+        {
+            if (!c.descriptorExists(descName) || c.getDescriptorDimension(descName) != 1) return false;
+            std::memset(&f, 0, sizeof f);
+            f.type = PGICP_FILTER_CUT_AT_DESCRIPTOR; f.p[0] = (double)c.getDescriptorStartingRow(descName); f.p[1] = useLargerThan ? 1.0 : 0.0; f.p[2] = (double)threshold;
+            return true;
+        }
+    };
     struct DataPointsFilters : std::vector<std::shared_ptr<DataPointsFilter>> {
         DataPointsFilters() {}
         //! Localizer.hpp:77 -- a YAML list of filters
@@ -1519,7 +1597,7 @@ struct PointMatcher {
         static std::string supportedNames()
         {
             return " (supported: Identity, MinDist, MaxDist, DistanceLimit, MaxQuantileOnAxis, BoundingBox, RemoveNaN, SurfaceNormal, "
-                   "SamplingSurfaceNormal, Elipsoids, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, NormalSpace, ObservationDirection, OrientNormals, Shadow, FixStepSampling, RandomSampling, MaxPointCount "
+                   "SamplingSurfaceNormal, Elipsoids, VoxelGrid, OctreeGrid, MaxDensity, CovarianceSampling, NormalSpace, ObservationDirection, OrientNormals, Shadow, IncidenceAngle, Sphericality, CutAtDescriptorThreshold, FixStepSampling, RandomSampling, MaxPointCount "
                    "(seeded samplers, not rand()-parity))";
         }
         //! refuses a module that carries a parameter outside `names` (only the filters that always refused one call it)
@@ -1679,6 +1757,24 @@ struct PointMatcher {
                     const double e = get("eps", "0.1");
                     if (!(e >= 0.0 && e <= 3.14159265358979323846)) throw std::runtime_error(m.name + ": eps must be in [0, pi]");
                     this->push_back(std::make_shared<ShadowDataPointsFilter>((T)e));
+                } else if (m.name == "IncidenceAngleDataPointsFilter") {
+                    allowOnly(m, {});
+                    this->push_back(std::make_shared<IncidenceAngleDataPointsFilter>());
+                } else if (m.name == "SphericalityDataPointsFilter") {
+                    allowOnly(m, {"keepUnstructureness", "keepStructureness"});
+                    const double ku = get("keepUnstructureness", "0"), ks = get("keepStructureness", "0");
+                    if ((ku != 0.0 && ku != 1.0) || (ks != 0.0 && ks != 1.0)) throw std::runtime_error(m.name + ": keepUnstructureness and keepStructureness must be 0 or 1");
+                    this->push_back(std::make_shared<SphericalityDataPointsFilter>(ku != 0.0, ks != 0.0));
+                } else if (m.name == "CutAtDescriptorThresholdDataPointsFilter") {
+                    allowOnly(m, {"descName", "useLargerThan", "threshold"});
+                    // upstream's defaults ("none" and 1) cut nothing meaningful: as VarTrimmedDistOutlierFilter asks for its parameters,
+                    // the name and the threshold are asked for rather than guessed
+                    for (const char *k : {"descName", "threshold"})
+                        if (!m.params.count(k)) throw std::runtime_error(m.name + ": parameter " + k + " must be given");
+                    const double lt = get("useLargerThan", "1"), thr = get("threshold", "1");
+                    if (lt != 0.0 && lt != 1.0) throw std::runtime_error(m.name + ": useLargerThan must be 0 or 1");
+                    if (m.params.at("descName").empty()) throw std::runtime_error(m.name + ": descName must name a descriptor");
+                    this->push_back(std::make_shared<CutAtDescriptorThresholdDataPointsFilter>(m.params.at("descName"), lt != 0.0, (T)thr));
                 } else if (m.name == "FixStepSamplingDataPointsFilter") {
                     const double start = get("startStep", "10"), end = get("endStep", "10"), mult = get("stepMult", "1");
                     if (!(start >= 1.0 && start <= 2147483647.0) || !(end >= 1.0 && end <= 2147483647.0) || !(mult > 0.0))
@@ -1698,45 +1794,77 @@ struct PointMatcher {
         }
         void init() { for (auto &f : *this) f->init(); }
         size_t lastFused = 0;
-        //! A sensor-chain RUN starting at filter k (include/pgicp_sensor_chain.h): the longest contiguous sub-list from k made of one
-        //! SurfaceNormalDataPointsFilter (no ext output, knn in [3, 32]) and ObservationDirection, OrientNormals, Shadow, MaxDensity,
-        //! SimpleSensorNoise, each at most once, that the device call accepts -- only ObservationDirection and SimpleSensorNoise may
-        //! stand ahead of the SurfaceNormal (they read coordinates, and nothing ahead of the head drops points); OrientNormals needs
-        //! keepNormals and the run's ObservationDirection before it, Shadow keepNormals, MaxDensity keepDensities and parameters
-        //! the device takes -- and that holds at least one of the four filters which otherwise run on the host.  Returns the run's
-        //! length, 0 when there is none at k.  Needs no device.
-        size_t sensorChainRunAt(size_t k) const
-        {
+        //! A sensor-chain RUN starting at filter k (include/pgicp_sensor_chain.h, include/pgicp_descriptor_filters.h): the longest
+        //! contiguous sub-list from k made of one SurfaceNormalDataPointsFilter (no ext output, knn in [3, 32]) and ObservationDirection,
+        //! OrientNormals, Shadow, MaxDensity, SimpleSensorNoise, IncidenceAngle, Sphericality, each at most once, and up to four
+        //! CutAtDescriptorThreshold, that the device call accepts -- only ObservationDirection and SimpleSensorNoise may stand ahead of
+        //! the SurfaceNormal (they read coordinates, and nothing ahead of the head drops points); OrientNormals and IncidenceAngle need
+        //! keepNormals and the run's ObservationDirection before them, Shadow keepNormals, MaxDensity keepDensities and parameters the
+        //! device takes, Sphericality keepEigenValues, a cut a descName that names a row the run has made by then or a one-row
+        //! descriptor `cloud` carries (null: no cloud to look at) -- and that holds at least one of the filters which otherwise run on
+        //! the host.  Returns the run's length, 0 when there is none at k.  Needs no device.
+        struct ChainRunState {
             SurfaceNormalDataPointsFilter *sn = nullptr;
-            bool obs = false, orient = false, shadow = false, md = false, noise = false;
-            size_t j = k;
-            for (; j < this->size(); j++) {
-                DataPointsFilter *f = (*this)[j].get();
+            SphericalityDataPointsFilter *sph = nullptr;
+            bool obs = false, orient = false, shadow = false, md = false, noise = false, inc = false;
+            int cuts = 0;
+            //! PGICP_CHAIN_ROW_* of a row the run has made so far, -1: none of that name
+            int rowMade(const std::string &name) const
+            {
+                if (name == "densities") return sn && sn->keepDensities ? PGICP_CHAIN_ROW_DENSITIES : -1;
+                if (name == "incidenceAngles") return inc ? PGICP_CHAIN_ROW_INCIDENCE_ANGLES : -1;
+                if (name == "sphericality") return sph ? PGICP_CHAIN_ROW_SPHERICALITY : -1;
+                if (name == "unstructureness") return sph && sph->keepUnstructureness ? PGICP_CHAIN_ROW_UNSTRUCTURENESS : -1;
+                if (name == "structureness") return sph && sph->keepStructureness ? PGICP_CHAIN_ROW_STRUCTURENESS : -1;
+                if (name == "simpleSensorNoise") return noise ? PGICP_CHAIN_ROW_SIMPLE_SENSOR_NOISE : -1;
+                return -1;
+            }
+            //! takes filter f into the run; false: the run ends ahead of it
+            bool take(DataPointsFilter *f, const DataPoints *cloud)
+            {
                 if (auto *s = dynamic_cast<SurfaceNormalDataPointsFilter *>(f)) {
-                    if (sn || s->wantsExt() || s->knn < 3 || s->knn > 32) break;
+                    if (sn || s->wantsExt() || s->knn < 3 || s->knn > 32) return false;
                     sn = s;
                 } else if (dynamic_cast<ObservationDirectionDataPointsFilter *>(f)) {
-                    if (obs) break;
+                    if (obs) return false;
                     obs = true;
                 } else if (dynamic_cast<SimpleSensorNoiseDataPointsFilter *>(f)) {
-                    if (noise) break;
+                    if (noise) return false;
                     noise = true;
                 } else if (dynamic_cast<OrientNormalsDataPointsFilter *>(f)) {
-                    if (orient || !sn || !sn->keepNormals || !obs) break;
+                    if (orient || !sn || !sn->keepNormals || !obs) return false;
                     orient = true;
                 } else if (dynamic_cast<ShadowDataPointsFilter *>(f)) {
-                    if (shadow || !sn || !sn->keepNormals) break;
+                    if (shadow || !sn || !sn->keepNormals) return false;
                     shadow = true;
                 } else if (auto *m = dynamic_cast<MaxDensityDataPointsFilter *>(f)) {
-                    if (md || !sn || !sn->keepDensities || !m->deviceTakesParameters()) break;
+                    if (md || !sn || !sn->keepDensities || !m->deviceTakesParameters()) return false;
                     md = true;
+                } else if (dynamic_cast<IncidenceAngleDataPointsFilter *>(f)) {
+                    if (inc || !sn || !sn->keepNormals || !obs) return false;
+                    inc = true;
+                } else if (auto *p = dynamic_cast<SphericalityDataPointsFilter *>(f)) {
+                    if (sph || !sn || !sn->keepEigenValues) return false;
+                    sph = p;
+                } else if (auto *p = dynamic_cast<CutAtDescriptorThresholdDataPointsFilter *>(f)) {
+                    if (cuts == PGICP_CHAIN_EXT_MAX_CUTS || !sn) return false;
+                    if (rowMade(p->descName) < 0 && !(cloud && cloud->descriptorExists(p->descName) && cloud->getDescriptorDimension(p->descName) == 1)) return false;
+                    cuts++;
                 } else
-                    break;
+                    return false;
+                return true;
             }
-            if (!sn || !(obs || orient || shadow || noise)) return 0;
+            bool ext() const { return inc || sph || cuts > 0; }
+        };
+        size_t sensorChainRunAt(size_t k, const DataPoints *cloud = nullptr) const
+        {
+            ChainRunState r;
+            size_t j = k;
+            while (j < this->size() && r.take((*this)[j].get(), cloud)) j++;
+            if (!r.sn || !(r.obs || r.orient || r.shadow || r.noise || r.ext())) return 0;
             return j - k;
         }
-        //! the number of filters the last apply() ran inside one pgicp_sensor_chain_* call; 0 when it ran none
+        //! the number of filters the last apply() ran inside one pgicp_sensor_chain_* / pgicp_sensor_chain_ext_* call; 0 when it ran none
         size_t lastFusedRun() const { return lastFused; }
         //! The run [k, k + len) as ONE device call: one upload of the cloud, one download of the kept points; the cloud ends in the
         //! state filter-by-filter application leaves (the same labels in the same order, the same bytes).  false: nothing was done
@@ -1746,15 +1874,27 @@ struct PointMatcher {
         bool applySensorChain(size_t k, size_t len, DataPoints &c)
         {
             const int n = (int)c.features.cols(), frows = (int)c.features.rows(), drows = (int)c.descriptors.rows();
-            if (n == 0 || frows < 3 || len > PGICP_CHAIN_MAX_STAGES + 1 || !DeviceBackedDataPointsFilter::deviceWanted("PGSLAM_HOST_SENSOR_CHAIN")) return false;
+            if (n == 0 || frows < 3 || len > PGICP_CHAIN_EXT_MAX_STAGES + 1 || !DeviceBackedDataPointsFilter::deviceWanted("PGSLAM_HOST_SENSOR_CHAIN")) return false;
             SurfaceNormalDataPointsFilter *sn = nullptr;
             MaxDensityDataPointsFilter *mdf = nullptr;
             std::vector<pgicp_chain_stage> stages;
+            ChainRunState made;                              // (what the run has made when a cut looks for its row)
             for (size_t j = k; j < k + len; j++) {
                 DataPointsFilter *f = (*this)[j].get();
                 pgicp_chain_stage s;
                 std::memset(&s, 0, sizeof s);
+                if (auto *p = dynamic_cast<CutAtDescriptorThresholdDataPointsFilter *>(f)) {
+                    s.type = PGICP_CHAIN_CUT_AT_DESCRIPTOR; s.p[0] = (double)made.rowMade(p->descName); s.p[1] = p->useLargerThan ? 1.0 : 0.0; s.p[2] = (double)p->threshold;
+                    if (s.p[0] < 0.0) {
+                        if (!c.descriptorExists(p->descName) || c.getDescriptorDimension(p->descName) != 1) return false;
+                        s.p[0] = (double)PGICP_CHAIN_ROW_DESC; s.p[3] = (double)c.getDescriptorStartingRow(p->descName);
+                    }
+                }
+                if (!made.take(f, &c)) return false;
+                if (s.type) { stages.push_back(s); continue; }
                 if (auto *p = dynamic_cast<SurfaceNormalDataPointsFilter *>(f)) { sn = p; continue; }
+                else if (dynamic_cast<IncidenceAngleDataPointsFilter *>(f)) s.type = PGICP_CHAIN_INCIDENCE_ANGLE;
+                else if (auto *p = dynamic_cast<SphericalityDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_SPHERICALITY; s.p[0] = p->keepUnstructureness ? 1.0 : 0.0; s.p[1] = p->keepStructureness ? 1.0 : 0.0; }
                 else if (auto *p = dynamic_cast<ObservationDirectionDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_OBSERVATION_DIRECTION; for (int a = 0; a < 3; a++) s.p[a] = (double)p->c0[a]; }
                 else if (auto *p = dynamic_cast<SimpleSensorNoiseDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_SIMPLE_SENSOR_NOISE; s.p[0] = (double)p->sensorType; s.p[1] = (double)p->gain; }
                 else if (auto *p = dynamic_cast<OrientNormalsDataPointsFilter *>(f)) { s.type = PGICP_CHAIN_ORIENT_NORMALS; s.p[0] = p->towardCenter ? 1.0 : 0.0; }
@@ -1763,10 +1903,10 @@ struct PointMatcher {
                 else return false;
                 stages.push_back(s);
             }
-            if (!sn) return false;
+            if (!sn || (!made.ext() && stages.size() > PGICP_CHAIN_MAX_STAGES)) return false;
             const bool kn = sn->keepNormals, ke = sn->keepEigenValues, kd = sn->keepDensities;
-            bool obs = false, noise = false;
-            for (auto &s : stages) { obs = obs || s.type == PGICP_CHAIN_OBSERVATION_DIRECTION; noise = noise || s.type == PGICP_CHAIN_SIMPLE_SENSOR_NOISE; }
+            const bool obs = made.obs, noise = made.noise, inc = made.inc, sph = made.sph != nullptr;
+            const bool uns = sph && made.sph->keepUnstructureness, str = sph && made.sph->keepStructureness;
             // the labels the run appends, in the order the filters append them one by one (SurfaceNormal: normals, densities, eigValues)
             typename DataPoints::Labels added;
             for (size_t j = k; j < k + len; j++) {
@@ -1777,23 +1917,42 @@ struct PointMatcher {
                     if (ke) added.push_back(typename DataPoints::Label("eigValues", 3));
                 } else if (dynamic_cast<ObservationDirectionDataPointsFilter *>(f)) added.push_back(typename DataPoints::Label("observationDirections", 3));
                 else if (dynamic_cast<SimpleSensorNoiseDataPointsFilter *>(f)) added.push_back(typename DataPoints::Label("simpleSensorNoise", 1));
+                else if (dynamic_cast<IncidenceAngleDataPointsFilter *>(f)) added.push_back(typename DataPoints::Label("incidenceAngles", 1));
+                else if (dynamic_cast<SphericalityDataPointsFilter *>(f)) {
+                    added.push_back(typename DataPoints::Label("sphericality", 1));
+                    if (uns) added.push_back(typename DataPoints::Label("unstructureness", 1));
+                    if (str) added.push_back(typename DataPoints::Label("structureness", 1));
+                }
             }
             for (auto &l : added) if (c.descriptorExists(l.text)) return false;
             Matrix ox(frows, n), on(3, kn ? n : 0), oe(3, ke ? n : 0), od(1, kd ? n : 0), oo(3, obs ? n : 0), oz(1, noise ? n : 0), oc(drows, drows > 0 ? n : 0);
+            Matrix oi(1, inc ? n : 0), os(1, sph ? n : 0), ou(1, uns ? n : 0), ot(1, str ? n : 0);
             std::vector<int32_t> idx((size_t)n);
             const double md = std::isfinite((double)sn->maxDist) ? (double)sn->maxDist : 1e300;
             int kept = 0;
-            const int st = pgslam_amd::Abi<T>::sensor_chain(sn->ctx, c.features.data(), frows, n, sn->knn, md, kn, ke, kd, (int)stages.size(), stages.data(),
-                                                            drows > 0 ? c.descriptors.data() : nullptr, drows, ox.data(), kn ? on.data() : nullptr,
-                                                            ke ? oe.data() : nullptr, kd ? od.data() : nullptr, obs ? oo.data() : nullptr,
-                                                            noise ? oz.data() : nullptr, drows > 0 ? oc.data() : nullptr, idx.data(), &kept);
+            // (a run without one of the three descriptor filters takes the call it always took)
+            int st;
+            if (made.ext()) {
+                const auto ptr = [](Matrix &m, bool want) { return want ? (void *)m.data() : nullptr; };
+                pgicp_chain_out o;
+                o.xyz = ox.data(); o.nrm = ptr(on, kn); o.nstride = 3; o.eig = ptr(oe, ke); o.dens = ptr(od, kd); o.obs = ptr(oo, obs); o.noise = ptr(oz, noise);
+                o.desc = ptr(oc, drows > 0); o.incidence = ptr(oi, inc); o.sphericality = ptr(os, sph); o.unstructureness = ptr(ou, uns);
+                o.structureness = ptr(ot, str); o.kept_idx = idx.data();
+                st = pgslam_amd::Abi<T>::sensor_chain_ext(sn->ctx, c.features.data(), frows, n, sn->knn, md, kn, ke, kd, (int)stages.size(), stages.data(),
+                                                          drows > 0 ? c.descriptors.data() : nullptr, drows, o, &kept);
+            } else
+                st = pgslam_amd::Abi<T>::sensor_chain(sn->ctx, c.features.data(), frows, n, sn->knn, md, kn, ke, kd, (int)stages.size(), stages.data(),
+                                                      drows > 0 ? c.descriptors.data() : nullptr, drows, ox.data(), kn ? on.data() : nullptr,
+                                                      ke ? oe.data() : nullptr, kd ? od.data() : nullptr, obs ? oo.data() : nullptr,
+                                                      noise ? oz.data() : nullptr, drows > 0 ? oc.data() : nullptr, idx.data(), &kept);
             if (st == PGICP_ERR_ARG) return false;
             check(sn->ctx, st);
             int nd = drows;
             for (auto &l : added) nd += (int)l.span;
             std::vector<const Matrix *> rows;               // the call's output behind each added label
             for (auto &l : added)
-                rows.push_back(l.text == "normals" ? &on : l.text == "densities" ? &od : l.text == "eigValues" ? &oe : l.text == "observationDirections" ? &oo : &oz);
+                rows.push_back(l.text == "normals" ? &on : l.text == "densities" ? &od : l.text == "eigValues" ? &oe : l.text == "observationDirections" ? &oo :
+                               l.text == "simpleSensorNoise" ? &oz : l.text == "incidenceAngles" ? &oi : l.text == "sphericality" ? &os : l.text == "unstructureness" ? &ou : &ot);
             Matrix f(frows, kept), d(nd, kept);
             for (int o = 0; o < kept; o++) {
                 const int i = idx[(size_t)o];
@@ -1817,7 +1976,7 @@ struct PointMatcher {
         {
             lastFused = 0;
             for (size_t k = 0; k < this->size(); k++) {
-                if (const size_t run = sensorChainRunAt(k)) {
+                if (const size_t run = sensorChainRunAt(k, &cloud)) {
                     if (applySensorChain(k, run, cloud)) { lastFused = run; k += run - 1; continue; }
                 }
                 if (k + 1 < this->size()) {
@@ -1828,12 +1987,13 @@ struct PointMatcher {
                 (*this)[k]->inPlaceFilter(cloud);
             }
         }
-        //! every filter of the list has a device form (and the list fits pgicp_filter_cloud): the list as its argument
-        bool deviceSpecs(std::vector<pgicp_filter> &out) const
+        //! every filter of the list has a device form (and the list fits pgicp_filter_cloud): the list as its argument.  `cloud`: the
+        //! cloud the pass is about to see, for the filters whose entry names one of its rows (without it they have no device form)
+        bool deviceSpecs(std::vector<pgicp_filter> &out, const DataPoints *cloud = nullptr) const
         {
             out.clear();
             if (this->size() > PGICP_MAX_FILTERS) return false;
-            for (auto &f : *this) { pgicp_filter s; if (!f->deviceSpec(s)) return false; out.push_back(s); }
+            for (auto &f : *this) { pgicp_filter s; if (!(cloud ? f->deviceSpec(s, *cloud) : f->deviceSpec(s))) return false; out.push_back(s); }
             return true;
         }
         bool allIdentity() const
@@ -1851,7 +2011,7 @@ struct PointMatcher {
     {
         std::vector<pgicp_filter> specs;
         const int n = (int)cloud.getNbPoints();
-        if (n == 0 || cloud.features.rows() < 3 || !filters.deviceSpecs(specs)) return false;
+        if (n == 0 || cloud.features.rows() < 3 || !filters.deviceSpecs(specs, &cloud)) return false;
         RigidTransformation check_t;
         if (!check_t.checkParameters(Tm)) throw std::runtime_error("RigidTransformation: the transformation is not rigid");
         double T16[16];

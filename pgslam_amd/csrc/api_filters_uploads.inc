@@ -8,13 +8,20 @@ bool axis_quantile_args_ok(double dim, double ratio)
     return (dim == 0.0 || dim == 1.0 || dim == 2.0) && std::isfinite(ratio) && r > (T)0 && r < (T)1;
 }
 
-// (*n_quantile: the list's MaxQuantileOnAxis entries -- the launcher wants their scratch)
+// (*n_quantile: the list's MaxQuantileOnAxis entries -- the launcher wants their scratch; *n_cut: its CutAtDescriptor entries
+// (pgicp_descriptor_filters.h) -- they read the descriptors, `drows` rows a point, 0: the call has none)
 template <typename T>
-int filter_specs(pgicp_ctx *c, int nf, const pgicp_filter *f, int *types, double *params, int *n_quantile)
+int filter_specs(pgicp_ctx *c, int nf, const pgicp_filter *f, int drows, int *types, double *params, int *n_quantile, int *n_cut)
 {
-    *n_quantile = 0;
+    *n_quantile = *n_cut = 0;
     for (int k = 0; k < nf; k++) {
-        if (f[k].type < PGICP_FILTER_IDENTITY || f[k].type > PGICP_FILTER_MAX_QUANTILE_ON_AXIS) return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: unknown filter type");
+        if (f[k].type < PGICP_FILTER_IDENTITY || f[k].type > PGICP_FILTER_CUT_AT_DESCRIPTOR) return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: unknown filter type");
+        if (f[k].type == PGICP_FILTER_CUT_AT_DESCRIPTOR) {
+            if (drows <= 0) return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: CutAtDescriptor needs descriptors (this call has none)");
+            if (!(f[k].p[0] >= 0.0 && f[k].p[0] < (double)drows && f[k].p[0] == std::floor(f[k].p[0])) || (f[k].p[1] != 0.0 && f[k].p[1] != 1.0))
+                return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: CutAtDescriptor needs a row in [0, drows) and useLargerThan 0 or 1");
+            ++*n_cut;
+        }
         if (f[k].type == PGICP_FILTER_MAX_QUANTILE_ON_AXIS) {
             if (!axis_quantile_args_ok<T>(f[k].p[0], f[k].p[1]))
                 return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud: MaxQuantileOnAxis needs dim in {0, 1, 2} and a finite ratio in (0, 1)");
@@ -36,6 +43,7 @@ int filter_specs(pgicp_ctx *c, int nf, const pgicp_filter *f, int *types, double
         std::memcpy(params + 8 * k, f[k].p, sizeof f[k].p);
         if (f[k].type == PGICP_FILTER_MAX_POINT_COUNT) params[8 * k + 2] = sizeof(T) == 4 ? 1.0 : 0.0;   // prob = T(maxCount) / T(N)
         if (f[k].type == PGICP_FILTER_MAX_QUANTILE_ON_AXIS) params[8 * k + 1] = (double)(T)f[k].p[1];      // (ratio is held as T)
+        if (f[k].type == PGICP_FILTER_CUT_AT_DESCRIPTOR) params[8 * k + 2] = (double)(T)f[k].p[2];         // (so is the threshold)
     }
     return PGICP_OK;
 }
@@ -50,23 +58,25 @@ int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat, int
     if (T16 && !is_rigid(T16)) return fail(c, PGICP_ERR_NOT_RIGID, "pgicp_filter_cloud: transformation is not rigid");
     int types[PGICP_MAX_FILTERS];
     double params[8 * PGICP_MAX_FILTERS];
-    int n_quantile = 0;
-    { const int st = filter_specs<T>(c, nf, f, types, params, &n_quantile); if (st) return st; }
+    int n_quantile = 0, n_cut = 0;
+    { const int st = filter_specs<T>(c, nf, f, desc ? drows : 0, types, params, &n_quantile, &n_cut); if (st) return st; }
     HIPC(c, hipSetDevice(c->device));
     pgicp_ctx::FilterSet &S = c->fset[c->fset_next];
     c->fset_next = (c->fset_next + 1) & 3;
     // Without a transformation (none, or the identity -- a sensor at the robot's origin) the kept points are the input's
     // own: only the features travel (the predicates look at nothing else, and the ICP wants them on the device anyway), and
-    // what comes back is the list of kept indices, if anything was dropped at all -- the host copies compact themselves.
+    // what comes back is the list of kept indices, if anything was dropped at all -- the host copies compact themselves.  (A
+    // CutAtDescriptor entry does look at the descriptors: with one they travel to the device in any case.)
     bool ident = T16 == nullptr;
     if (T16) {
         ident = true;
         for (int i = 0; i < 12; i++) ident = ident && T16[i] == (i % 5 == 0 ? 1.0 : 0.0);
     }
-    const bool dev_desc = desc && !ident;
+    const bool dev_desc = desc && !ident, in_desc = desc && (!ident || n_cut > 0);     // (which descriptors leave the pass; which enter it)
     const size_t bf = sizeof(T) * (size_t)frows * n, bd = dev_desc ? sizeof(T) * (size_t)drows * n : 0;
     HIPC(c, S.in_f.ensure(bf)); HIPC(c, S.out_f.ensure(bf));
-    if (dev_desc) { HIPC(c, S.in_d.ensure(bd)); HIPC(c, S.out_d.ensure(bd)); }
+    if (in_desc) HIPC(c, S.in_d.ensure(sizeof(T) * (size_t)drows * n));
+    if (dev_desc) HIPC(c, S.out_d.ensure(bd));
     HIPC(c, S.keep.ensure(sizeof(int) * ((size_t)n + 1))); HIPC(c, S.pos.ensure(sizeof(int) * ((size_t)n + 1)));
     HIPC(c, S.bsum.ensure(sizeof(int) * scan_scratch_ints(n)));
     AqScratch aq{};
@@ -74,14 +84,14 @@ int filter_cloud(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat, int
     const bool want_idx = kept_idx || ident;
     if (want_idx) HIPC(c, S.idx.ensure(sizeof(int) * (size_t)n));
     XFER(c, h2d(c, S.in_f.p, feat, bf));
-    if (dev_desc) XFER(c, h2d(c, S.in_d.p, desc, bd));
+    if (in_desc) XFER(c, h2d(c, S.in_d.p, desc, sizeof(T) * (size_t)drows * n));
     // (without a transformation and without a caller's kept_idx the host side only has to close the gaps of the dropped points: a
     // short ascending list of them comes back with the count -- the kept indices, 4 bytes a point, are fetched only when that
     // list would not hold them)
     constexpr int kDropCap = 4096, kDropHead = 256;
     const bool want_drop = ident && !kept_idx;
     if (want_drop) HIPC(c, S.drop.ensure(sizeof(int) * kDropCap));
-    launch_filter_cloud<T>(c->stream, S.in_f.as<T>(), frows, frows, dev_desc ? S.in_d.as<T>() : nullptr, drows, n, nf, types, params,
+    launch_filter_cloud<T>(c->stream, S.in_f.as<T>(), frows, frows, in_desc ? S.in_d.as<T>() : nullptr, drows, n, nf, types, params,
                            ident ? nullptr : T16, rot0, rot1, S.keep.as<int>(), S.pos.as<int>(), S.bsum.as<int>(), S.out_f.as<T>(),
                            dev_desc ? S.out_d.as<T>() : nullptr, want_idx ? S.idx.as<int>() : nullptr, want_drop ? S.drop.as<int>() : nullptr,
                            want_drop ? std::min(kDropCap, n) : 0, n_quantile ? &aq : nullptr);
@@ -150,8 +160,8 @@ int filter_cloud_dev(pgicp_ctx *c, int nf, const pgicp_filter *f, const T *feat,
         return fail(c, PGICP_ERR_ARG, "pgicp_filter_cloud_dev: bad argument");
     int types[PGICP_MAX_FILTERS];
     double params[8 * PGICP_MAX_FILTERS];
-    int n_quantile = 0;
-    { const int st = filter_specs<T>(c, nf, f, types, params, &n_quantile); if (st) return st; }
+    int n_quantile = 0, n_cut = 0;
+    { const int st = filter_specs<T>(c, nf, f, 0, types, params, &n_quantile, &n_cut); if (st) return st; }
     HIPC(c, hipSetDevice(c->device));
     pgicp_ctx::FilterSet &S = c->fset[c->fset_next];
     c->fset_next = (c->fset_next + 1) & 3;

@@ -22,16 +22,18 @@ struct FilterDev { int type; int pad_; double p[8]; };
 #define PGICP_F_RANDOM_SAMPLING 6
 #define PGICP_F_MAX_POINT_COUNT 7
 #define PGICP_F_MAX_QUANTILE_ON_AXIS 8       // (include/pgicp_quantile.h; its kernels: k_axisquantile.inc)
+#define PGICP_F_CUT_AT_DESCRIPTOR 9          // (include/pgicp_descriptor_filters.h; the test: descriptor_filters_host.hpp's cut_keep)
 
 __device__ __forceinline__ float sqrt_rn(float v) { return __builtin_sqrtf(v); }      // (correctly rounded; __fsqrt_rn is the native 1-ulp one)
 __device__ __forceinline__ double sqrt_rn(double v) { return __builtin_sqrt(v); }
 
 struct FilterList { int n; int pad_; FilterDev f[8]; };
 
-// filters [first, last) of the list, all of them point-wise: a point's flag goes to 0 when one of them drops it
+// filters [first, last) of the list, all of them point-wise: a point's flag goes to 0 when one of them drops it (desc, drows: the
+// descriptors a CutAtDescriptor entry reads; the list's check has made sure they are there and hold its row)
 template <typename T>
-__global__ __launch_bounds__(256) void k_filter_points(const T *__restrict__ feat, int fstride, int frows, int n, FilterList fl,
-                                                        int first, int last, int *__restrict__ keep)
+__global__ __launch_bounds__(256) void k_filter_points(const T *__restrict__ feat, int fstride, int frows, const T *__restrict__ desc,
+                                                        int drows, int n, FilterList fl, int first, int last, int *__restrict__ keep)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !keep[i]) return;
@@ -57,6 +59,9 @@ __global__ __launch_bounds__(256) void k_filter_points(const T *__restrict__ fea
             ok = in != (f.p[6] != 0.0);
         } else if (f.type == PGICP_F_REMOVE_NAN) {
             for (int r = 0; r < frows; ++r) ok = ok && q[r] == q[r];
+        } else if (f.type == PGICP_F_CUT_AT_DESCRIPTOR) {
+            // p[0] = the row, p[1] = useLargerThan, p[2] = the threshold (it arrives rounded to T)
+            ok = pgslam_amd::descriptor_filters::cut_keep<T>(desc[(long long)i * drows + (int)f.p[0]], (T)f.p[2], f.p[1] != 0.0);
         }
     }
     if (!ok) keep[i] = 0;

@@ -508,7 +508,7 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
         int e = k;
         while (e < fl.n && fl.f[e].type != PGICP_F_FIX_STEP && fl.f[e].type != PGICP_F_RANDOM_SAMPLING && fl.f[e].type != PGICP_F_MAX_POINT_COUNT &&
                fl.f[e].type != PGICP_F_MAX_QUANTILE_ON_AXIS) ++e;
-        if (e > k) hipLaunchKernelGGL(k_filter_points<T>, grid, block, 0, st, feat, fstride, frows, n, fl, k, e, keep);
+        if (e > k) hipLaunchKernelGGL(k_filter_points<T>, grid, block, 0, st, feat, fstride, frows, desc, drows, n, fl, k, e, keep);
         if (e < fl.n && fl.f[e].type == PGICP_F_MAX_QUANTILE_ON_AXIS) {
             // the third kind of entry: it looks at all the survivors before it decides -- the selection over the flags as they
             // stand, then the cut; the limit stays on the device (aq: the caller's scratch, required with such an entry)
@@ -526,7 +526,8 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
     launch_exclusive_scan(st, keep, n, pos, block_sums);
     Mat34 M;
     for (int i = 0; i < 12; i++) M.v[i] = T16 ? T16[i] : (i % 5 == 0 ? 1.0 : 0.0);
-    hipLaunchKernelGGL(k_filter_compact<T>, grid, block, 0, st, feat, fstride, frows, desc, drows, n, (const int *)keep, (const int *)pos, M,
+    // (descriptors handed in for a CutAtDescriptor entry alone -- no out_desc -- stay behind)
+    hipLaunchKernelGGL(k_filter_compact<T>, grid, block, 0, st, feat, fstride, frows, out_desc ? desc : (const T *)nullptr, drows, n, (const int *)keep, (const int *)pos, M,
                        T16 ? 1 : 0, rot0, rot1, out_feat, out_desc, kept_idx, dropped, dropped_cap);
 }
 

@@ -11,6 +11,8 @@
 #endif
 #include "pgicp_sensor_chain.h"
 #include "pgslam_amd/sensor_chain_host.hpp"
+#include "pgicp_descriptor_filters.h"
+#include "pgslam_amd/descriptor_filters_host.hpp"
 
 namespace pgicp {
 
@@ -369,30 +371,48 @@ void launch_density_compact(hipStream_t st, int n, const int *keep, const int *p
                             const T *nrm, const T *eig, const T *dens, T *out_xyz, T *out_desc, T *out_nrm, int out_nstride, T *out_eig,
                             T *out_dens, int *kept_idx);
 
-// include/pgicp_sensor_chain.h (k_sensor_chain.inc): the stages behind the normals kernel.  ChainSeg: the parameters of every stage
-// type (each appears at most once) and the stages of ONE segment, in list order.  ChainRows: the scratch of a call -- the rows at
-// the points' input indices (null: not made), the survivors' densities by rank, and per dropping stage (at most two) the flags, their
-// scan (n + 1 each; pos[n] = the number kept) and the survivor list.  ChainOut: where the kept points' rows go (null: not asked for)
+// include/pgicp_sensor_chain.h, include/pgicp_descriptor_filters.h (k_sensor_chain.inc): the stages behind the normals kernel.
+// ChainSeg: the parameters of every stage type that appears at most once, and the stages of ONE segment, in list order; a
+// CutAtDescriptor stage drops, so it ends its segment and `cut` is that one's.  ChainCut: the row a cut reads (PGICP_CHAIN_ROW_*;
+// desc_row with ROW_DESC), its direction and threshold.  ChainRows: the scratch of a call -- the rows at the points' input indices
+// (null: not made), the survivors' densities by rank, and per dropping stage (kChainMaxDrops: Shadow, MaxDensity, four cuts) the
+// flags, their scan (n + 1 each; pos[n] = the number kept) and the survivor list.  ChainOut: where the kept points' rows go (null:
+// not asked for)
+constexpr int kChainMaxDrops = 2 + PGICP_CHAIN_EXT_MAX_CUTS;
+template <typename T>
+struct ChainCut { int row, desc_row, larger; T thr; };
 template <typename T>
 struct ChainSeg {
-    int n_ops, op[PGICP_CHAIN_MAX_STAGES];
+    int n_ops, op[PGICP_CHAIN_EXT_MAX_STAGES];
     T c[3]; int toward; T sin_eps; T max_density; unsigned long long seed;
     pgslam_amd::sensor_chain::NoiseModel<T> noise;
+    int keep_uns, keep_str;
+    ChainCut<T> cut;
 };
 template <typename T>
-struct ChainRows { T *nrm, *eig, *dens, *obs, *noise, *dens_rank; int *keep[2], *pos[2], *idx[2], *bsum; };
+struct ChainRows {
+    T *nrm, *eig, *dens, *obs, *noise, *inc, *sph, *uns, *str, *dens_rank;
+    int *keep[kChainMaxDrops], *pos[kChainMaxDrops], *idx[kChainMaxDrops], *bsum;
+};
 template <typename T>
-struct ChainOut { T *xyz, *desc, *nrm; int nstride; T *eig, *dens, *obs, *noise; int *kept_idx; };
+struct ChainOut { T *xyz, *desc, *nrm; int nstride; T *eig, *dens, *obs, *noise, *inc, *sph, *uns, *str; int *kept_idx; };
+// which rows a call makes
+struct ChainHas { bool nrm, eig, dens, obs, noise, inc, sph, uns, str, max_density; };
 template <typename T>
-ChainRows<T> chain_scratch(Carve &cv, int n, bool nrm, bool eig, bool dens, bool obs, bool noise, bool max_density, int drops)
+ChainRows<T> chain_scratch(Carve &cv, int n, const ChainHas &h, int drops)
 {
     ChainRows<T> w{};
-    w.nrm = cv.take<T>(3 * (size_t)n, nrm);
-    w.eig = cv.take<T>(3 * (size_t)n, eig);
-    w.dens = cv.take<T>((size_t)n, dens);
-    w.obs = cv.take<T>(3 * (size_t)n, obs);
-    w.noise = cv.take<T>((size_t)n, noise);
-    w.dens_rank = cv.take<T>((size_t)n, max_density);
+    w.nrm = cv.take<T>(3 * (size_t)n, h.nrm);
+    w.eig = cv.take<T>(3 * (size_t)n, h.eig);
+    w.dens = cv.take<T>((size_t)n, h.dens);
+    w.obs = cv.take<T>(3 * (size_t)n, h.obs);
+    w.noise = cv.take<T>((size_t)n, h.noise);
+    // (placed only when made: a list of the older stages carves what it always carved)
+    if (h.inc) w.inc = cv.take<T>((size_t)n);
+    if (h.sph) w.sph = cv.take<T>((size_t)n);
+    if (h.uns) w.uns = cv.take<T>((size_t)n);
+    if (h.str) w.str = cv.take<T>((size_t)n);
+    w.dens_rank = cv.take<T>((size_t)n, h.max_density);
     for (int k = 0; k < drops; k++) {
         w.keep[k] = cv.take<int>((size_t)n + 1);
         w.pos[k] = cv.take<int>((size_t)n + 1);
@@ -401,9 +421,11 @@ ChainRows<T> chain_scratch(Carve &cv, int n, bool nrm, bool eig, bool dens, bool
     w.bsum = cv.take<int>(scan_scratch_ints(n));
     return w;
 }
+// cuts[k]: the cut of stage k (read only where types[k] is CUT_AT_DESCRIPTOR)
 template <typename T>
 void launch_sensor_chain(hipStream_t st, const T *xyz, int stride, int n, const T *desc, int drows, int n_stages, const int *types,
-                         const ChainSeg<T> &params, const ChainRows<T> &w, DensStat *stat, const ChainOut<T> &out, const int **last_pos);
+                         const ChainSeg<T> &params, const ChainCut<T> *cuts, const ChainRows<T> &w, DensStat *stat, const ChainOut<T> &out,
+                         const int **last_pos);
 
 // include/pgicp_covsample.h (k_covsample.inc): CovarianceSamplingDataPointsFilter
 constexpr int kCovBlocks = 1024;        // the most blocks of a frame reduction: one row of partials each

@@ -19,6 +19,7 @@
 #include "pgicp_ssn_ext.h"
 #include "pgicp_elipsoids.h"
 #include "pgicp_sensor_chain.h"
+#include "pgicp_descriptor_filters.h"
 #include "kernels.hpp"
 #include "seed_source.hpp"
 
@@ -60,6 +61,7 @@ using namespace pgicp;
 #include "api_quantile.inc"           // pgicp_axis_quantile_* (pgicp_quantile.h); the list entry runs in launch_filter_cloud
 #include "api_box.inc"                // pgicp_sampling_surface_normal_*, pgicp_sampling_surface_normal_ext_* (pgicp_ssn_ext.h), pgicp_elipsoids_* (pgicp_elipsoids.h)
 #include "api_sensor_chain.inc"       // pgicp_sensor_chain_* (pgicp_sensor_chain.h)
+#include "api_descriptor_filters.inc" // pgicp_sensor_chain_ext_* (pgicp_descriptor_filters.h)
 
 extern "C" {
 

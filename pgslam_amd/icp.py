@@ -92,6 +92,12 @@ ELIPSOIDS_SYMBOLS = ("pgicp_elipsoids_f32", "pgicp_elipsoids_f64")
 SENSOR_CHAIN_SYMBOLS = ("pgicp_sensor_chain_f32", "pgicp_sensor_chain_f64")
 CHAIN_OBSERVATION_DIRECTION, CHAIN_ORIENT_NORMALS, CHAIN_SHADOW, CHAIN_MAX_DENSITY, CHAIN_SIMPLE_SENSOR_NOISE = range(1, 6)
 CHAIN_MAX_STAGES = 8
+# every symbol the companion header include/pgicp_descriptor_filters.h declares (checked by tests/test_descriptor_filters_host.py)
+DESCRIPTOR_FILTERS_SYMBOLS = ("pgicp_sensor_chain_ext_f32", "pgicp_sensor_chain_ext_f64")
+CHAIN_INCIDENCE_ANGLE, CHAIN_SPHERICALITY, CHAIN_CUT_AT_DESCRIPTOR = 6, 7, 8
+CHAIN_EXT_MAX_STAGES, CHAIN_EXT_MAX_CUTS = 12, 4
+# the row a cut_at_descriptor stage reads (PGICP_CHAIN_ROW_*); an integer names a row of `desc`
+CHAIN_ROWS = dict(desc=0, densities=1, incidence_angles=2, sphericality=3, unstructureness=4, structureness=5, simple_sensor_noise=6)
 SENSOR_SICK_LMS, SENSOR_HOKUYO_URG, SENSOR_HOKUYO_UTM, SENSOR_KINECT, SENSOR_SICK_TIM = range(5)
 
 
@@ -131,9 +137,17 @@ class ChainStage(C.Structure):
     _fields_ = [("type", C.c_int), ("p", C.c_double * 4)]
 
 
+class ChainOut(C.Structure):
+    """pgicp_chain_out (include/pgicp_descriptor_filters.h)"""
+    _fields_ = [("xyz", C.c_void_p), ("nrm", C.c_void_p), ("nstride", C.c_int), ("eig", C.c_void_p), ("dens", C.c_void_p), ("obs", C.c_void_p),
+                ("noise", C.c_void_p), ("desc", C.c_void_p), ("incidence", C.c_void_p), ("sphericality", C.c_void_p),
+                ("unstructureness", C.c_void_p), ("structureness", C.c_void_p), ("kept_idx", C.c_void_p)]
+
+
 FILTER_IDENTITY, FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_REMOVE_NAN, FILTER_FIX_STEP, FILTER_RANDOM_SAMPLING, \
     FILTER_MAX_POINT_COUNT = range(8)
 FILTER_MAX_QUANTILE_ON_AXIS = 8         # (include/pgicp_quantile.h) p[0] = dim, p[1] = ratio
+FILTER_CUT_AT_DESCRIPTOR = 9            # (include/pgicp_descriptor_filters.h) p[0] = descriptor row, p[1] = useLargerThan, p[2] = threshold
 
 
 class CovFrame(C.Structure):
@@ -1132,16 +1146,28 @@ class Context:
 
     # ---- the sensor filter chain (include/pgicp_sensor_chain.h) ------------------------
     SENSOR_CHAIN_STAGES = dict(observation_direction=(CHAIN_OBSERVATION_DIRECTION, 3), orient_normals=(CHAIN_ORIENT_NORMALS, 1),
-                               shadow=(CHAIN_SHADOW, 1), max_density=(CHAIN_MAX_DENSITY, 2), simple_sensor_noise=(CHAIN_SIMPLE_SENSOR_NOISE, 2))
+                               shadow=(CHAIN_SHADOW, 1), max_density=(CHAIN_MAX_DENSITY, 2), simple_sensor_noise=(CHAIN_SIMPLE_SENSOR_NOISE, 2),
+                               incidence_angle=(CHAIN_INCIDENCE_ANGLE, 0), sphericality=(CHAIN_SPHERICALITY, 2),
+                               cut_at_descriptor=(CHAIN_CUT_AT_DESCRIPTOR, 4))
     SENSOR_CHAIN_ROWS = dict(normals=3, eigen_values=3, densities=1)
 
     @classmethod
     def chain_stages(cls, stages):
         """a list of tuples such as ("shadow", 0.1), ("observation_direction", 0, 0, 0), ("max_density", 100.0, 1) as an array of
-        pgicp_chain_stage; a stage may also be given as (type number, p0, ...).  Parameters left out are 0 (max_density's seed: 1)."""
+        pgicp_chain_stage; a stage may also be given as (type number, p0, ...).  Parameters left out are 0 (max_density's seed: 1).
+        ("sphericality", keepUnstructureness, keepStructureness); ("cut_at_descriptor", row, useLargerThan, threshold) with row a
+        name of CHAIN_ROWS, or the index of a row of `desc`."""
         arr = (ChainStage * max(len(stages), 1))()
         for k, s in enumerate(stages):
-            name, args = s[0], [float(v) for v in s[1:]]
+            name, args = s[0], list(s[1:])
+            if name == "cut_at_descriptor" and args:
+                if isinstance(args[0], str):
+                    if args[0] not in CHAIN_ROWS or args[0] == "desc":
+                        raise ValueError(f"sensor_chain: unknown row {args[0]!r} (known: {sorted(set(CHAIN_ROWS) - {'desc'})}, or an index into desc)")
+                    args = [CHAIN_ROWS[args[0]]] + args[1:3]
+                else:
+                    args = [CHAIN_ROWS["desc"]] + args[1:3] + [0] * (3 - len(args)) + [int(args[0])]
+            args = [float(v) for v in args]
             if isinstance(name, str):
                 if name not in cls.SENSOR_CHAIN_STAGES:
                     raise ValueError(f"sensor_chain: unknown stage {name!r} (known: {sorted(cls.SENSOR_CHAIN_STAGES)})")
@@ -1159,11 +1185,13 @@ class Context:
 
     def sensor_chain(self, xyz, knn=10, max_dist=float("inf"), stages=(), keep=("normals", "densities"), desc=None, mem=None, dtype=None):
         """SurfaceNormalDataPointsFilter{knn, maxDist} and a list of stages -- ObservationDirection, OrientNormals, Shadow,
-        MaxDensity, SimpleSensorNoise -- as one device call (pgicp_sensor_chain_*, statement in include/pgicp_sensor_chain.h).  numpy
+        MaxDensity, SimpleSensorNoise -- as one device call (pgicp_sensor_chain_*, statement in include/pgicp_sensor_chain.h); a
+        list that holds IncidenceAngle, Sphericality or CutAtDescriptor goes to pgicp_sensor_chain_ext_*
+        (include/pgicp_descriptor_filters.h) and may be CHAIN_EXT_MAX_STAGES long.  numpy
         in -> numpy out, torch CUDA in -> torch CUDA out; `mem` ("host" or "device"), when given, must name the memory xyz lies in.
         `stages`: see chain_stages.  `keep`: the head's rows, of SENSOR_CHAIN_ROWS.  Returns dict(xyz (k,3), kept_idx (k,) int32,
-        count, descriptors (k,drows) or None, normals, eigen_values, densities, observation_directions (k,3), noise (k,)) for the k
-        kept points in input order; a row that is not kept, or whose stage is not listed, is None."""
+        count, descriptors (k,drows) or None, normals, eigen_values, densities, observation_directions (k,3), noise (k,),
+        incidence_angles, sphericality, unstructureness, structureness (k,)) for the k kept points in input order; a row that is not kept, or whose stage is not listed, is None."""
         unknown = set(keep) - set(self.SENSOR_CHAIN_ROWS)
         if unknown:
             raise ValueError(f"sensor_chain: unknown rows {sorted(unknown)} (known: {sorted(self.SENSOR_CHAIN_ROWS)})")
@@ -1182,15 +1210,26 @@ class Context:
         obs = mk((m, 3)) if CHAIN_OBSERVATION_DIRECTION in listed else None
         noise = mk((m,)) if CHAIN_SIMPLE_SENSOR_NOISE in listed else None
         n_out = C.c_int(0)
-        self._check(s.fn(self.lib, "sensor_chain")(
-            self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
-            C.c_int(int("normals" in keep)), C.c_int(int("eigen_values" in keep)), C.c_int(int("densities" in keep)),
-            C.c_int(len(stages)), arr, ptr(d), C.c_int(drows), ptr(ox), ptr(rows["normals"]), C.c_int(3), ptr(rows["eigen_values"]),
-            ptr(rows["densities"]), ptr(obs), ptr(noise), ptr(oc), ptr(oi), C.byref(n_out)))
+        head = (self.h, C.c_void_p(x.ptr), C.c_int(x.stride), C.c_int(n), C.c_int(x.mem), C.c_int(knn), C.c_double(md),
+                C.c_int(int("normals" in keep)), C.c_int(int("eigen_values" in keep)), C.c_int(int("densities" in keep)),
+                C.c_int(len(stages)), arr, ptr(d), C.c_int(drows))
+        more = dict(incidence_angles=None, sphericality=None, unstructureness=None, structureness=None)
+        if listed & {CHAIN_INCIDENCE_ANGLE, CHAIN_SPHERICALITY, CHAIN_CUT_AT_DESCRIPTOR}:
+            sph = [arr[k] for k in range(len(stages)) if arr[k].type == CHAIN_SPHERICALITY]
+            more["incidence_angles"] = mk((m,)) if CHAIN_INCIDENCE_ANGLE in listed else None
+            more["sphericality"] = mk((m,)) if sph else None
+            more["unstructureness"] = mk((m,)) if sph and sph[0].p[0] == 1.0 else None
+            more["structureness"] = mk((m,)) if sph and sph[0].p[1] == 1.0 else None
+            out = ChainOut(ptr(ox), ptr(rows["normals"]), 3, ptr(rows["eigen_values"]), ptr(rows["densities"]), ptr(obs), ptr(noise), ptr(oc),
+                           ptr(more["incidence_angles"]), ptr(more["sphericality"]), ptr(more["unstructureness"]), ptr(more["structureness"]), ptr(oi))
+            self._check(s.fn(self.lib, "sensor_chain_ext")(*head, C.byref(out), C.byref(n_out)))
+        else:
+            self._check(s.fn(self.lib, "sensor_chain")(*head, ptr(ox), ptr(rows["normals"]), C.c_int(3), ptr(rows["eigen_values"]),
+                                                       ptr(rows["densities"]), ptr(obs), ptr(noise), ptr(oc), ptr(oi), C.byref(n_out)))
         k = n_out.value
         cut = lambda a: a[:k] if a is not None else None
         return dict(xyz=ox[:k, :3], kept_idx=oi[:k], count=k, descriptors=cut(oc), observation_directions=cut(obs), noise=cut(noise),
-                    **{key: cut(a) for key, a in rows.items()})
+                    **{key: cut(a) for key, a in rows.items()}, **{key: cut(a) for key, a in more.items()})
 
     # ---- CovarianceSampling (include/pgicp_covsample.h) ------------------------
     def covariance_sampling(self, xyz, normals, nb_sample=5000, torque_norm=1, descriptors=None, dtype=None, frame=None):

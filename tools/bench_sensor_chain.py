@@ -4,7 +4,8 @@
 # (median of --reps after 10 warm-up calls), device in / device out and host in / host out; beside it the head alone
 # (pgicp_surface_densities_*) and pgicp_normals_max_density_*, device in / device out.  Then DataPointsFilters::apply on the same
 # list through the C++ drop-in (tools/bench_sensor_chain_host.cpp, built here when its binary is missing): the run as one call
-# against the list filter by filter -- what apply did before the call existed --, wall time, median of --host-reps, alternating.
+# against the list filter by filter -- what apply did before the call existed --, wall time, median of --host-reps, alternating; and
+# the same for the eight-filter list of include/pgicp_descriptor_filters.h (IncidenceAngle, Sphericality, two cuts at 1.3 and 0.2).
 # One JSON line.
 import argparse
 import json
@@ -49,7 +50,7 @@ def timed(call, reps):
 
 
 exe = os.path.join(ROOT, "tools", "bench_sensor_chain_host")
-if not os.path.exists(exe):
+if not os.path.exists(exe) or os.path.getmtime(exe) < os.path.getmtime(exe + ".cpp"):
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-pthread", "-I" + os.path.join(ROOT, "include"), exe + ".cpp", "-o", exe,
                            "-L" + os.path.join(ROOT, "pgslam_amd", "lib"), "-lpgicp", "-Wl,-rpath," + os.path.join(ROOT, "pgslam_amd", "lib"),
                            "-Wl,-rpath,/opt/rocm/lib"])
@@ -76,5 +77,8 @@ for name, xyz in clouds.items():
         with open(path, "wb") as fh:
             fh.write(struct.pack("<i", len(xyz)) + xyz.tobytes())
         res["dropin_apply"] = json.loads(subprocess.run([exe, path, repr(md), str(args.host_reps)], capture_output=True, text=True, check=True).stdout)
+        # the list of include/pgicp_descriptor_filters.h: one pgicp_sensor_chain_ext_* call against filter by filter
+        res["dropin_apply_descriptor"] = json.loads(subprocess.run([exe, path, repr(md), str(args.host_reps), "descriptor"], capture_output=True, text=True,
+                                                                   check=True).stdout)
     out[name] = res
 print(json.dumps(out))
