@@ -31,6 +31,7 @@
 #include "../pgicp.h"
 #include "../pgicp_noise.h"
 #include "../pgicp_vardist.h"
+#include "../pgicp_robust.h"
 #include "../pgicp_density.h"
 #include "../pgicp_covsample.h"
 #include "covsample_host.hpp"
@@ -2227,19 +2228,35 @@ struct PointMatcher {
     };
     //! [EXT] RobustOutlierFilter{robustFct, tuning, scaleEstimator, nbIterationForScale, distanceType, approximation}: an
     //! M-estimator weight per pair from e2 = dist / scale^2 (OutlierFiltersImpl.cpp as restated in oracle/icp_oracle.c:
-    //! orc_robust_weights), scale = sqrt(median absolute deviation of the finite squared distances) or 1.  Supported as
-    //! upstream's defaults have it: distanceType point2point and nbIterationForScale 0 (the scale re-estimated at every
-    //! call); no TrimmedDist / MedianDist filter beside it, knn 1.  Inside an ICP run the device applies it
-    //! (pgicp_params.robust_*); this stage-level call is pgicp_outlier_weights under the same parameters.
+    //! orc_robust_weights), scale = sqrt(median absolute deviation of the finite squared distances), 1, or berg's (scaleEstimator
+    //! berg: `tuning` is the target scale and the weight function runs with tuning 1).  distanceType point2plane weighs by the
+    //! squared distance from the matched point's plane; nbIterationForScale n > 0 estimates the scale in the first n iterations
+    //! of an ICP and holds it afterwards (the statement and its marked deviation: include/pgicp_robust.h).  No TrimmedDist /
+    //! MedianDist filter beside it, knn 1; scaleEstimator std is not offered.  These three are the constructor's: loadFromYaml keeps
+    //! refusing them by name, a YAML names upstream's defaults only.  Inside an ICP run the device applies it
+    //! (pgicp_params.robust_*, pgicp_set_robust_ext); this stage-level call is pgicp_outlier_weights under the same settings: one
+    //! pass is iteration 1, and a bare array of distances has no planes -- point2plane is refused there.
     struct RobustOutlierFilter : OutlierFilter {
         ICPChainBase *chain; std::string robustFct, scaleEstimator; T tuning, approximation;
+        std::string distanceType;
+        int nbIterationForScale;
         RobustOutlierFilter(ICPChainBase *c, const std::string &fct = "cauchy", T tun = T(1), const std::string &scale = "mad",
-                            T approx = std::numeric_limits<T>::infinity())
-            : chain(c), robustFct(fct), scaleEstimator(scale), tuning(tun), approximation(approx)
+                            T approx = std::numeric_limits<T>::infinity(), const std::string &dist = "point2point", int nbIter = 0)
+            : chain(c), robustFct(fct), scaleEstimator(scale), tuning(tun), approximation(approx), distanceType(dist), nbIterationForScale(nbIter)
         {
-            fctCode(); scaleCode();
+            fctCode(); scaleCode(); distCode();
             if (!(tuning > T(0))) throw std::runtime_error("RobustOutlierFilter: tuning must be positive");
+            if (nbIterationForScale < 0) throw std::runtime_error("RobustOutlierFilter: nbIterationForScale must be >= 0");
         }
+        int distCode() const
+        {
+            if (distanceType == "point2point") return PGICP_ROBUST_DIST_POINT2POINT;
+            if (distanceType == "point2plane") return PGICP_ROBUST_DIST_POINT2PLANE;
+            throw std::runtime_error("RobustOutlierFilter: unknown distanceType " + distanceType + " (point2point, point2plane)");
+        }
+        //! what pgicp_set_robust_ext is handed; asksNothing(): the filter as pgicp_params alone describes it
+        pgicp_robust_ext ext() const { pgicp_robust_ext x = {distCode(), scaleCode(), nbIterationForScale}; return x; }
+        bool asksNothing() const { return distCode() == PGICP_ROBUST_DIST_POINT2POINT && scaleCode() != PGICP_ROBUST_SCALE_BERG && nbIterationForScale == 0; }
         int fctCode() const
         {
             static const char *names[] = {"cauchy", "welsch", "sc", "gm", "tukey", "huber", "L1"};
@@ -2250,7 +2267,9 @@ struct PointMatcher {
         {
             if (scaleEstimator == "mad") return PGICP_ROBUST_SCALE_MAD;
             if (scaleEstimator == "none") return PGICP_ROBUST_SCALE_NONE;
-            throw std::runtime_error("RobustOutlierFilter: scaleEstimator " + scaleEstimator + " is not supported (mad, none)");
+            if (scaleEstimator == "berg") return PGICP_ROBUST_SCALE_BERG;
+            if (scaleEstimator == "std") throw std::runtime_error("RobustOutlierFilter: scaleEstimator std is not offered (mad, none, berg): its treatment of pairs without a neighbour is not pinned here");
+            throw std::runtime_error("RobustOutlierFilter: scaleEstimator " + scaleEstimator + " is not supported (mad, none, berg)");
         }
         OutlierWeights compute(const DataPoints &, const DataPoints &, const Matches &input) override
         {
@@ -2605,8 +2624,11 @@ struct PointMatcher {
                             else if (kv.first == "nbIterationForScale") nbIter = (int)to_double(kv.second, "nbIterationForScale");
                             else throw std::runtime_error("RobustOutlierFilter: unknown parameter " + kv.first);
                         }
-                        if (dtype != "point2point") throw std::runtime_error("RobustOutlierFilter: distanceType " + dtype + " is not supported (point2point)");
-                        if (nbIter != 0) throw std::runtime_error("RobustOutlierFilter: nbIterationForScale must be 0 (the scale is estimated at every iteration)");
+                        // A YAML still names upstream's defaults only (tests/cpp/test_dropin_cpu.cpp pins these refusals): the filter's
+                        // other settings -- include/pgicp_robust.h -- are given to its constructor, which a chain built in code calls.
+                        if (dtype != "point2point") throw std::runtime_error("RobustOutlierFilter: distanceType " + dtype + " is not supported in a YAML (point2point; the constructor takes point2plane)");
+                        if (nbIter != 0) throw std::runtime_error("RobustOutlierFilter: nbIterationForScale must be 0 in a YAML (the constructor takes a count)");
+                        if (scale == "berg") throw std::runtime_error("RobustOutlierFilter: scaleEstimator berg is not supported in a YAML (mad, none; the constructor takes berg)");
                         outlierFilters.push_back(std::make_shared<RobustOutlierFilter>(this, fct, tun, scale, approx));
                     } else if (m.name == "VarTrimmedDistOutlierFilter" && n_trim++ == 0) {
                         // (every parameter explicit: upstream's defaults are not pinned here -- refuse rather than guess)
@@ -2681,6 +2703,7 @@ struct PointMatcher {
             p.trim_ratio = 1.0;                    // no TrimmedDist filter in the chain: every finite pair passes it
             p.outlier_max_dist = 0.0;
             const VarTrimmedDistOutlierFilter *vt = nullptr;
+            const RobustOutlierFilter *rx = nullptr;
             for (auto &f : outlierFilters) {
                 if (auto v = std::dynamic_pointer_cast<VarTrimmedDistOutlierFilter>(f)) vt = v.get();
                 if (auto t = std::dynamic_pointer_cast<TrimmedDistOutlierFilter>(f)) { p.trim_ratio = (double)t->ratio; p.quantile_scale = 1.0; }
@@ -2688,7 +2711,10 @@ struct PointMatcher {
                 if (auto m = std::dynamic_pointer_cast<MaxDistOutlierFilter>(f)) p.outlier_max_dist = (double)m->maxDist;
                 if (auto rb = std::dynamic_pointer_cast<RobustOutlierFilter>(f)) {
                     if (p.robust_fct != PGICP_ROBUST_NONE) throw std::runtime_error("ICP chain: more than one RobustOutlierFilter");
-                    p.robust_fct = rb->fctCode(); p.robust_scale = rb->scaleCode(); p.robust_tuning = (double)rb->tuning;
+                    // (berg is not a value of pgicp_params.robust_scale: it travels through pgicp_set_robust_ext below)
+                    p.robust_fct = rb->fctCode(); p.robust_scale = rb->scaleCode() == PGICP_ROBUST_SCALE_BERG ? PGICP_ROBUST_SCALE_MAD : rb->scaleCode();
+                    p.robust_tuning = (double)rb->tuning;
+                    rx = rb.get();
                     p.robust_approx = std::isfinite((double)rb->approximation) ? (double)rb->approximation : 0.0;
                 }
             }
@@ -2715,6 +2741,9 @@ struct PointMatcher {
             check(ctx, pgicp_set_params(ctx, &p));
             if (vt) { const double q[3] = {(double)vt->minRatio, (double)vt->maxRatio, (double)vt->lambda}; check(ctx, pgicp_set_var_trim(ctx, q)); }
             else check(ctx, pgicp_set_var_trim(ctx, nullptr));
+            // RobustOutlierFilter's distanceType / berg / nbIterationForScale (pgicp_robust.h); a chain without such settings: off
+            if (rx && !rx->asksNothing()) { const pgicp_robust_ext x = rx->ext(); check(ctx, pgicp_set_robust_ext(ctx, &x)); }
+            else check(ctx, pgicp_set_robust_ext(ctx, nullptr));
             if (const GenericDescriptorOutlierFilter *gd = descriptorFilter()) check(ctx, pgicp_set_descriptor_filter(ctx, gd->mode(), (double)gd->threshold));
             else check(ctx, pgicp_set_descriptor_filter(ctx, PGICP_DESC_FILTER_OFF, 0.0));
         }
@@ -2782,6 +2811,14 @@ struct PointMatcher {
         };
         //! a device copy of a cloud may stand for the cloud itself in operator(): the chain's reading filters change nothing
         //! and no outlier filter looks at the reading's descriptors
+        //! a RobustOutlierFilter with distanceType point2plane reads the reference's normals, whatever the minimiser
+        bool robustNeedsNormals() const
+        {
+            for (auto &f : outlierFilters)
+                if (auto rb = std::dynamic_pointer_cast<RobustOutlierFilter>(f)) if (rb->distCode() == PGICP_ROBUST_DIST_POINT2PLANE) return true;
+            return false;
+        }
+        static void robustNormalsMissing() { throw typename DataPoints::InvalidField("RobustOutlierFilter: Error, cannot find normals in descriptors (distanceType point2plane)."); }
         //! the chain's GenericDescriptorOutlierFilter, or null
         const GenericDescriptorOutlierFilter *descriptorFilter() const
         {
@@ -2898,6 +2935,7 @@ struct PointMatcher {
             this->referenceDataPointsFilters.init();
             this->referenceDataPointsFilters.apply(reference);
             this->prefilteredReferencePtsCount = reference.getNbPoints();
+            if (!reference.descriptorExists("normals") && this->robustNeedsNormals()) this->robustNormalsMissing();
             if (!reference.descriptorExists("normals") && !(this->errorMinimizer && this->errorMinimizer->pointToPoint && !this->errorMinimizer->withCov))
                 throw std::runtime_error("PointToPlaneErrorMinimizer: the reference has no 'normals' descriptor");
             this->matcher->initImpl(reference, 1);
@@ -2914,6 +2952,7 @@ struct PointMatcher {
         {
             if (!this->referenceDataPointsFilters.allIdentity() || !this->deviceReadingEquivalent())
                 throw std::logic_error("ICP::computeOnDevice: the chain filters its clouds or reads their descriptors");
+            if (!reference.hasNormals() && this->robustNeedsNormals()) this->robustNormalsMissing();
             if (!reference.hasNormals() && !(this->errorMinimizer && this->errorMinimizer->pointToPoint && !this->errorMinimizer->withCov))
                 throw std::runtime_error("PointToPlaneErrorMinimizer: the reference has no 'normals' descriptor");
             this->prefilteredReferencePtsCount = reference.n;
@@ -2936,6 +2975,7 @@ struct PointMatcher {
         bool setMap(const pgslam_amd::DeviceCloud<T> &deviceCloud, std::function<DataPoints()> hostCopy)
         {
             if (!deviceMapEquivalent()) throw std::logic_error("ICPSequence::setMap(DeviceCloud): the chain has reference filters");
+            if (!deviceCloud.hasNormals() && this->robustNeedsNormals()) this->robustNormalsMissing();
             if (!deviceCloud.hasNormals() && !(this->errorMinimizer && this->errorMinimizer->pointToPoint && !this->errorMinimizer->withCov))
                 throw std::runtime_error("PointToPlaneErrorMinimizer: the map has no 'normals' descriptor");
             mapPointCloud = DataPoints();
@@ -2953,6 +2993,7 @@ struct PointMatcher {
             this->referenceDataPointsFilters.init();
             this->referenceDataPointsFilters.apply(mapPointCloud);
             this->prefilteredReferencePtsCount = mapPointCloud.getNbPoints();
+            if (!mapPointCloud.descriptorExists("normals") && this->robustNeedsNormals()) this->robustNormalsMissing();
             if (!mapPointCloud.descriptorExists("normals") && !(this->errorMinimizer && this->errorMinimizer->pointToPoint && !this->errorMinimizer->withCov))
                 throw std::runtime_error("PointToPlaneErrorMinimizer: the map has no 'normals' descriptor");
             this->matcher->initImpl(mapPointCloud, 1);

@@ -138,6 +138,9 @@ struct pgicp_ctx {
     double vt[3] = {0.0, 0.0, 0.0};
     DevBuf vt_keys, vt_prob;
     std::vector<double> vt_last;
+    // RobustOutlierFilter's distanceType, berg and nbIterationForScale (pgicp_robust.h, pgicp_set_robust_ext): on, the setting
+    int rx_on = 0;
+    pgicp_robust_ext rx = {0, 0, 0};
     // (ABI 6, added) GenericDescriptorOutlierFilter (pgicp_set_descriptor_filter): PGICP_DESC_FILTER_*, the hard modes' threshold
     int gd_mode = 0;
     double gd_thr = 0.0;
@@ -393,6 +396,7 @@ ChainDev<T> make_chain(const pgicp_params &p)
     ch.robust.k = (T)p.robust_tuning; ch.robust.k2 = ch.robust.k * ch.robust.k;
     ch.robust.cut = (p.robust_approx > 0.0 && std::isfinite(p.robust_approx)) ? 1 : 0;
     { const T a = (T)p.robust_approx; ch.robust.a2 = a * a; }
+    ch.robust.dist = 0; ch.robust.est = ch.robust.mad; ch.robust.nb = 0; ch.robust.target = (T)0;      // (pgicp_robust.h's settings: robust_ext_apply)
     ch.force4dof = p.error_minimizer == PGICP_MINIMIZER_POINT_TO_PLANE_4DOF ? 1 : 0;
     ch.bound_rot = (p.bound_max_rot > 0.0 && std::isfinite(p.bound_max_rot)) ? p.bound_max_rot : 0.0;
     ch.bound_trans = (p.bound_max_trans > 0.0 && std::isfinite(p.bound_max_trans)) ? p.bound_max_trans : 0.0;
@@ -402,6 +406,32 @@ ChainDev<T> make_chain(const pgicp_params &p)
     ch.var_trim = 0; ch.vt_min = ch.vt_max = ch.vt_lambda = 0.0;   // (set by chain_of: a setting of the context)
     ch.gd_mode = PGICP_DESC_FILTER_OFF; ch.gd_thr = (T)0;            // (the same)
     return ch;
+}
+
+// pgicp_set_robust_ext's setting laid over the robust filter of pgicp_params (pgicp_robust.h).  berg: the tuning is the target
+// scale and the weight function runs with tuning 1.  Off, or {point2point, -1, 0}: `rb` stays what make_chain made it.
+template <typename T>
+void robust_ext_apply(const pgicp_ctx *c, const pgicp_params &p, RobustDev<T> &rb)
+{
+    if (!c->rx_on || rb.fct == 0) return;
+    rb.dist = c->rx.distance_type == PGICP_ROBUST_DIST_POINT2PLANE ? 1 : 0;
+    if (c->rx.scale_estimator >= 0) rb.est = c->rx.scale_estimator;
+    rb.mad = rb.est == 1 ? 1 : 0;
+    rb.nb = c->rx.nb_iteration_for_scale;
+    if (rb.est == 2) { rb.target = (T)p.robust_tuning; rb.k = (T)1; rb.k2 = (T)1; }
+}
+// the setting against the robust filter of pgicp_params: checked by the setter and again by every call that runs the chain (the two
+// settings are made separately, as VarTrimmedDist's)
+int robust_ext_check(pgicp_ctx *c, const pgicp_robust_ext &x)
+{
+    const bool asks = x.distance_type != PGICP_ROBUST_DIST_POINT2POINT || x.scale_estimator == PGICP_ROBUST_SCALE_BERG || x.nb_iteration_for_scale != 0;
+    if (asks && c->prm.robust_fct == PGICP_ROBUST_NONE)
+        return fail(c, PGICP_ERR_ARG, "RobustOutlierFilter: distanceType point2plane, scaleEstimator berg and nbIterationForScale need a robustFct (pgicp_params.robust_fct is none)");
+    return PGICP_OK;
+}
+static inline bool robust_plane_dist(const pgicp_ctx *c)
+{
+    return c->rx_on && c->prm.robust_fct != PGICP_ROBUST_NONE && c->rx.distance_type == PGICP_ROBUST_DIST_POINT2PLANE;
 }
 
 // the chain of a call that has sorted its readings (begin_batch): with PGICP_SUM_ORDER_SCAN the reduce kernels are handed the
@@ -414,6 +444,7 @@ ChainDev<T> chain_of(pgicp_ctx *c, const pgicp_params &p)
     ch.var_trim = c->vt_on;
     ch.vt_min = c->vt[0]; ch.vt_max = c->vt[1]; ch.vt_lambda = c->vt[2];
     ch.gd_mode = c->gd_mode; ch.gd_thr = (T)c->gd_thr;              // (the threshold in T, as the comparison is)
+    robust_ext_apply<T>(c, p, ch.robust);
     return ch;
 }
 

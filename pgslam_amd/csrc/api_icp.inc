@@ -63,6 +63,7 @@ int batch_begin(pgicp_ctx *c, int P, const pgicp_problem *pr, F Tpre_of, BatchLa
     if (P > 65535) return fail(c, PGICP_ERR_ARG, "pgicp: at most 65535 problems per batch (the problem index is a launch-grid dimension)");
     c->vt_last.clear();
     { const int vst = var_trim_check(c); if (vst) return vst; }
+    if (c->rx_on) { const int xst = robust_ext_check(c, c->rx); if (xst) return xst; }
     State<T> &S = state<T>(c);
     L.P = P; L.max_n = 0; L.max_rows = 1; L.total = 0; L.table_kinds = 0;
     c->last_icp_P = P;                          // (pgicp_debug_last_matches / _reading_order: the range of their `problem`)
@@ -297,7 +298,22 @@ struct IterPlan {
     int exact_all;      // this iteration must resolve every pair exactly
     int n_pairs;        // pairs a problem has at most: what everything behind the matcher is launched over
     int fold_solve;     // one problem: the solve kernel also does the bookkeeping of k_compact_active (one launch less per iteration)
+    int robust_phase;   // what the robust scale of THIS iteration takes (RobustPhase; robust_phase_of): the one switch that differs
+                        // from iteration to iteration of a call
 };
+// The launches the robust scale of an iteration needs (pgicp_robust.h).  `it`: the iteration (1, 2, ...) the active problems share -- they
+// iterate in lockstep -- or 0: the problems' iterations differ (the residual pass behind a batch of ICPs: each is at its own
+// iterations + 1 >= 2: k_reopen reopens only problems whose status is OK, and such a problem has been through at least one solve,
+// which counts its iteration -- so none of them is at berg's first iteration, the one that reads the median) and the launches are
+// those that any of them may need.  The device decides the rest (k_robust_finish).
+template <typename T>
+int robust_phase_of(const RobustDev<T> &rb, int it)
+{
+    if (rb.fct == 0 || rb.est == 0 || (rb.est == 1 && rb.nb == 0)) return kRobustLegacy;
+    const bool estimate = rb.nb == 0 || (it > 0 ? it <= rb.nb : rb.nb >= 2);
+    if (rb.est == 1) return estimate ? kRobustMad : kRobustHold;
+    return it == 1 ? kRobustMedian : kRobustHold;       // (berg: the recurrence of the later iterations reads no distance)
+}
 template <typename T>
 IterPlan iter_plan(const pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch)
 {
@@ -310,6 +326,7 @@ IterPlan iter_plan(const pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &
     pl.exact_all = robust || ch.var_trim || vardist;
     pl.gd_soft = ch.gd_mode == PGICP_DESC_FILTER_SOFT;
     pl.n_pairs = pl.topk ? L.max_pairs() : L.max_n; pl.fold_solve = L.P == 1 && !pl.topk;
+    pl.robust_phase = robust_phase_of(ch.robust, 1);        // (a single pass is iteration 1; align_batch sets it per iteration)
     return pl;
 }
 
@@ -427,7 +444,13 @@ void pairs_stage(pgicp_ctx *c, const BatchLayout &L, const ChainDev<T> &ch, cons
         });
         part(pl.topk && !ch.var_trim, [&] { select(0, use_seed); });     // (top-K: the iteration's one selection, over the knn * N distances)
         // the scale of this iteration from the distances: median, absolute deviations, their median
-        part(pl.robust, [&] { launch_robust_scale<T>(c->stream, B.probs, B.pair_d2, B.robust_dev, ch, nA, pl.n_pairs, B.active, B.sel_tables, B.qtmp); });
+        // (with pgicp_robust.h's scale settings every selection is an entry of its own, and so is the finish: an iteration that holds
+        //  the scale shows in the profile as the one that spares them)
+        auto scale = [&](int piece) { launch_robust_scale<T>(c->stream, B.probs, B.pair_d2, B.robust_dev, ch, nA, pl.n_pairs, B.active, B.sel_tables, B.qtmp, pl.robust_phase, piece); };
+        part(pl.robust && pl.robust_phase == kRobustLegacy, [&] { scale(-1); });
+        part(pl.robust && (pl.robust_phase == kRobustMad || pl.robust_phase == kRobustMedian), [&] { scale(0); });
+        part(pl.robust && pl.robust_phase == kRobustMad, [&] { scale(1); });
+        part(pl.robust && pl.robust_phase != kRobustLegacy, [&] { scale(2); });
         part(pl.gd_soft, [&] { launch_gd_max<T>(c->stream, B.probs, B.maps, B.pair_slot, nA, pl.n_pairs, B.active); });      // the soft maximum of this iteration
     }
     {
@@ -597,6 +620,8 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         if (!M) return fail(c, PGICP_ERR_ARG, "pgicp_align: unknown map id");
         if (!M->has_nrm && needs_ref_normals(prm))
             return fail(c, PGICP_ERR_ARG, "pgicp_align: reference has no normals descriptor");
+        if (!M->has_nrm && robust_plane_dist(c))
+            return fail(c, PGICP_ERR_ARG, "RobustOutlierFilter: distanceType point2plane, and the map of problem " + std::to_string(p) + " has no normals");
     }
     static const bool host_timing = std::getenv("PGICP_HOST_TIMING") != nullptr;      // diagnostics
     const auto ht0 = std::chrono::steady_clock::now();
@@ -609,6 +634,8 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
     const auto ht1 = std::chrono::steady_clock::now();
     const ChainDev<T> ch = chain_of<T>(c, prm);
     const IterPlan pl = iter_plan(c, L, ch);
+    // (the plan of iteration `at`, 1-based: the robust scale's launches are the one switch that moves with the iteration)
+    auto plan_at = [&](int at) { IterPlan q = pl; q.robust_phase = robust_phase_of(ch.robust, at); return q; };
     const int every = std::max(1, prm.check_every);
     // active-problem accounting for the profile: exact when check_every == 1 and all
     // readings have the same size (the benchmark's case), an upper bound otherwise
@@ -629,13 +656,13 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         c->prof_next_m = total_m * act_p / P;
         if (!(ahead && ahead_mode == 2)) {
             c->sel_guess_first = it == 0 && hint_first ? 1 : 0;
-            one_iteration<T>(c, L, ch, B, pl, true, L.total * act_p / P, act_p, it > 0 ? 1 : 0, ahead ? 2 : 0);
+            one_iteration<T>(c, L, ch, B, plan_at(it + 1), true, L.total * act_p / P, act_p, it > 0 ? 1 : 0, ahead ? 2 : 0);
             c->sel_guess_first = 0;
         }
         ahead = false;
         if (ahead_mode && it + 1 < prm.max_iters) {
             if (c->prof_on) { std::lock_guard<std::mutex> lock(c->prof_m); ahead_events = c->prof_events.size(); }
-            one_iteration<T>(c, L, ch, B, pl, true, L.total, 1, 1, ahead_mode == 1 ? 1 : 0);
+            one_iteration<T>(c, L, ch, B, plan_at(it + 2), true, L.total, 1, 1, ahead_mode == 1 ? 1 : 0);
             ahead = true;
         }
         if ((it + 1) % every == 0 || it + 1 == prm.max_iters) {
@@ -667,7 +694,7 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         HIPC(c, N.out.ensure(cnt_off + sizeof(int) * (size_t)P));
         HIPC(c, N.dist.ensure(sizeof(T) * (size_t)L.total * L.knn));
         HIPC(c, hipMemsetAsync((char *)N.out.p + cnt_off, 0, sizeof(int) * (size_t)P, c->stream));
-        launch_noise_overlap<T>(c->stream, B.probs, B.maps, B.rd_nrm, B.pair_slot, B.pair_d2, B.order, N.vals.template as<T>(),
+        launch_noise_overlap<T>(c->stream, B.probs, B.maps, B.rd, B.rd_nrm, B.pair_slot, B.pair_d2, B.order, N.vals.template as<T>(),
                                 N.off_dev.as<long long>(), N.dist.template as<T>(), B.partials, N.out.as<double>(),
                                 (int *)((char *)N.out.p + cnt_off), P, L.max_pairs(), ch);
         nres.resize(cnt_off + sizeof(int) * (size_t)P);
@@ -689,7 +716,7 @@ int align_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *T_out, pgi
         launch_reopen(c->stream, B.probs, P);
         XFER(c, h2d(c, B.active, c->h_ident.data(), sizeof(int) * P));
         c->prof_next_m = total_m;
-        one_iteration<T>(c, L, ch, B, pl, false, L.total, P, 1);
+        one_iteration<T>(c, L, ch, B, plan_at(0), false, L.total, P, 1);
         HIPC(c, c->sums2.ensure(sizeof(double) * (size_t)P * kSys));
         launch_sum_partials(c->stream, B.partials, reduce_blocks(L.max_pairs()), kSys, B.probs, 0, c->sums2.as<double>(), P);
         rsys.resize((size_t)P * kSys);

@@ -80,6 +80,8 @@ int partial_chain_batch(pgicp_ctx *c, int P, const pgicp_problem *pr, double *ra
         { const int gst = descriptor_filter_check<T>(c, M, pr[p].map_id); if (gst) return gst; }
         if (!M->has_nrm && needs_ref_normals(c->prm))
             return fail(c, PGICP_ERR_ARG, "pgicp: reference has no normals descriptor");
+        if (!M->has_nrm && robust_plane_dist(c))
+            return fail(c, PGICP_ERR_ARG, "RobustOutlierFilter: distanceType point2plane, and the map of problem " + std::to_string(p) + " has no normals");
     }
     BatchLayout L;
     std::vector<ProblemDev> hp;
@@ -165,6 +167,9 @@ int outlier_weights(pgicp_ctx *c, const T *dist2, int n, int mem, T *weights, T 
     if (!c || !dist2 || n <= 0) return fail(c, PGICP_ERR_ARG, "pgicp_outlier_weights: bad argument");
     c->vt_last.clear();
     { const int vst = var_trim_check(c); if (vst) return vst; }
+    if (c->rx_on) { const int xst = robust_ext_check(c, c->rx); if (xst) return xst; }
+    if (robust_plane_dist(c))
+        return fail(c, PGICP_ERR_ARG, "pgicp_outlier_weights: RobustOutlierFilter's distanceType is point2plane, and an array of distances has no geometry");
     HIPC(c, hipSetDevice(c->device));
     const T *d_d2 = dist2;
     T *d_w = weights;
@@ -218,7 +223,9 @@ int outlier_weights(pgicp_ctx *c, const T *dist2, int n, int mem, T *weights, T 
     }
     {
         ProfScope ps(c, PGICP_PROF_TRIM, n);
-        if (robust) launch_robust_raw<T>(c->stream, d_d2, n, make_chain<T>(c->prm).robust, c->robust_dev.as<T>(), c->small.as<T>(), d_w);
+        RobustDev<T> rb = make_chain<T>(c->prm).robust;
+        robust_ext_apply<T>(c, c->prm, rb);             // (one pass is iteration 1: berg's first scale; nb has no effect)
+        if (robust) launch_robust_raw<T>(c->stream, d_d2, n, rb, c->robust_dev.as<T>(), c->small.as<T>(), d_w);
         else launch_trim_raw<T>(c->stream, d_d2, n, (T)ratio, (T)c->prm.quantile_scale, c->small.as<T>(), d_w);
     }
     T h[2];

@@ -88,6 +88,20 @@ struct RobustDev {
     int mad;             // scaleEstimator: 1 mad, 0 none
     int cut;             // approximation given: e2 >= a2 -> weight 0
     T k, k2, a2;
+    // (pgicp_robust.h, added; all zero: the filter as it was) distanceType, scaleEstimator and nbIterationForScale
+    int dist;            // 0 point2point: the weights see d2; 1 point2plane: the squared plane distance (robust_pair_dd)
+    int est;             // 0 none, 1 mad (`mad` says the same), 2 berg: `target` is the tuning and k = k2 = 1
+    int nb;              // 0: the scale is estimated in every iteration; n: in the first n, then held (ProblemDev::robust_s)
+    T target;
+};
+// What launch_robust_scale enqueues for an iteration (IterPlan::robust_phase).  The DEVICE decides problem by problem whether the
+// scale is estimated or held (k_robust_finish: ProblemDev::iters + 1 against nb); the host only spares the launches whose results
+// no active problem will read, by the iteration index the active problems share.
+enum RobustPhase {
+    kRobustLegacy = 0,   // the filter without pgicp_robust.h's scale settings: mad's two selections or none's one, in one scope
+    kRobustMad,          // the median, the absolute deviations, their median
+    kRobustMedian,       // berg's first iteration: the median
+    kRobustHold          // no selection: the count of finite pairs, and what restores limit / rlimit / n_refined
 };
 
 template <typename T>
@@ -161,6 +175,8 @@ struct ProblemDev {
     double qhint[2][4];
     double qrec[2][4];
     double robust_s2;        // RobustOutlierFilter: this iteration's squared scale (k_robust_finish)
+    double robust_s;         // ... and the scale itself, a value of T: what a held iteration keeps and berg's recurrence starts from
+                             // (the root of robust_s2 need not give it back)
     double vt_ratio;         // VarTrimmedDistOutlierFilter: this iteration's tuned ratio (k_var_trim), -1: no positive finite distance
     int vt_count;            // ... and the number of positive finite distances it was chosen over
     int vt_pad_;

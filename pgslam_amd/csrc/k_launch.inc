@@ -383,20 +383,30 @@ void launch_map_values(hipStream_t st, const typename Vec4<T>::type *pts, int fi
 
 template <typename T>
 void launch_robust_scale(hipStream_t st, ProblemDev *probs, const T *d2, T *dev, const ChainDev<T> &ch, int n_active, int max_pairs,
-                         const int *active, int *tables, void *keys)
+                         const int *active, int *tables, void *keys, int phase, int part)
 {
-    if (ch.robust.mad) {
-        ChainDev<T> half = ch;
-        half.trim_ratio = (T)0.5; half.trim_scale = (T)1;
-        // (no guesses: the two medians alternate -- each would start from the other's value)
-        launch_trim_select<T>(st, probs, d2, half, n_active, max_pairs, 0, active, tables, keys, nullptr, 0);
+    // phase: a RobustPhase; part: -1 everything, or (the caller profiles them apart) 0 the first selection, 1 the deviations and
+    // their median, 2 the finish
+    const bool all = part < 0;
+    const bool mad = phase == kRobustMad || (phase == kRobustLegacy && ch.robust.mad);
+    ChainDev<T> half = ch;
+    half.trim_ratio = (T)0.5; half.trim_scale = (T)1;
+    // (no guesses: the two medians alternate -- each would start from the other's value)
+    if (all || part == 0) {
+        if (mad || phase == kRobustMedian) launch_trim_select<T>(st, probs, d2, half, n_active, max_pairs, 0, active, tables, keys, nullptr, 0);
+        // scaleEstimator none: one selection over the resolved distances all the same, for the count of finite pairs
+        else if (phase == kRobustLegacy) launch_trim_select<T>(st, probs, d2, ch, n_active, max_pairs, 0, active, tables, keys, nullptr, 0);
+    }
+    if ((all || part == 1) && mad) {
         hipLaunchKernelGGL(k_robust_absdev<T>, dim3(cdiv(max_pairs, 256), n_active), dim3(256), 0, st, (const ProblemDev *)probs, d2, dev, active);
         launch_trim_select<T>(st, probs, (const T *)dev, half, n_active, max_pairs, 0, active, tables, keys, nullptr, 0);
-    } else {
-        // scaleEstimator none: one selection over the resolved distances all the same, for the count of finite pairs
-        launch_trim_select<T>(st, probs, d2, ch, n_active, max_pairs, 0, active, tables, keys, nullptr, 0);
     }
-    hipLaunchKernelGGL(k_robust_finish<T>, dim3(cdiv(n_active, 64)), dim3(64), 0, st, probs, active, n_active, ch.robust.mad, ch.outlier_max_d2);
+    if (all || part == 2) {
+        // a held iteration ran no selection: the pairs with a neighbour are counted behind the finish, which clears the count
+        const int count = phase == kRobustHold ? 1 : 0;
+        hipLaunchKernelGGL(k_robust_finish<T>, dim3(cdiv(n_active, 64)), dim3(64), 0, st, probs, active, n_active, ch.robust, ch.outlier_max_d2, count);
+        if (count) hipLaunchKernelGGL(k_robust_count<T>, dim3(cdiv(max_pairs, 256 * kRobustCountItems), n_active), dim3(256), 0, st, probs, d2, active);
+    }
 }
 
 void launch_sum_partials(hipStream_t st, const double *partials, int max_blocks, int nt, const ProblemDev *probs,
@@ -419,7 +429,9 @@ void launch_robust_raw(hipStream_t st, const T *d2, int n, const RobustDev<T> &r
         hipLaunchKernelGGL(k_trim_select_raw<T>, dim3(1), dim3(kSelectBlock), 0, st, d2, n, (T)0.5, (T)1, stat);
         hipLaunchKernelGGL(k_robust_absdev_raw<T>, dim3(cdiv(n, 256)), dim3(256), 0, st, d2, n, (const T *)stat, dev);
         hipLaunchKernelGGL(k_trim_select_raw<T>, dim3(1), dim3(kSelectBlock), 0, st, (const T *)dev, n, (T)0.5, (T)1, stat + 2);
-    } else
+    } else if (rb.est == 2)
+        hipLaunchKernelGGL(k_trim_select_raw<T>, dim3(1), dim3(kSelectBlock), 0, st, d2, n, (T)0.5, (T)1, stat);   // (berg, iteration 1: the median)
+    else
         hipLaunchKernelGGL(k_trim_select_raw<T>, dim3(1), dim3(kSelectBlock), 0, st, d2, n, (T)1, (T)1, stat);     // (the finite count)
     if (w) hipLaunchKernelGGL(k_robust_weights_raw<T>, dim3(cdiv(n, 256)), dim3(256), 0, st, d2, n, rb, (const T *)stat, w);
 }
@@ -557,7 +569,7 @@ void launch_filter_cloud(hipStream_t st, const T *feat, int fstride, int frows, 
                                 double *, double *, int, int, const ChainDev<T> &);                                       \
     template void launch_trim_raw<T>(hipStream_t, const T *, int, T, T, T *, T *);                                           \
     template void launch_robust_raw<T>(hipStream_t, const T *, int, const RobustDev<T> &, T *, T *, T *);                 \
-    template void launch_robust_scale<T>(hipStream_t, ProblemDev *, const T *, T *, const ChainDev<T> &, int, int, const int *, int *, void *); \
+    template void launch_robust_scale<T>(hipStream_t, ProblemDev *, const T *, T *, const ChainDev<T> &, int, int, const int *, int *, void *, int, int); \
     template void launch_error_stats<T>(hipStream_t, const MapDev<T> *, int, const int *, const T *, int, const int *,    \
                                         const T *, int, int, const T[3], double *, double *, int);                        \
     template void launch_filter_cloud<T>(hipStream_t, const T *, int, int, const T *, int, int, int, const int *, const double *,   \

@@ -190,6 +190,20 @@ __device__ __forceinline__ T robust_weight(const RobustDev<T> &rb, T dd, T s2)
     return w;
 }
 
+// [EXT] The distance RobustOutlierFilter weighs a pair by (pgicp_robust.h): the matcher's d2, or -- distanceType point2plane -- the
+// squared distance of the step reading p' = Tc (rx, ry, rz) from the plane through the matched map point q with normal n, in T.
+// One statement for k_p2plane_reduce, k_cov_reduce and k_noise_sum (Tc: as for pair_filter_weight).
+template <typename T, typename S>
+__device__ __forceinline__ T robust_pair_dd(const RobustDev<T> &rb, T d2, const S *Tc, T rx, T ry, T rz, T qx, T qy, T qz, T nx, T ny, T nz)
+{
+    if (rb.dist == 0) return d2;
+    T px, py, pz;
+    apply_T<T>(Tc, rx, ry, rz, px, py, pz);
+    const T dx = px - qx, dy = py - qy, dz = pz - qz;
+    const T v = (nx * dx + ny * dy) + nz * dz;
+    return v * v;
+}
+
 // [EXT] GenericDescriptorOutlierFilter's weight of a pair whose neighbour's value is v (pgicp.h, pgicp_set_descriptor_filter; in
 // T): hard modes 1 / 0 by the strict comparison, soft v / gmax -- and 0 when the soft maximum is 0 (deviation b)
 template <typename T>
@@ -249,7 +263,8 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
     const MapDev<T> M = maps[P.map];
     const T limit = (T)P.limit;
     const bool use_nrm = GEN && rd_nrm != nullptr;
-    const bool need_nrm = MIN == 0 || use_nrm;
+    const bool plane_dd = GEN && robust && rb.dist != 0;        // (pgicp_robust.h: the robust weights see plane distances)
+    const bool need_nrm = MIN == 0 || use_nrm || plane_dd;
     const bool gd = GEN && gd_mode != PGICP_DESC_FILTER_OFF;
     const T gmax = GEN ? Bits<T>::val((typename Bits<T>::U)P.gd_key) : (T)0;
     double acc[kSys];
@@ -301,8 +316,10 @@ __global__ __launch_bounds__(kReduceBlock) void k_p2plane_reduce(const ProblemDe
             if constexpr (GEN) {
                 // SurfaceNormal x Robust x GenericDescriptor (pair_filter_weight; the quantile / MaxDist filters are `keep`)
                 const T w = pair_filter_weight<T>(tcur_of<T>(P), use_nrm, qn[it], use_nrm ? mn[it].x : (T)0, use_nrm ? mn[it].y : (T)0,
-                                                  use_nrm ? mn[it].z : (T)0, normal_cos, robust, rb, dds[it], rs2, gd, gd_mode, gd_thr,
-                                                  gd ? gv[it] : (T)0, gmax);
+                                                  use_nrm ? mn[it].z : (T)0, normal_cos, robust, rb,
+                                                  plane_dd ? robust_pair_dd<T>(rb, dds[it], tcur_of<T>(P), qv[it][0], qv[it][1], qv[it][2], mp[it].x, mp[it].y,
+                                                                               mp[it].z, mn[it].x, mn[it].y, mn[it].z) : dds[it],
+                                                  rs2, gd, gd_mode, gd_thr, gd ? gv[it] : (T)0, gmax);
                 if (w == (T)0) continue;
                 wgt = (double)w;
             }
@@ -742,7 +759,9 @@ __global__ __launch_bounds__(kReduceBlock) void k_cov_reduce(const ProblemDev *_
 #pragma unroll
     for (int it = 0; it < kReduceItems; it++) {
         if (!keep[it]) continue;
-        const T dd = dds[it];
+        // (the distance the robust weight saw in the last iteration: robust_pair_dd with the transform that iteration ran with)
+        const T dd = rb.fct != 0 ? robust_pair_dd<T>(rb, dds[it], Tp, qv[it][0], qv[it][1], qv[it][2], mps[it].x, mps[it].y, mps[it].z,
+                                                     mns[it].x, mns[it].y, mns[it].z) : dds[it];
         if constexpr (GD) {
             // the pair's Robust x GenericDescriptor weight in T, as k_p2plane_reduce forms it (the GenericDescriptor soft maximum:
             // the last iteration's); a pair of weight 0 is not an error element
@@ -873,21 +892,56 @@ __global__ __launch_bounds__(256) void k_robust_absdev(const ProblemDev *__restr
     const T med = (T)P.qraw, v = d2[pairs_off(P) + e];
     dev[pairs_off(P) + e] = v > med ? v - med : med - v;               // (+inf stays +inf: not a value of the selection)
 }
+// The scale of an iteration, problem by problem (pgicp_robust.h): it = iters + 1 is the problem's iteration, estimated while
+// nb == 0 || it <= nb and held afterwards (ProblemDev::robust_s carries it from iteration to iteration, in T).  mad: the rounded
+// root of the second median (P.qraw, launch_robust_scale); berg: T(1.9) times the rounded root of the median in the first
+// iteration, then the recurrence towards the target.  `count`: no selection ran in this iteration -- k_robust_count follows and
+// adds the pairs with a neighbour up in n_finite, which is cleared here.
 template <typename T>
-__global__ __launch_bounds__(64) void k_robust_finish(ProblemDev *__restrict__ probs, const int *__restrict__ active, int n_active, int mad, T outlier_max_d2)
+__global__ __launch_bounds__(64) void k_robust_finish(ProblemDev *__restrict__ probs, const int *__restrict__ active, int n_active, RobustDev<T> rb, T outlier_max_d2,
+                                                      int count)
 {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n_active) return;
     ProblemDev &P = probs[active[a]];
     if (P.done) return;
-    T s2 = (T)1;
-    if (mad) { const T sc = sqrt_rn_t((T)P.qraw); s2 = sc * sc; }
-    P.robust_s2 = (double)s2;
+    const int it = P.iters + 1;
+    const bool estimate = rb.nb == 0 || it <= rb.nb;
+    T s = (T)P.robust_s;
+    if (rb.est == 0) s = (T)1;
+    else if (estimate) {
+        if (rb.est == 1) s = sqrt_rn_t((T)P.qraw);
+        else if (it == 1) s = (T)1.9 * sqrt_rn_t((T)P.qraw);
+        else s = (T)0.85 * (s - rb.target) + rb.target;
+    }
+    P.robust_s = (double)s;
+    P.robust_s2 = (double)(s * s);
+    if (count) P.n_finite = 0;
     // a MaxDistOutlierFilter beside the robust one still cuts (the weights multiply): the minimiser's `dist <= limit`; the NEXT
     // pass of the matcher must again find every pair exactly (the medians are over all finite distances): no search cap
     P.limit = (double)outlier_max_d2;
     P.rlimit = __longlong_as_double(0x7FF0000000000000LL);
     P.n_refined = 0;
+}
+// a held iteration's count of the pairs with a neighbour (what a selection leaves in n_finite): an integer sum, no order in it
+constexpr int kRobustCountItems = 16;       // pairs per thread of k_robust_count
+template <typename T>
+__global__ __launch_bounds__(256) void k_robust_count(ProblemDev *__restrict__ probs, const T *__restrict__ d2, const int *__restrict__ active)
+{
+    ProblemDev &P = probs[active[blockIdx.y]];
+    if (P.done) return;
+    const int np = pairs_n(P);
+    const int base = blockIdx.x * (256 * kRobustCountItems);
+    if (base >= np) return;
+    const long long poff = pairs_off(P);
+    // wave ballot and popcount, one integer add a wave (as k_noise_count counts): no LDS
+    int cnt = 0;
+#pragma unroll
+    for (int it = 0; it < kRobustCountItems; it++) {
+        const int e = base + it * 256 + threadIdx.x;
+        cnt += __popcll(__ballot(e < np && d2[poff + e] != Bits<T>::inf()));
+    }
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&P.n_finite, cnt);
 }
 
 // stage-level RobustOutlierFilter::compute over one raw array of squared distances (pgicp_outlier_weights): stat[0] the median,
@@ -907,7 +961,8 @@ __global__ __launch_bounds__(256) void k_robust_weights_raw(const T *__restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     T s2 = (T)1;
-    if (rb.mad) { const T sc = sqrt_rn_t(stat[2]); s2 = sc * sc; }
+    if (rb.est == 2) { const T sc = (T)1.9 * sqrt_rn_t(stat[0]); s2 = sc * sc; }        // (berg, iteration 1: pgicp_robust.h)
+    else if (rb.mad) { const T sc = sqrt_rn_t(stat[2]); s2 = sc * sc; }
     const T v = d2[i];
     w[i] = v == __builtin_huge_val() ? (T)0 : robust_weight<T>(rb, v, s2);      // (no neighbour: never an error element)
 }

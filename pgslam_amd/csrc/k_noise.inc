@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_noise_stage(const T *__restrict__ src, 
 // k_sum_partials T5), the tree position being a sorted position or -- scan_pos -- a position in the caller's reading.
 template <typename T>
 __global__ __launch_bounds__(kReduceBlock) void k_noise_sum(const ProblemDev *__restrict__ probs, const MapDev<T> *__restrict__ maps,
-                                                             const T *__restrict__ rd_nrm, const int *__restrict__ slot,
+                                                             const T *__restrict__ rd_pre, const T *__restrict__ rd_nrm, const int *__restrict__ slot,
                                                              const T *__restrict__ d2, const long long *__restrict__ noise_off,
                                                              T *__restrict__ dist_out, double *__restrict__ partials, int max_blocks,
                                                              T normal_cos, RobustDev<T> rb, const int *__restrict__ scan_pos, int gd_mode,
@@ -55,6 +55,7 @@ __global__ __launch_bounds__(kReduceBlock) void k_noise_sum(const ProblemDev *__
     const T limit = (T)P.limit;
     const bool use_nrm = rd_nrm != nullptr;
     const bool robust = rb.fct != 0;
+    const bool plane_dd = robust && rb.dist != 0;      // (pgicp_robust.h: the robust weights saw plane distances)
     const bool gd = gd_mode != PGICP_DESC_FILTER_OFF;
     const T rs2 = (T)P.robust_s2;
     const T gmax = Bits<T>::val((typename Bits<T>::U)P.gd_last);
@@ -72,8 +73,14 @@ __global__ __launch_bounds__(kReduceBlock) void k_noise_sum(const ProblemDev *__
         if (s >= 0 && dd <= limit) {
             const int i = knn == 1 ? e : e / knn;
             T bx = (T)0, by = (T)0, bz = (T)0;
-            if (use_nrm) { const auto mn = M.nrm[2 * (long long)s + 1]; bx = mn.x; by = mn.y; bz = mn.z; }
-            const T w = pair_filter_weight<T>(Tp, use_nrm, use_nrm ? rd_nrm + 3 * (P.off + i) : nullptr, bx, by, bz, normal_cos, robust, rb, dd, rs2, gd, gd_mode,
+            if (use_nrm || plane_dd) { const auto mn = M.nrm[2 * (long long)s + 1]; bx = mn.x; by = mn.y; bz = mn.z; }
+            T rdd = dd;
+            if (plane_dd) {
+                const auto mp = M.nrm[2 * (long long)s];
+                const T *q = rd_pre + 3 * (P.off + i);
+                rdd = robust_pair_dd<T>(rb, dd, Tp, q[0], q[1], q[2], mp.x, mp.y, mp.z, bx, by, bz);
+            }
+            const T w = pair_filter_weight<T>(Tp, use_nrm, use_nrm ? rd_nrm + 3 * (P.off + i) : nullptr, bx, by, bz, normal_cos, robust, rb, rdd, rs2, gd, gd_mode,
                                               gd_thr, gd ? M.val[s - M.first] : (T)0, gmax);
             if (w != (T)0) {
                 dist = sqrt_rn_t(dd);
@@ -132,12 +139,12 @@ void launch_noise_stage(hipStream_t st, const T *src, int stride, int n, T *dst,
 }
 // out: {S, nb} per problem (2 P doubles); count: P ints, zero on entry (the caller clears them on the same stream)
 template <typename T>
-void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, const T *rd_nrm, const int *slot, const T *d2,
+void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, const T *rd_pre, const T *rd_nrm, const int *slot, const T *d2,
                           const int *order, const T *noise, const long long *noise_off, T *dist, double *partials, double *out, int *count,
                           int P, int max_pairs, const ChainDev<T> &ch)
 {
     const int nb = reduce_blocks(max_pairs);
-    hipLaunchKernelGGL(k_noise_sum<T>, dim3(nb, P), dim3(kReduceBlock), 0, st, probs, maps, rd_nrm, slot, d2, noise_off, dist, partials, nb,
+    hipLaunchKernelGGL(k_noise_sum<T>, dim3(nb, P), dim3(kReduceBlock), 0, st, probs, maps, rd_pre, rd_nrm, slot, d2, noise_off, dist, partials, nb,
                        ch.normal_cos, ch.robust, ch.scan_pos, ch.gd_mode, ch.gd_thr);
     hipLaunchKernelGGL(k_sum_partials, dim3(P), dim3(256), 0, st, (const double *)partials, nb, 2, probs, 0, out);
     hipLaunchKernelGGL(k_noise_count<T>, dim3(cdiv(max_pairs, 256), P), dim3(256), 0, st, probs, (const T *)dist, order, noise, noise_off,
@@ -147,7 +154,7 @@ void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<
 #define INSTANTIATE_NOISE(T)                                                                                                           \
     template void launch_simple_sensor_noise<T>(hipStream_t, const T *, int, int, int, T, T, T, T, T *);                               \
     template void launch_noise_stage<T>(hipStream_t, const T *, int, int, T *, int *);                                                 \
-    template void launch_noise_overlap<T>(hipStream_t, const ProblemDev *, const MapDev<T> *, const T *, const int *, const T *,       \
+    template void launch_noise_overlap<T>(hipStream_t, const ProblemDev *, const MapDev<T> *, const T *, const T *, const int *, const T *, \
                                           const int *, const T *, const long long *, T *, double *, double *, int *, int, int,         \
                                           const ChainDev<T> &);
 INSTANTIATE_NOISE(float)

@@ -92,7 +92,7 @@ void launch_simple_sensor_noise(hipStream_t st, const T *xyz, int stride, int n,
 template <typename T>
 void launch_noise_stage(hipStream_t st, const T *src, int stride, int n, T *dst, int *flag);
 template <typename T>
-void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, const T *rd_nrm, const int *slot, const T *d2,
+void launch_noise_overlap(hipStream_t st, const ProblemDev *probs, const MapDev<T> *maps, const T *rd_pre, const T *rd_nrm, const int *slot, const T *d2,
                           const int *order, const T *noise, const long long *noise_off, T *dist, double *partials, double *out, int *count,
                           int P, int max_pairs, const ChainDev<T> &ch);
 // KDTreeVarDistMatcher's per-point radii (k_vardist.inc, include/pgicp_vardist.h): staging a device row; the cut of the matcher's
@@ -113,7 +113,7 @@ template <typename T>
 void launch_robust_raw(hipStream_t st, const T *d2, int n, const RobustDev<T> &rb, T *dev, T *stat, T *w);
 template <typename T>
 void launch_robust_scale(hipStream_t st, ProblemDev *probs, const T *d2, T *dev, const ChainDev<T> &ch, int n_active, int max_pairs,
-                         const int *active, int *tables, void *keys);
+                         const int *active, int *tables, void *keys, int phase, int part);
 template <typename T>
 void launch_var_trim(hipStream_t st, ProblemDev *probs, const T *d2, const int *active, int n_active, void *keys_a, void *keys_b,
                      double min_ratio, double max_ratio, double lambda);

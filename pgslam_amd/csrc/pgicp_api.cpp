@@ -7,6 +7,7 @@
 #include "pgicp.h"
 #include "pgicp_noise.h"
 #include "pgicp_vardist.h"
+#include "pgicp_robust.h"
 #include "pgicp_density.h"
 #include "pgicp_covsample.h"
 #include "pgslam_amd/covsample_host.hpp"
@@ -62,6 +63,7 @@ using namespace pgicp;
 #include "api_box.inc"                // pgicp_sampling_surface_normal_*, pgicp_sampling_surface_normal_ext_* (pgicp_ssn_ext.h), pgicp_elipsoids_* (pgicp_elipsoids.h)
 #include "api_sensor_chain.inc"       // pgicp_sensor_chain_* (pgicp_sensor_chain.h)
 #include "api_descriptor_filters.inc" // pgicp_sensor_chain_ext_* (pgicp_descriptor_filters.h)
+#include "api_robust.inc"             // pgicp_set_robust_ext, pgicp_get_robust_ext (pgicp_robust.h)
 
 extern "C" {
 

@@ -59,6 +59,10 @@ ABI_SYMBOLS = [
 SUM_ORDER_SORTED, SUM_ORDER_SCAN = 0, 1
 # every symbol the companion header include/pgicp_vardist.h declares (checked by tests/test_var_dist_host.py)
 VARDIST_SYMBOLS = ("pgicp_arm_reading_radii_f32", "pgicp_arm_reading_radii_f64")
+# every symbol the companion header include/pgicp_robust.h declares (checked by tests/test_robust_ext_host.py)
+ROBUST_SYMBOLS = ("pgicp_set_robust_ext", "pgicp_get_robust_ext")
+ROBUST_DIST = dict(point2point=0, point2plane=1)
+ROBUST_SCALE = dict(none=0, mad=1, berg=2)
 # every symbol the companion header include/pgicp_noise.h declares (checked by tests/test_noise_overlap_host.py)
 NOISE_SYMBOLS = (
     "pgicp_simple_sensor_noise_f32", "pgicp_simple_sensor_noise_f64",
@@ -121,6 +125,11 @@ class Stats(C.Structure):
                     max_iter_reached=bool(self.max_iter_reached), overlap=self.overlap, residual=self.residual,
                     trim_limit=self.trim_limit, n_kept=self.n_kept, n_finite=self.n_finite,
                     cov=np.array(self.cov[:]).reshape(6, 6))
+
+
+class RobustExt(C.Structure):
+    """pgicp_robust_ext (include/pgicp_robust.h)"""
+    _fields_ = [("distance_type", C.c_int), ("scale_estimator", C.c_int), ("nb_iteration_for_scale", C.c_int)]
 
 
 class Problem(C.Structure):
@@ -562,6 +571,25 @@ class Context:
         r = C.c_double(0)
         self._check(self.lib.pgicp_last_var_trim_ratio(self.h, C.c_int(problem), C.byref(r)))
         return r.value
+
+    def set_robust_ext(self, distance_type="point2point", scale_estimator=None, nb_iteration_for_scale=0):
+        """[EXT] RobustOutlierFilter's distanceType ("point2point" / "point2plane"), scaleEstimator ("none" / "mad" / "berg"; None:
+        what the parameters' robust_scale says) and nbIterationForScale (pgicp_set_robust_ext, include/pgicp_robust.h).  A setting
+        of the context: it stays until set again or cleared.  The names' codes are accepted too."""
+        x = RobustExt(ROBUST_DIST.get(distance_type, distance_type), -1 if scale_estimator is None else ROBUST_SCALE.get(scale_estimator, scale_estimator),
+                      int(nb_iteration_for_scale))
+        self._check(self.lib.pgicp_set_robust_ext(self.h, C.byref(x)))
+
+    def clear_robust_ext(self):
+        """takes set_robust_ext's setting out: the context is what it was without it"""
+        self._check(self.lib.pgicp_set_robust_ext(self.h, None))
+
+    def get_robust_ext(self):
+        """dict(distance_type, scale_estimator, nb_iteration_for_scale) of codes, or None when the setting is off."""
+        on = C.c_int(0)
+        x = RobustExt()
+        self._check(self.lib.pgicp_get_robust_ext(self.h, C.byref(on), C.byref(x)))
+        return dict(distance_type=x.distance_type, scale_estimator=x.scale_estimator, nb_iteration_for_scale=x.nb_iteration_for_scale) if on.value else None
 
     _DESC_MODES = {None: 0, "larger": 1, "smaller": 2, "soft": 3}
 

@@ -18,7 +18,7 @@ run() { # tag, sanitizer flags, env, exe args...
 for SAN in asan tsan; do
   if [ $SAN = asan ]; then F="-fsanitize=address,undefined -fno-omit-frame-pointer"; export ASAN_OPTIONS=detect_leaks=1:halt_on_error=0 UBSAN_OPTIONS=print_stacktrace=1
   else F="-fsanitize=thread"; export PGSLAM_TEST_TIME_SCALE=20 TSAN_OPTIONS="halt_on_error=0 second_deadlock_stack=1"; fi
-  for t in test_dropin_cpu test_slam_cpu test_instantiation; do
+  for t in test_dropin_cpu test_slam_cpu test_instantiation test_robust_ext_cpu; do
     g++ -std=c++17 -O1 -g $F -pthread -Iinclude tests/cpp/$t.cpp -o $OUT/${t}_$SAN $LINK 2> $OUT/build_${t}_$SAN.log || { echo "build ${t}_$SAN FAILED"; continue; }
     HIP_VISIBLE_DEVICES=-1 ROCR_VISIBLE_DEVICES=-1 run ${t}_$SAN $OUT/${t}_$SAN
   done
